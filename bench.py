@@ -29,6 +29,12 @@ one GPU) also runs abbreviated legs of BASELINE configs 3 (`kitti`), 4 (`ncd-inc
 Infinity Cache (`kitti-large`) and rank 0's share of config 5 (`kitti-dp8-rank`); each prints its OWN compact line
 (`{"leg": ...}`) BEFORE the record.  The full (un-cut) records go to --full-record-dir (default gpurun_out/bench_records/).
 DESIGN.md §5 explains every field.
+
+`--steps K` is the number of timed steps (one window of K steps; `--repeats R` times R windows of K) and `ms_per_step` the
+time one of them took.  `--dump-outputs DIR` (batch workloads) writes what the last timed step of the requested workload
+handed its caller as DIR/<name>.npy: `loss` (float64), `pred` (float32, one per point of the batch), `grad_features_<s>` (the
+feature-table gradients, top-down) and `grad_decoder_<j>` (W1, b1, W2, b2, w3, b3), at most 64 MB in all (an array beyond its
+share keeps a fixed, seeded sample of its elements).  Such a run's inputs are the same from run to run (run_batch(outputs=)).
 """
 import argparse
 import json
@@ -36,7 +42,9 @@ import os
 import statistics
 import sys
 import time
+import zlib
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -49,6 +57,7 @@ from shine_mapping_amd.benchlib import (WORKLOADS, gpu_iteration_n4096, kernel_r
                                         run_dp_rank, run_incremental)
 
 RECORD_LIMIT = 4096  # bytes of the final line (the 22 kB line of round 5 was not parsed by the driver)
+DUMP_LIMIT = 64 << 20  # bytes of --dump-outputs, all files together
 
 
 def cpu_baseline(wl, seconds=12.0, n=4096, max_iters=400, regularize=False):
@@ -248,6 +257,26 @@ def write_full(directory, name, rec):
         return None
 
 
+def dump_outputs(directory, tensors, limit=DUMP_LIMIT):
+    """host tensors -> <directory>/<name>.npy (float32, or float64 where the tensor is), at most `limit` bytes in all: the
+    smallest arrays go first and whole; an array larger than its share of what is left keeps a sorted sample of its (flat)
+    elements drawn with a seed of its name -> {name: elements written}"""
+    os.makedirs(directory, exist_ok=True)
+    items = sorted(((k, v.numpy()) for k, v in tensors.items()), key=lambda kv: kv[1].size)
+    left = limit - 1024 * len(items)  # (the .npy headers)
+    written = {}
+    for i, (name, a) in enumerate(items):
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        share = left // (len(items) - i)
+        if a.nbytes > share:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            a = a.reshape(-1)[np.unique(rng.integers(0, a.size, size=share // a.itemsize))]
+        np.save(os.path.join(directory, name + ".npy"), a)
+        left -= a.nbytes
+        written[name] = int(a.size)
+    return written
+
+
 def emit(obj):
     """one JSON object = one stdout line, flushed (stderr chatter must not end up inside it)"""
     sys.stderr.flush()
@@ -274,8 +303,9 @@ def main():
     ap.add_argument("--sync-frames", action="store_true",
                     help="ncd-incre: one host synchronisation at the end of every frame (a frame's latency) instead of letting the "
                          "host run a frame ahead of the device (throughput)")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed windows of exactly --steps steps each; the line reports the median window")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed windows of exactly --steps steps each (R windows time R x K steps); the line reports the median "
+                         "window")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-tier-a", action="store_true", help="ncd-incre: skip the Tier A (unchanged driver's loop) measurement")
     ap.add_argument("--no-extra-configs", action="store_true",
@@ -304,6 +334,9 @@ def main():
                     help="initialise torch.distributed (RCCL) and run the data-parallel code path even at world size 1")
     ap.add_argument("--full-record-dir", default=os.path.join(ROOT, "gpurun_out", "bench_records"),
                     help="where the un-cut record of every leg is written (the printed lines are cut to < 4 kB)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="batch workloads: after the timed steps write the last step's loss, predictions and gradients as "
+                         "DIR/<name>.npy (<= 64 MB in all); the run's inputs are the same from run to run")
     ap.add_argument("--launch-check", action="store_true",
                     help="launcher / rendezvous check only (no GPU work): used by tests/test_bench_launch.py")
     args = ap.parse_args()
@@ -327,13 +360,19 @@ def main():
     full_dir = args.full_record_dir
 
     if incre:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: batch workloads only (not ncd-incre)")
         if world > 1:
             raise SystemExit("ncd-incre is a single-GPU workload (BASELINE.json config 4)")
         rec = run_incremental(args, dev, args.steps, args.warmup, cpu_baseline=cb)
         emit(compact(rec, write_full(full_dir, "ncd-incre", rec)))
         return
 
-    rec = run_batch(args, args.workload, dist, world, rank, dev, args.steps, args.warmup, cpu_baseline=cb)
+    outputs = {} if args.dump_outputs else None
+    rec = run_batch(args, args.workload, dist, world, rank, dev, args.steps, args.warmup, cpu_baseline=cb, outputs=outputs)
+    if outputs:
+        written = dump_outputs(args.dump_outputs, outputs)
+        print("dumped %d arrays (%d elements) to %s" % (len(written), sum(written.values()), args.dump_outputs), file=sys.stderr)
     if default_run and world == 1 and not args.no_extra_configs:
         # BASELINE configs 3, 4 and 5's rank share under the same driver clock: abbreviated legs (fewer steps, shorter CPU
         # samples), each printed as its own compact line BEFORE the record.  A failing leg is reported, never allowed to take

@@ -1,6 +1,7 @@
 """benchlib — the measured legs behind bench.py (the CLI and the printed record live there).
 
-  timed_windows        THE timed region of a batch workload: R windows of exactly K steps between barrier + synchronize pairs
+  timed_windows        THE timed region of a batch workload: R (default 1) windows of exactly K steps between barrier +
+                       synchronize pairs
   run_batch            a batch-mode workload (BASELINE configs 2, 3 and `kitti-large`; config 5 under torch.distributed)
   run_incremental      BASELINE config 4 (shine_incre.py:86-195), Tier B loop + the Tier A loop body beside it
   run_dp_rank          rank 0's share of BASELINE config 5 on ONE GPU, reduced with the eight ranks' REAL messages
@@ -534,8 +535,8 @@ def launch_check(args, dist, world, rank, backend):
 def timed_windows(run, steps, repeats, barrier, dist, world, dev):
     """THE TIMED REGION.  `run(k)` issues exactly k steps of the hot path (HIP-graph replays or eager launches, one fresh batch
     per step; under data parallelism the exchange is inside the step).  R windows of exactly K = `steps` steps, each bracketed by
-    barrier + torch.cuda.synchronize() on BOTH sides and scored by its SLOWEST rank; the line reports the MEDIAN window (one
-    window of the driver's K = 20 is ~2 ms and says nothing about its own spread).
+    barrier + torch.cuda.synchronize() on BOTH sides and scored by its SLOWEST rank; the line reports the MEDIAN window.
+    bench.py's default R = 1: the timed region is then exactly the K steps --steps asks for.
     -> (seconds of the median window, [seconds per window], {"max","min"} ms per step over the ranks or None)"""
     windows, rank_windows = [], []
     for _ in range(max(1, int(repeats))):
@@ -562,9 +563,16 @@ def timed_windows(run, steps, repeats, barrier, dist, world, dev):
 
 
 
+DUMP_PREHEAT_STEPS = 400  # the preheat of a run whose outputs are kept: a fixed count, so the batch a step draws is too
+
+
 def run_batch(args, workload, dist, world, rank, dev, steps, warmup, cpu_baseline=None, with_like_for_like=True,
-              with_iteration=True, cpu_seconds=12.0):
-    """One batch-mode workload -> the bench record (dict on rank 0, None elsewhere)."""
+              with_iteration=True, cpu_seconds=12.0, outputs=None):
+    """One batch-mode workload -> the bench record (dict on rank 0, None elsewhere).
+
+    `outputs` (a dict, or None): filled on rank 0 with what the last timed step handed its caller, as host tensors — loss,
+    per-point prediction, feature and decoder gradients.  Its inputs are then the same from run to run: the pool is planned
+    in canonical order and the preheat is DUMP_PREHEAT_STEPS steps instead of a time-sized stretch."""
     from shine_mapping_amd import StepOptions, fused_train_step, synth
     from shine_mapping_amd import dp as shine_dp
     from shine_mapping_amd.sampler import SortedPool
@@ -589,7 +597,7 @@ def run_batch(args, workload, dist, world, rank, dev, steps, warmup, cpu_baselin
     # (canonical: the plan leaves the samples of one node in atomic-retirement order, which differs between processes)
     torch.cuda.synchronize()
     t_plan = time.perf_counter()
-    spool = SortedPool(octree, pool.coord, pool.sdf_label, pool.weight, seed=1000, canonical=use_dist)
+    spool = SortedPool(octree, pool.coord, pool.sdf_label, pool.weight, seed=1000, canonical=use_dist or outputs is not None)
     torch.cuda.synchronize()
     pool_plan_ms = (time.perf_counter() - t_plan) * 1e3
     feats, dec_params = list(octree.hier_features), decoder.fused_params()
@@ -641,14 +649,15 @@ def run_batch(args, workload, dist, world, rank, dev, steps, warmup, cpu_baselin
         primed = [False]
         def run_micro(idx, n_surf):
             """the rank's slice as m contiguous micro-batches: fused step (marks its rows) -> pack + all-gather; then add back"""
-            loss = None
+            loss, preds = None, []
             for k in range(m):
                 a_, b_ = k * points // m, (k + 1) * points // m
-                l_, _, _ = fused_train_step(octree, decoder, None, None, None, opts_last if k == m - 1 else opts, n_surf=n_surf,
-                                            pool=spool, idx=idx[a_:b_], touched=reducer.flags)
+                l_, p_, _ = fused_train_step(octree, decoder, None, None, None, opts_last if k == m - 1 else opts, n_surf=n_surf,
+                                             pool=spool, idx=idx[a_:b_], touched=reducer.flags)
                 loss = l_ if loss is None else loss + l_
+                preds.append(p_)
                 reducer.exchange(finish=k == m - 1)
-            return loss
+            return loss, preds
 
         if use_dist and kind == "gather":  # one real step through the candidate == the dense all-reduce of the same grads
             ok = 1
@@ -680,7 +689,7 @@ def run_batch(args, workload, dist, world, rank, dev, steps, warmup, cpu_baselin
         # under the fused kernel was measured slower — profiles/r03_ab_experiments.txt block 9.)
         def step_body():
             """draw (its first pass also clears the gradient bucket: opt.zero_grad()) -> fused step on this rank's slice
-            (-> exchange)"""
+            (-> exchange) -> (loss, [prediction of each fused step])"""
             # this rank's contiguous slice of the ONE global sorted draw (same seed / draw count on every rank): only the
             # slice's indices are generated (shine_sample_sorted_slice), so the draw does not grow with the world size
             idx = spool.draw(points, out=idx_buf, zero=reducer.flat, graph_safe=True, n_global=n_global,
@@ -702,7 +711,7 @@ def run_batch(args, workload, dist, world, rank, dev, steps, warmup, cpu_baselin
                     reducer.all_reduce_touched(flags)
                 else:
                     reducer.all_reduce_grads()
-            return loss
+            return loss, [pred]
 
         # The loop body has no host sync and no allocation outside torch's allocator, so it is captured into HIP graphs and
         # replayed (launch-bound inner loops belong in hipGraphs): one graph of `--graph-steps` U consecutive steps — a
@@ -725,7 +734,7 @@ def run_batch(args, workload, dist, world, rank, dev, steps, warmup, cpu_baselin
                     graph_u = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph_u):
                         for _ in range(U):
-                            loss_u = step_body()
+                            loss_u = step_body()  # (the graph's outputs: those of its last step)
                 launch = "hipgraph, %d step%s per replay, fresh batch per step%s%s" % (
                     U, "s" if U > 1 else "", " (collectives captured)" if use_dist else "",
                     ", first pass of the next draw on the step's reduction launch" if rider is not None else "")
@@ -736,7 +745,7 @@ def run_batch(args, workload, dist, world, rank, dev, steps, warmup, cpu_baselin
                 torch.cuda.synchronize()
 
         def run(k):
-            """exactly k steps -> the last step's loss (also kept as run.last_loss)"""
+            """exactly k steps -> the last step's loss (also kept as run.last_loss; its predictions as run.last_pred)"""
             out = None
             if graph_1 is None:
                 for _ in range(k):
@@ -750,12 +759,17 @@ def run_batch(args, workload, dist, world, rank, dev, steps, warmup, cpu_baselin
                     graph_1.replay()
                     out = loss_1
             if out is not None:
-                run.last_loss = out
-            return out
+                run.last_loss, run.last_pred = out
+            return None if out is None else out[0]
 
-        run.last_loss = None
+        run.last_loss = run.last_pred = None
 
-        return dict(run=run, launch=launch, reducer=reducer, kind=kind, micro=m, keep=(graph_u, graph_1, flags))
+        def last_grads():
+            """the gradient tables the last step left (the exchange's result under data parallelism)"""
+            return [p.grad for p in feats], [p.grad for p in dec_params]
+
+        return dict(run=run, launch=launch, reducer=reducer, kind=kind, micro=m, keep=(graph_u, graph_1, flags),
+                    last_grads=last_grads)
 
     def build_chain_runner():
         """One rank, batches of >= 16 K points (round 6): a step is TWO launches.  The step's reduction launch also draws the NEXT
@@ -790,8 +804,11 @@ def run_batch(args, workload, dist, world, rank, dev, steps, warmup, cpu_baselin
         chain.prime()
 
         def step_body(par):
-            return fused_train_step(octree, decoder, None, None, None, chain_opts[par], n_surf=chain.surf_parts[par] if eik else None,
-                                    pool=spool, idx=idx_buf, grad_buffers=views[par])[0]
+            """-> (loss, [prediction])"""
+            loss, pred, _ = fused_train_step(octree, decoder, None, None, None, chain_opts[par],
+                                             n_surf=chain.surf_parts[par] if eik else None, pool=spool, idx=idx_buf,
+                                             grad_buffers=views[par])
+            return loss, [pred]
 
         def eager(k):
             out = None
@@ -824,7 +841,7 @@ def run_batch(args, workload, dist, world, rank, dev, steps, warmup, cpu_baselin
                 torch.cuda.synchronize()
 
         def run(k):
-            """exactly k steps -> the last step's loss (also kept as run.last_loss)"""
+            """exactly k steps -> the last step's loss (also kept as run.last_loss; its predictions as run.last_pred)"""
             out = None
             if g1[0] is None:
                 out = eager(k)
@@ -839,11 +856,17 @@ def run_batch(args, workload, dist, world, rank, dev, steps, warmup, cpu_baselin
                         out, k = loss1[chain.parity], k - 1
                         chain.parity ^= 1
             if out is not None:
-                run.last_loss = out
-            return out
+                run.last_loss, run.last_pred = out
+            return None if out is None else out[0]
 
-        run.last_loss = None
-        return dict(run=run, launch=launch, reducer=reducer, kind="dense", micro=1, keep=(gu, g1, chain, flat, views))
+        run.last_loss = run.last_pred = None
+
+        def last_grads():
+            """the last step's bucket: the other one's clearing rode on that step's launch (the step's result stays intact)"""
+            return views[chain.parity ^ 1]
+
+        return dict(run=run, launch=launch, reducer=reducer, kind="dense", micro=1, keep=(gu, g1, chain, flat, views),
+                    last_grads=last_grads)
 
     exchange, micro, exchange_note, tuned = args.exchange, 1, None, None
     want_m = max(1, int(args.micro_batches))
@@ -905,12 +928,22 @@ def run_batch(args, workload, dist, world, rank, dev, steps, warmup, cpu_baselin
         if dist is not None:  # every rank must replay the same number of steps (the collectives are in the step)
             dist.all_reduce(est, op=dist.ReduceOp.MAX)
         n_pre = int(min(4000, max(1, args.preheat_ms * 1e-3 / max(float(est), 1e-6))) // U + 1) * U
+        if outputs is not None:  # (a count that does not depend on the clock: the timed steps draw the same batches every run)
+            n_pre = (DUMP_PREHEAT_STEPS // U + 1) * U
         run(n_pre)
         barrier()
         preheat_ms = (time.perf_counter() - t_pre) * 1e3
     run(warmup)
     dt, windows, rank_ms = timed_windows(run, steps, args.repeats, barrier, dist, world, dev)
     loss = run.last_loss
+    if outputs is not None and rank == 0:  # before anything else launches: what the last timed step handed its caller
+        gf, gm = runner["last_grads"]()
+        outputs["loss"] = loss.detach().reshape(1).cpu()
+        outputs["pred"] = torch.cat([p.detach() for p in run.last_pred]).cpu()
+        for s, g in enumerate(gf):
+            outputs["grad_features_%d" % s] = g.detach().cpu()
+        for j, g in enumerate(gm):
+            outputs["grad_decoder_%d" % j] = g.detach().cpu()
 
     gather_overflow = None
     if use_dist and exchange == "gather":  # a message too small for a step's rows makes that step's grads incomplete: say so

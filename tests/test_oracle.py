@@ -1,5 +1,6 @@
 """CPU suite: the oracle against the committed golden vectors (generated from the real reference by
 oracle/make_golden.py), the kaolin shim's self-consistency, and the host-side octree build."""
+import functools
 import os
 
 import numpy as np
@@ -8,7 +9,6 @@ import torch
 
 from conftest import GOLDEN_NAMES, load_golden, oracle_from_golden
 from oracle import kaolin_shim as kal
-from oracle import ref_import
 from oracle import shine_oracle as so
 
 
@@ -129,136 +129,129 @@ def test_morton_helpers_match_shim():
     assert np.array_equal(morton_decode(m), p.numpy())
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not ref_import.available(), reason="needs /root/reference (authoring container)")
+@functools.lru_cache(maxsize=None)
+def _reference_checks(name="reference_checks"):
+    """what the reference's own functions returned on the stored inputs (oracle/make_reference_checks.py)"""
+    from oracle import make_reference_checks as mrc
+
+    return mrc.load_xz(name)
+
+
 def test_oracle_bit_identical_to_live_reference():
-    """Runs the real reference modules here and compares with the oracle to the bit (one fresh case)."""
-    R = ref_import.install()
-    from oracle import make_golden as mg
+    """One fresh case of oracle/make_golden.py (tests/golden/live_check.pt.xz, written by oracle/make_reference_checks.py while
+    the oracle agreed with the running reference to the bit): the oracle's octree build on the case's surface samples gives
+    the reference's tables, and its step on the recorded batch the reference's outputs (a few ulp of slack for other CPUs).
+    The stored features hold the rows the batch reads; the others are zero."""
+    from oracle import make_reference_checks as mrc
 
     torch.set_num_threads(1)
-    spec = dict(cfg=dict(tree_level_world=11, tree_level_feat=3, leaf_vox_size=0.25, sigma_sigmoid_m=0.07,
-                         ekional_loss_on=True, weight_e=0.2), n=512, decoder="pretrained", gain=5.0)
-    import tempfile, os
-    old = mg.GOLDEN_DIR
-    with tempfile.TemporaryDirectory() as d:
-        mg.GOLDEN_DIR = d
-        try:
-            mg.run_case(R, "live_check", spec)  # asserts bit-equality internally
-        finally:
-            mg.GOLDEN_DIR = old
+    fx = _reference_checks("live_check")
+    assert fx["cfg"] == mrc.LIVE_SPEC["cfg"] and fx["coord"].shape[0] == mrc.LIVE_SPEC["n"]
+    ocfg = so.make_config(**fx["cfg"])
+    built = so.OracleOctree(ocfg)
+    for sp in fx["surface_points"]:
+        built.update(sp, False)
+    for s, (keys, ids) in enumerate(fx["tables"]):
+        tab = built.node_table[built.free_level_num + s]
+        assert list(tab.keys()) == keys.tolist() and list(tab.values()) == ids.tolist()
+    cfg, oct_, mlp = oracle_from_golden(fx)
+    out = so.train_step(oct_, mlp, fx["coord"], fx["sdf_label"], fx["weight"], cfg)
+    ref = fx["out"]
+    for k in range(len(ref["indices"])):
+        assert torch.equal(out["indices"][k], ref["indices"][k])
+    for key in ("pred", "feat", "loss", "g"):
+        _close(out[key], ref[key], 2e-6, key)
+    for k in range(len(ref["feat_grads"])):
+        _close(out["feat_grads"][k], ref["feat_grads"][k], 1e-5, "feat_grad[%d]" % k)
+    for k in range(6):
+        _close(out["mlp_grads"][k], ref["mlp_grads"][k], 1e-5, "mlp_grad[%d]" % k)
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not ref_import.available(), reason="needs /root/reference (authoring container)")
 @pytest.mark.parametrize("reduction", ["mean", "sum"])
 def test_weighted_bce_of_the_oracle_is_the_reference_function(reduction):
     """loss_weight_on (off in every shipped yaml, so no golden fixture exercises it): the oracle's weighted BCE and its
-    gradient against the reference's own sdf_bce_loss(weighted=True) (utils/loss.py:17-24), to the bit."""
-    R = ref_import.install()
-    from oracle import shine_oracle as so
-
-    torch.manual_seed(3)
-    pred = (3.0 * torch.randn(777)).requires_grad_(True)
-    label = 0.05 * torch.randn(777)
-    w = torch.rand(777) + 0.1
-    sigma = 0.0123
-    ours = so.sdf_bce_loss(pred, label, sigma, reduction, weight=w)
+    gradient against what the reference's own sdf_bce_loss(weighted=True) (utils/loss.py:17-24) returned on the same
+    inputs."""
+    rec = _reference_checks()["weighted_bce"]
+    pred = rec["pred"].clone().requires_grad_(True)
+    ours = so.sdf_bce_loss(pred, rec["label"], rec["sigma"], reduction, weight=rec["weight"])
     (g_ours,) = torch.autograd.grad(ours, pred)
-    ref = R.sdf_bce_loss(pred, label, sigma, w, True, reduction)
-    (g_ref,) = torch.autograd.grad(ref, pred)
-    assert torch.equal(ours, ref) and torch.equal(g_ours, g_ref)
+    _close(ours.detach(), rec[reduction]["loss"], 2e-6, "loss")
+    _close(g_ours, rec[reduction]["grad"], 2e-6, "d loss / d pred")
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not ref_import.available(), reason="needs /root/reference (authoring container)")
 @pytest.mark.parametrize("reduction,bs,down_rate,take", [("mean", 100, 3, 1001), ("sum", 4096, 1, 700), ("mean", 64, 2, 1024)])
 def test_importance_sweep_of_the_oracle_is_the_reference_loop(reduction, bs, down_rate, take):
     """The chunking of cal_feature_importance (utils/incre_learning.py:15-40: head:tail:down_rate slices, a short last
-    chunk, the per-chunk 'mean') — the reference's own function, run unmodified on the oracle's octree / decoder objects
-    (it only duck-types them), against the oracle's restatement of the loop: bit-equal importance.  These are the cases
+    chunk, the per-chunk 'mean'): the oracle's restatement of the loop against the importance the reference's own function
+    computed on the same octree / decoder / pool.  These are the cases
     tests/test_gpu_parity.py::test_importance_sweep_chunking_matches_oracle holds the HIP sweep to."""
     import copy
 
-    R = ref_import.install()
-    from oracle import shine_oracle as so
-
     torch.set_num_threads(1)
+    want = _reference_checks("reference_importance")["importance_sweep"][(reduction, bs, down_rate, take)]
     fx = load_golden("ncd_reg_L3")
-    ocfg, oct_a, mlp_a = oracle_from_golden(fx)
-    _, oct_b, mlp_b = oracle_from_golden(fx)
+    ocfg, oct_b, mlp_b = oracle_from_golden(fx)
     ocfg = copy.copy(ocfg)
     ocfg.loss_reduction = reduction
     coord, label = fx["coord"][:take].contiguous(), fx["sdf_label"][:take].contiguous()
-    for o in (oct_a, oct_b):
-        for t in o.importance_weight:
-            t.zero_()
-    data = type("Pool", (), {"coord_pool": coord, "sdf_label_pool": label})()
-    decoder = type("Callable", (), {"__call__": lambda self, f: mlp_a.sdf(f)})()
-    R.cal_feature_importance(data, oct_a, decoder, so.sigma_sigmoid(ocfg), bs, down_rate, reduction)
+    for t in oct_b.importance_weight:
+        t.zero_()
     so.importance_sweep(oct_b, mlp_b, coord, label, ocfg, bs, down_rate)
-    for a, b in zip(oct_a.importance_weight, oct_b.importance_weight):
-        assert torch.equal(a, b) and float(a.abs().max()) > 0.0
+    assert len(oct_b.importance_weight) == len(want)
+    for k, (a, b) in enumerate(zip(oct_b.importance_weight, want)):
+        _close(a, b, 1e-5, "importance[%d]" % k)
+        assert float(a.abs().max()) > 0.0
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not ref_import.available(), reason="needs /root/reference (authoring container)")
 @pytest.mark.parametrize("ratio", [1.0, 0.5])
 def test_optimizer_groups_are_the_reference_groups(ratio):
     """setup_optimizer (utils/tools.py:57-83): decoder group with weight decay, then one group per feature level from the
     leaf level up with lr *= lr_level_reduce_ratio, Adam(betas=(0.9, 0.99), eps=adam_eps).  The product's FusedAdam groups
-    and the oracle's torch.optim.Adam groups against the reference's own function (structure only: no step is taken)."""
-    R = ref_import.install()
+    and the oracle's torch.optim.Adam groups against the groups the reference's own function built (structure only: no step
+    is taken; parameters named by their position in features + decoder parameters)."""
     from shine_mapping_amd.optim import setup_optimizer
 
+    ref = _reference_checks()["optimizer_groups"][ratio]
     fx = load_golden("ncd_reg_L3")
     ocfg, oct_, mlp = oracle_from_golden(fx)
     cfg = type("Cfg", (), dict(lr=0.01, weight_decay=1e-7, semantic_on=False, ray_loss=False, opt_adam=True, adam_eps=1e-15,
                                lr_level_reduce_ratio=ratio, tree_level_feat=ocfg.tree_level_feat))()
     feats = list(oct_.hier_features)
-    ref = R.setup_optimizer(cfg, feats, mlp.params(), None, None)
+    pos = {id(p): i for i, p in enumerate(feats + list(mlp.params()))}
     ours = setup_optimizer(cfg, feats, mlp.params())
     orc = so.adam_param_groups(oct_, mlp, lr=0.01, weight_decay=1e-7, lr_level_reduce_ratio=ratio)
     for opt in (ours, orc):
-        assert len(opt.param_groups) == len(ref.param_groups) == 1 + ocfg.tree_level_feat
-        for g, r in zip(opt.param_groups, ref.param_groups):
-            assert [id(p) for p in g["params"]] == [id(p) for p in r["params"]]
-            assert g["lr"] == r["lr"] and g.get("weight_decay", 0) == r.get("weight_decay", 0)
-    assert tuple(ours.betas) == tuple(ref.param_groups[0]["betas"]) == (0.9, 0.99)
-    assert ours.eps == ref.param_groups[0]["eps"] == 1e-15
+        assert len(opt.param_groups) == len(ref["groups"]) == 1 + ocfg.tree_level_feat
+        for g, r in zip(opt.param_groups, ref["groups"]):
+            assert [pos[id(p)] for p in g["params"]] == r["params"]
+            assert g["lr"] == r["lr"] and g.get("weight_decay", 0) == r["weight_decay"]
+    assert tuple(ours.betas) == tuple(ref["betas"]) == (0.9, 0.99)
+    assert ours.eps == ref["eps"] == 1e-15
     assert all(tuple(g["betas"]) == (0.9, 0.99) and g["eps"] == 1e-15 for g in orc.param_groups)
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not ref_import.available(), reason="needs /root/reference (authoring container)")
 def test_product_decoder_and_losses_are_interchangeable_with_the_reference():
     """Decoder (model/decoder.py:9-63): same state_dict keys and shapes as the reference's class, the reference's
-    pretrained/geo_decoder_8dim.pth loads strictly, and on CPU tensors (the composite branch) `sdf` equals the reference's
-    to the bit; sdf_bce_loss / get_gradient under the reference names (utils/loss.py:17-24, utils/tools.py:175-185)."""
-    import os
-
-    R = ref_import.install()
-    from model.decoder import Decoder as RefDecoder  # the reference's own module (ref_import put it on sys.path)
-
+    pretrained/geo_decoder_8dim.pth weights load strictly, and on CPU tensors (the composite branch) `sdf` equals what the
+    reference's returned; sdf_bce_loss / get_gradient under the reference names (utils/loss.py:17-24, utils/tools.py:175-185)
+    against the reference's values on the same inputs."""
     from shine_mapping_amd import Decoder, synth
     from shine_mapping_amd.losses import get_gradient, sdf_bce_loss
 
+    rec = _reference_checks()["decoder"]
     cfg = synth.make_config("maicity", device="cpu")
     torch.manual_seed(0)
-    ours, ref = Decoder(cfg), RefDecoder(cfg)
-    assert {k: tuple(v.shape) for k, v in ours.state_dict().items()} == {k: tuple(v.shape) for k, v in ref.state_dict().items()}
-    sd = torch.load(os.path.join(ref_import.REFERENCE_ROOT, "pretrained", "geo_decoder_8dim.pth"), map_location="cpu")
-    sd = sd.get("geo_decoder", sd) if isinstance(sd, dict) else sd
-    ours.load_state_dict(sd)
-    ref.load_state_dict(sd)
-    f = torch.randn(257, 8, requires_grad=True)
-    a, b = ours.sdf(f), ref.sdf(f)
-    assert torch.equal(a, b)
-    label, w = 0.05 * torch.randn(257), torch.rand(257) + 0.1
-    for weighted in (False, True):
-        for red in ("mean", "sum"):
-            assert torch.equal(sdf_bce_loss(a, label, 0.0123, w, weighted, red), R.sdf_bce_loss(b, label, 0.0123, w, weighted, red))
-    assert torch.equal(get_gradient(f, a), R.get_gradient(f, b))
+    ours = Decoder(cfg)
+    assert {k: tuple(v.shape) for k, v in ours.state_dict().items()} == rec["state_shapes"]
+    ours.load_state_dict(rec["state_dict"])
+    f = rec["feat"].clone().requires_grad_(True)
+    a = ours.sdf(f)
+    _close(a.detach(), rec["sdf"], 2e-6, "sdf")
+    for (weighted, red), want in rec["losses"].items():
+        _close(sdf_bce_loss(a, rec["label"], rec["sigma"], rec["weight"], weighted, red).detach(), want, 2e-6,
+               "sdf_bce_loss(weighted=%s, %s)" % (weighted, red))
+    _close(get_gradient(f, a).detach(), rec["get_gradient"], 1e-5, "get_gradient")
 
 
 def test_node_ranks_are_a_z_order_over_all_levels():
@@ -340,7 +333,9 @@ def test_host_update_equals_oracle_update_over_random_frame_sequences(seed):
 
 @pytest.mark.parametrize("name", ["mesh_query_L3", "mesh_query_L4"])
 def test_oracle_mesher_query_matches_reference_fixture(name):
-    """Mesher.get_query_from_bbx + query_points (utils/mesher.py:33-152) as run by the real reference."""
+    """Mesher.get_query_from_bbx + query_points (utils/mesher.py:33-152) as run by the real reference: the query grid and
+    the mask exactly, the SDF values to a few ulp (bit-identical on the authoring machine; another CPU's BLAS rounds the
+    decoder's matrix products differently)."""
     import numpy as np
 
     fx = load_golden(name)
@@ -350,33 +345,27 @@ def test_oracle_mesher_query_matches_reference_fixture(name):
     assert np.array_equal(origin, fx["voxel_origin"].numpy())
     sdf, mask = so.mesher_query_points(oct_, mlp, coord, fx["bs"], fx["mc_vis_level"])
     assert str(sdf.dtype) == fx["sdf_dtype"] and str(mask.dtype) == fx["mask_dtype"]
-    assert np.array_equal(sdf.astype("float32"), fx["sdf_pred"].numpy())
+    assert sdf.shape == tuple(fx["sdf_pred"].shape)
+    _close(torch.from_numpy(sdf.astype("float32")), fx["sdf_pred"], 2e-6, "sdf_pred")
     assert np.array_equal(mask.astype("uint8"), fx["mc_mask"].numpy())
     assert 0 < int(mask.sum()) < mask.size
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not ref_import.available(), reason="needs /root/reference (authoring container)")
 def test_reference_pickled_octree_loads_through_the_dropin(tmp_path):
     """utils/tools.py:200-213 pickles the reference's whole FeatureOctree; with shine_mapping_amd.dropin installed the
-    class path resolves to ours and __setstate__ adopts the reference's dict tables (ids and insertion order kept)."""
-    import subprocess, sys, os, json
+    class path resolves to ours and __setstate__ adopts the reference's dict tables (ids and insertion order kept).  The
+    checkpoint is one the reference wrote (oracle/make_reference_checks.py: the first CKPT_POINTS surface points of the
+    maicity_bce_L3 scans)."""
+    import json
+    import subprocess
+    import sys
 
-    R = ref_import.install()
-    fx = load_golden("maicity_bce_L3")
-    cfg = R.SHINEConfig()
-    for k, v in fx["cfg"].items():
-        setattr(cfg, k, v)
-    cfg.device = "cpu"
-    cfg.calculate_world_scale() if hasattr(cfg, "calculate_world_scale") else None
-    ref_oct = R.FeatureOctree(cfg)
-    for sp in fx["surface_points"]:
-        ref_oct.update(sp, True)
-    path = os.path.join(str(tmp_path), "ckpt.pth")
-    torch.save({"feature_octree": ref_oct}, path)
-    L = ref_oct.featured_level_num
-    want = {str(lvl): {str(k): v for k, v in ref_oct.nodes_lookup_tables[lvl].items()}
-            for lvl in range(ref_oct.free_level_num, ref_oct.max_level + 1)}
+    rec = _reference_checks()["pickled_octree"]
+    path = tmp_path / "ckpt.pth"
+    path.write_bytes(rec["checkpoint"])
+    L = len(rec["tables"])
+    want = {str(rec["free_level_num"] + s): {str(k): v for k, v in zip(keys.tolist(), ids.tolist())}
+            for s, (keys, ids) in enumerate(rec["tables"])}
     code = (
         "import json, sys, torch\n"
         "sys.path.insert(0, %r)\n"
@@ -387,7 +376,7 @@ def test_reference_pickled_octree_loads_through_the_dropin(tmp_path):
         "out = {str(l): {str(k): v for k, v in t[l].items()} for l in range(o.free_level_num, o.max_level + 1)}\n"
         "rows = [int(p.shape[0]) for p in o.hier_features]\n"
         "print(json.dumps(dict(tables=out, rows=rows, corners=o._corner_count, imp=len(o.importance_weight))))\n"
-    ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), path)
+    ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), str(path))
     env = dict(os.environ)
     env.pop("PYTHONPATH", None)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd=str(tmp_path))
@@ -396,7 +385,7 @@ def test_reference_pickled_octree_loads_through_the_dropin(tmp_path):
     assert got["tables"] == want
     for lvl in want:  # insertion order survives too (dicts keep it)
         assert list(got["tables"][lvl]) == list(want[lvl])
-    assert got["rows"] == [int(p.shape[0]) for p in ref_oct.hier_features]
+    assert got["rows"] == rec["rows"]
     assert got["corners"] == [r_ - 1 for r_ in got["rows"]]
     assert got["imp"] == L
 
@@ -454,22 +443,53 @@ def test_incremental_trajectory_literal_vs_clean_regulariser():
         assert abs(a - b) <= 1e-2 * max(1.0, abs(b))
 
 
-@pytest.mark.reference
-def test_dropin_rebinds_the_reference_utils_functions():
+# The driver-side modules the drop-in re-binds names in (utils/tools.py, utils/loss.py, utils/incre_learning.py,
+# utils/config.py of the reference), as stand-ins over the oracle's restatements of those functions — which the tests
+# above hold to the reference's recorded values.  The drop-in only sees module names and function objects.
+_UTILS_STAND_INS = {
+    "__init__.py": "",
+    "config.py": (
+        "class SHINEConfig:\n"
+        "    def __init__(self):\n"
+        "        self.device, self.tree_level_feat, self.lr, self.weight_decay = 'cuda', 3, 0.01, 1e-7\n"
+        "        self.lr_level_reduce_ratio, self.opt_adam, self.adam_eps = 1.0, True, 1e-15\n"
+        "        self.semantic_on, self.ray_loss = False, False\n"),
+    "loss.py": (
+        "from oracle import shine_oracle as so\n"
+        "def sdf_bce_loss(pred, label, sigma, weight, weighted=False, bce_reduction='mean'):\n"
+        "    return so.sdf_bce_loss(pred, label, sigma, bce_reduction, weight=weight if weighted else None)\n"),
+    "tools.py": (
+        "from types import SimpleNamespace\n"
+        "from oracle import shine_oracle as so\n"
+        "def get_gradient(inputs, outputs):\n"
+        "    return so.coord_gradient(inputs, outputs)\n"
+        "def setup_optimizer(config, octree_feat, mlp_geo_param, mlp_sem_param, sigma_size):\n"
+        "    octree = SimpleNamespace(featured_level_num=len(octree_feat), hier_features=list(octree_feat))\n"
+        "    mlp = SimpleNamespace(params=lambda: list(mlp_geo_param))\n"
+        "    return so.adam_param_groups(octree, mlp, config.lr, config.weight_decay, config.lr_level_reduce_ratio)\n"),
+    "incre_learning.py": (
+        "def cal_feature_importance(data, octree, mlp, sigma, bs, down_rate=1, loss_reduction='mean', loss_weight_on=False):\n"
+        "    raise NotImplementedError('stand-in: only its name is re-bound here')\n"),
+}
+
+
+def test_dropin_rebinds_the_reference_utils_functions(tmp_path):
     """VERDICT r03 missing 2: `import shine_mapping_amd.dropin` hands the unchanged drivers the rest of the fast path — the
     names they import with `from utils.tools import *` / `from utils.loss import *` (shine_batch.py:14-15): setup_optimizer
     (utils/tools.py:57-83) -> the fused Adam on the same groups, get_gradient (:175-185) and sdf_bce_loss (utils/loss.py:17-24)
-    -> the one-launch forms; each falls back to the reference's original for what it does not cover (CPU tensors here), each
-    has an opt-out, uninstall() puts the originals back."""
+    -> the one-launch forms; each falls back to the original for what it does not cover (CPU tensors here), each has an
+    opt-out, uninstall() puts the originals back.  The driver-side `utils` modules are stand-ins (_UTILS_STAND_INS)."""
     import subprocess
     import sys
 
-    if not ref_import.available():
-        pytest.skip("needs /root/reference")
+    (tmp_path / "utils").mkdir()
+    for name, text in _UTILS_STAND_INS.items():
+        (tmp_path / "utils" / name).write_text(text)
     code = (
         "import os, sys, torch\n"
-        "from oracle import ref_import\n"
-        "ref = ref_import.install()\n"
+        "sys.path.insert(0, %r)\n"
+        "from utils.config import SHINEConfig\n"
+    ) % str(tmp_path) + (
         "import utils.tools as ut, utils.loss as ul, utils.incre_learning as ui\n"
         "orig = (ut.setup_optimizer, ut.get_gradient, ul.sdf_bce_loss)\n"
         "orig_sweep = ui.cal_feature_importance\n"
@@ -491,7 +511,7 @@ def test_dropin_rebinds_the_reference_utils_functions():
         "assert ns['cal_feature_importance'] is ui.cal_feature_importance\n"
         "assert ns['get_gradient'] is losses.get_gradient and ns['sdf_bce_loss'] is losses.sdf_bce_loss\n"
         "# CPU parameters: the wrapper hands over to the reference's own setup_optimizer (torch.optim.Adam)\n"
-        "cfg = ref.SHINEConfig(); cfg.device = 'cpu'\n"
+        "cfg = SHINEConfig(); cfg.device = 'cpu'\n"
         "feats = [torch.nn.Parameter(torch.zeros(5, 8)) for _ in range(cfg.tree_level_feat)]\n"
         "dec = [torch.nn.Parameter(torch.zeros(4, 4))]\n"
         "opt = ns['setup_optimizer'](cfg, feats, dec, dec, torch.nn.Parameter(torch.ones(1)))\n"
