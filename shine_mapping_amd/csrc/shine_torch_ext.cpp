@@ -74,7 +74,6 @@ struct PyKeep {
 struct RegRiderState {
   std::vector<Tensor> last, imp, stamp;  // per level: features_last_frame, importance_weight (float32 contiguous), uint32 stamps
   Tensor acc;                            // float32[8]
-  uint32_t epoch = 0;
 };
 
 // What a FeatureOctree's launches need, refreshed by the Python side whenever the tables or the configuration change
@@ -95,6 +94,7 @@ struct TierAState {
                                                      // the octree itself and must not keep it alive
   std::shared_ptr<PyKeep> keep;                      // snapshots only: (octree, tables), strong
   std::shared_ptr<RegRiderState> reg;                // null: query_feature does not evaluate the regulariser
+  uint32_t reg_epoch = 0;  // the rider's launch counter: outlives `reg` (the stamps and the ring are kept across off -> on)
   int L() const { return cfg.n_levels; }
   void set(uintptr_t handle, const std::string& cfg_bytes, std::vector<int64_t> r, int64_t id, bool async_, int64_t epoch_,
            py::object owner) {
@@ -426,7 +426,7 @@ std::tuple<Tensor, c10::optional<Tensor>, c10::optional<Tensor>> query_feature(c
         rider.stamp[s] = reinterpret_cast<uint32_t*>(rs.stamp[s].data_ptr<int32_t>());
       }
       rider.acc = rs.acc.data_ptr<float>();
-      rider.epoch = ++rs.epoch;
+      rider.epoch = ++st->reg_epoch;
       cfg.reg_rider = &rider;
       reg = rs.acc.select(0, (int64_t)(rider.epoch & 7u));
     }
@@ -654,10 +654,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           TORCH_CHECK(stamp[k].is_cuda() && stamp[k].scalar_type() == at::kInt && stamp[k].numel() >= s.rows[k] + 1,
                       "set_reg: one int32 stamp per row");
         }
-        auto keep_epoch = s.reg ? s.reg->epoch : 0u;  // (stamps may be re-used: the epoch never goes back)
-        s.reg = std::make_shared<RegRiderState>();
+        s.reg = std::make_shared<RegRiderState>();  // (s.reg_epoch goes on: stamps may be re-used, the epoch never goes back)
         s.reg->last = std::move(last), s.reg->imp = std::move(imp), s.reg->stamp = std::move(stamp), s.reg->acc = std::move(acc);
-        s.reg->epoch = keep_epoch;
       });
   py::class_<Link, std::shared_ptr<Link>>(m, "Link").def("pending", [](Link& l) { return l.q.defined(); });
   m.def("set_callbacks", [](py::object interp_backward, py::object fused_split, py::object read_done) {

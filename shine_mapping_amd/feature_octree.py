@@ -771,9 +771,11 @@ class FeatureOctree(nn.Module):
         d = self.__dict__
         coord = d.get("_hidx_coord")
         riding = d.get("_reg_riding")
-        if riding is not None and coord is not None and d.get("_hidx") is None and d.get("_hidx_epoch") == self._tables_epoch:
+        if (riding is not None and coord is not None and d.get("_hidx") is None and d.get("_hidx_epoch") == self._tables_epoch
+                and d.get("_reg_riding_versions") == self._reg_versions()):
             # the query's own launch evaluated it (_reg_rider: value only, its gradient cancels): no launch but the copy that
-            # takes the number out of the rider's ring
+            # takes the number out of the rider's ring — unless a feature, features_last_frame or importance_weight was written
+            # since the query (an optimiser step, an in-place update): then the regulariser's own launches below
             return riding.clone()
         if (coord is not None and d.get("_hidx") is None and d.get("_hidx_epoch") == self._tables_epoch and coord.is_cuda
                 and self.featured_level_num <= 4 and len(self.importance_weight) == self.featured_level_num
@@ -789,6 +791,10 @@ class FeatureOctree(nn.Module):
                                                   list(self.importance_weight), self._reg_row_flags(coord.device), live)
                 return autograd_ops.OctreeRegularizer.apply(self, coord, *self.feature_list())
         return self._cal_regularization_composite()
+
+    def _reg_versions(self):
+        """the in-place write counters of the tensors the regulariser reads"""
+        return tuple(t._version for ts in (self.hier_features, self.features_last_frame, self.importance_weight) for t in ts)
 
     def _reg_live_levels(self):
         """OctreeRegularizer.levels_with_gradient, remembered for as long as the tensors it looked at are the same objects (they
@@ -852,7 +858,7 @@ class FeatureOctree(nn.Module):
         state.pop("_ext_st", None)
         state.pop("_ext_key", None)
         state.pop("_reg_flags", None)
-        for k in ("_rider_key", "_rider_on", "_rider_keep", "_rider_stamps", "_rider_acc", "_reg_riding"):
+        for k in ("_rider_key", "_rider_on", "_rider_keep", "_rider_stamps", "_rider_acc", "_reg_riding", "_reg_riding_versions"):
             state.pop(k, None)
         state["_dict_cache"] = None
         state["_pending"] = None

@@ -308,6 +308,8 @@ def _ext_query(ext, octree, coord):
     octree.__dict__["_spec_result"] = (pred, dec, mlp, autograd_ops.param_epoch(), [p._version for p in mlp]) if mlp else None
     octree._defer_indices(coord)
     octree.__dict__["_reg_riding"] = reg  # None, or this query's regulariser (a view of the rider's ring: clone to keep)
+    if reg is not None:  # ... of the tensors as they are now (cal_regularization evaluates at call time)
+        octree.__dict__["_reg_riding_versions"] = octree._reg_versions()
     return feat
 
 

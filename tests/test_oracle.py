@@ -69,6 +69,50 @@ def test_quantize_edges():
     assert q.tolist() == [[0, 15, 8], [0, 15, 7], [15, 0, 12]]
 
 
+@pytest.mark.parametrize("name", ["edges_L3", "edges_L2_nopoly_eik"])
+def test_oracle_reproduces_the_edge_fixtures(name):
+    """The designed-coordinate fixtures (oracle/make_golden.py edge_batch: voxel vertices / edges / faces of every level, one ulp
+    either side, the cube's boundary, points outside it, misses, duplicates).  Indices and features are elementwise arithmetic
+    and must be bit-identical; what goes through the decoder's GEMMs as in test_oracle_reproduces_reference_goldens."""
+    torch.set_num_threads(1)
+    fx = load_golden(name)
+    cfg, oct_, mlp = oracle_from_golden(fx)
+    out = so.train_step(oct_, mlp, fx["coord"], fx["sdf_label"], fx["weight"], cfg)
+    ref = fx["out"]
+    for k in range(len(ref["indices"])):
+        assert torch.equal(out["indices"][k], ref["indices"][k]), "indices[%d]" % k
+    assert torch.equal(out["feat"], ref["feat"])
+    _close(out["pred"], ref["pred"], 2e-6, "pred")
+    _close(out["loss"], ref["loss"], 2e-6, "loss")
+    if ref["g"] is not None:
+        _close(out["g"], ref["g"], 2e-6, "g")
+    for k in range(len(ref["feat_grads"])):
+        _close(out["feat_grads"][k], ref["feat_grads"][k], 1e-5, "feat_grad[%d]" % k)
+    for k in range(6):
+        _close(out["mlp_grads"][k], ref["mlp_grads"][k], 1e-5, "mlp_grad[%d]" % k)
+    # every family is present, and the fixture reaches both sides of every decision it was designed for
+    fam, c = fx["family"], fx["coord"]
+    assert sorted(torch.unique(fam).tolist()) == [1, 2, 3, 4, 5, 6]
+    assert bool((c.abs() == 1.0).any()) and bool((c.abs() > 1.0).any()) and bool((c < -1.0).any())
+    finest = (ref["indices"][0] >= 0).all(1)
+    assert bool(finest.any()) and not bool(finest.all())
+    # the kaolin shim's clamp (quantize_points: floor(clamp(res (x + 1) / 2, 0, res - 1))) is what the reference ran on: a point
+    # outside the cube, or on its +1 face, addresses the boundary voxel — the recorded indices equal those of the point clamped
+    # into [-1, 1), while d = frac(res (x/2 + 1/2)) keeps the unclamped x (negative below -1)
+    inside = torch.nextafter(torch.tensor(1.0), torch.tensor(0.0))
+    cl = c.clamp(-1.0, float(inside))
+    moved = (cl != c).any(1)
+    assert int(moved.sum()) > 0
+    for i in range(oct_.featured_level_num):
+        lvl = oct_.max_level - i
+        q = kal.quantize_points(c, lvl)
+        assert int(q.min()) >= 0 and int(q.max()) <= 2 ** lvl - 1
+        assert torch.equal(q, kal.quantize_points(cl, lvl))
+    assert all(torch.equal(a[moved], b[moved]) for a, b in zip(oct_.get_indices(cl), ref["indices"]))
+    u = (2 ** oct_.max_level) * (c * 0.5 + 0.5)
+    assert bool((torch.frac(u) < 0).any())  # (torch.frac's sign: the reference's weights there leave [0, 1])
+
+
 def test_corner_order_matches_interpolation_weights():
     """Planting f(corner) = a.x+b.y+c.z+d on the corners must be reproduced exactly by (linear) interpolation:
     checks points_to_corners' order against interpolat's weight order and the quantise formula."""
