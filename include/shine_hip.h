@@ -227,6 +227,27 @@ int shine_forward(const shine_tables* t, const shine_step_config* cfg, const flo
 int shine_bce_loss(const float* pred, const float* sdf_label, const float* weight, int64_t n, float sigma,
                    int32_t reduction_sum, float* loss_out, float* dpred_out, void* stream);
 
+/* ---- Tier A (strict drop-in): the other training objectives of the yamls, each loss and its derivative in ONE launch.
+ *      workspace: SHINE_LOSS_WORKSPACE_BYTES of 8-byte aligned device memory, ZERO when first used; every call leaves it zero
+ *      again.  Calls that share a workspace must not overlap (one workspace per stream).  The loss is summed in fp64 partials
+ *      that the last workgroup adds up in a fixed order: repeated calls give the same bits at any size.
+ *
+ *      sdf_diff_loss (utils/loss.py:6-14), main_loss_type sdf_l1 / sdf_l2: diff_m = (pred - sdf_label) / scale,
+ *      *loss_out = sum(weight * diff_m^2) / n (l2_loss != 0) or sum(weight * |diff_m|) / n; dpred_out [n] (or NULL) =
+ *      d loss / d pred.  weight is used as given (the driver applies abs first, shine_batch.py:166). */
+#define SHINE_LOSS_WORKSPACE_BYTES 16384
+int shine_sdf_diff_loss(const float* pred, const float* sdf_label, const float* weight, int64_t n, float scale,
+                        int32_t l2_loss, float* loss_out, float* dpred_out, void* workspace, void* stream);
+
+/*      batch_ray_rendering_loss (utils/loss.py:82-118), ray_loss with main_loss_type dr (neus_on = 0) / dr_neus: x (sample
+ *      depths) and y (occupancy probabilities) [rays, samples] row-major, d_meas [rays].  Per ray the samples are sorted by x
+ *      (ties by column), alphas a = sorted y (dr) or clamp((y[i+1] - y[i]) / (1 - y[i] + 1e-10), 0, 1) (dr_neus),
+ *      d = sum (cumprod(1 - a + 1e-10) / (1 - a + 1e-10)) a x; *loss_out = mean |d - d_meas|.  dy_out [rays, samples] =
+ *      d loss / d y as autograd forms it from that composite, at the unsorted columns.  samples <= SHINE_RAY_MAX_SAMPLES. */
+#define SHINE_RAY_MAX_SAMPLES 32
+int shine_ray_render_loss(const float* x, const float* y, const float* d_meas, int64_t rays, int32_t samples, int32_t neus_on,
+                          float* loss_out, float* dy_out, void* workspace, void* stream);
+
 /* ---- Tier A (strict drop-in): the backward of FeatureOctree.query_feature as autograd derives it from
  *      model/feature_octree.py:222-234, and its own backward (needed by get_gradient(create_graph=True),
  *      utils/tools.py:175-185, when the eikonal term is differentiated, shine_batch.py:182-185).

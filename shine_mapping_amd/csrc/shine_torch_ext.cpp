@@ -12,6 +12,8 @@
 //   grad_coord       get_gradient(coord, pred) (utils/tools.py:175-185): shine_forward's closed-form d pred / d coord; its
 //                    backward leaves d loss / d g with the fused node (shared Link)
 //   bce_loss         sdf_bce_loss (utils/loss.py:17-24): shine_bce_loss, loss and d loss / d pred in one launch
+//   diff_loss        sdf_diff_loss (utils/loss.py:6-14): shine_sdf_diff_loss, loss and d loss / d pred in one launch
+//   ray_render_loss  batch_ray_rendering_loss (utils/loss.py:82-118): shine_ray_render_loss, loss and d loss / d y in one launch
 //   cal_regularization  FeatureOctree.cal_regularization (model/feature_octree.py:246-255): a node only while a gradient is live
 //   adam_step        FusedAdam.step (utils/tools.py:57-83's Adam): shine_adam_step without Python-side pointer arrays
 //
@@ -321,6 +323,19 @@ struct BceNode : public Node {
   void release_variables() override { dpred.reset(); }
 };
 
+// sdf_diff_loss / batch_ray_rendering_loss: the derivative for an upstream gradient of 1 was written by the forward launch
+struct ScaledGradNode : public Node {
+  std::string label;
+  std::string name() const override { return label; }
+  Tensor dgrad;
+  variable_list apply(variable_list&& grads) override {
+    variable_list out(1);
+    if (grads[0].defined()) out[0] = dgrad * grads[0];
+    return out;
+  }
+  void release_variables() override { dgrad.reset(); }
+};
+
 // reg = cal_regularization() (model/feature_octree.py:246-255; autograd_ops.OctreeRegularizer): the rows the octree's last
 // query addressed are flagged (shine_mark_touched) and summed by one row-parallel launch that clears the flags again.  A node
 // exists only while a level's features_last_frame is still a detached copy (`live`): from the second frame on the reference holds
@@ -535,6 +550,60 @@ Tensor bce_loss(const Tensor& pred, const Tensor& label, const c10::optional<Ten
   return loss;
 }
 
+void check_workspace(const Tensor& ws, const Tensor& like) {
+  TORCH_CHECK(ws.is_cuda() && ws.get_device() == like.get_device() && ws.is_contiguous() &&
+                  ws.numel() * ws.element_size() >= SHINE_LOSS_WORKSPACE_BYTES,
+              "loss workspace: SHINE_LOSS_WORKSPACE_BYTES of zeroed device memory on the inputs' device");
+}
+
+Tensor diff_loss(const Tensor& pred, const Tensor& label, const Tensor& weight, double scale, bool l2_loss, const Tensor& ws) {
+  check_workspace(ws, pred);
+  Tensor loss, dpred;
+  {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    Tensor p = f32c(pred.detach()), l = f32c(label.detach()), w = f32c(weight.detach());
+    const int64_t n = p.size(0);
+    Tensor out = at::empty({n + 1}, p.options());  // [d loss / d pred (n) | loss]
+    check(shine_sdf_diff_loss(p.data_ptr<float>(), l.data_ptr<float>(), w.data_ptr<float>(), n, (float)scale, l2_loss ? 1 : 0,
+                              out.data_ptr<float>() + n, out.data_ptr<float>(), ws.data_ptr(), cur_stream(p)),
+          "shine_sdf_diff_loss");
+    loss = out.select(0, n);
+    dpred = out.narrow(0, 0, n);
+  }
+  if (at::GradMode::is_enabled() && pred.requires_grad()) {
+    auto node = make_node<ScaledGradNode>({pred});
+    node->label = "SdfDiff[ext]";
+    node->dgrad = dpred;
+    torch::autograd::create_gradient_edge(loss, node);
+  }
+  return loss;
+}
+
+Tensor ray_render_loss(const Tensor& x, const Tensor& y, const Tensor& d_meas, bool neus_on, const Tensor& ws) {
+  check_workspace(ws, y);
+  TORCH_CHECK(y.dim() == 2 && x.sizes() == y.sizes() && d_meas.dim() == 1 && d_meas.size(0) == y.size(0),
+              "ray_render_loss: x, y [rays, samples], d_meas [rays]");
+  Tensor loss, dy;
+  {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    Tensor xc = f32c(x.detach()), yc = f32c(y.detach()), dc = f32c(d_meas.detach());
+    const int64_t r = yc.size(0), s = yc.size(1);
+    Tensor out = at::empty({r * s + 1}, yc.options());  // [d loss / d y (r * s) | loss]
+    check(shine_ray_render_loss(xc.data_ptr<float>(), yc.data_ptr<float>(), dc.data_ptr<float>(), r, (int32_t)s, neus_on ? 1 : 0,
+                                out.data_ptr<float>() + r * s, out.data_ptr<float>(), ws.data_ptr(), cur_stream(yc)),
+          "shine_ray_render_loss");
+    loss = out.select(0, r * s);
+    dy = out.narrow(0, 0, r * s).view({r, s});
+  }
+  if (at::GradMode::is_enabled() && y.requires_grad()) {
+    auto node = make_node<ScaledGradNode>({y});
+    node->label = "RayRender[ext]";
+    node->dgrad = dy;
+    torch::autograd::create_gradient_edge(loss, node);
+  }
+  return loss;
+}
+
 // FeatureOctree.cal_regularization for the coordinates of the octree's last query.  flags: one uint8 per row and level, all zero
 // (left zero again).  live[s]: level s's features_last_frame is a detached copy (its gradient does not cancel).
 Tensor cal_regularization(const std::shared_ptr<TierAState>& st, const Tensor& coord, const std::vector<Tensor>& feats,
@@ -667,6 +736,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_sdf", &fused_sdf);
   m.def("grad_coord", &grad_coord);
   m.def("bce_loss", &bce_loss);
+  m.def("diff_loss", &diff_loss);
+  m.def("ray_render_loss", &ray_render_loss);
   m.def("cal_regularization", &cal_regularization);
   m.def("adam_step", &adam_step);
   m.def("config_bytes", []() { return (int64_t)sizeof(shine_step_config); });

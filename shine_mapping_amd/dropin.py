@@ -17,8 +17,12 @@ Four FUNCTIONS of the reference's own `utils` modules are additionally re-bound 
 for anything it does not cover, each with an opt-out environment variable (= "0"):
 
     utils.tools.setup_optimizer  ->  optim.setup_optimizer: the same Adam groups (utils/tools.py:57-83) as ONE fused launch per
-                                     step instead of torch's multi-tensor Adam            SHINE_DROPIN_FUSED_OPTIMIZER
+                                     step instead of torch's multi-tensor Adam (ray_loss: with the learnable sigma_size
+                                     group, :74-76)                                       SHINE_DROPIN_FUSED_OPTIMIZER
     utils.loss.sdf_bce_loss      ->  losses.sdf_bce_loss: loss and d loss / d pred in ONE launch      SHINE_DROPIN_FUSED_LOSS
+    utils.loss.sdf_diff_loss     ->  losses.sdf_diff_loss (sdf_l1 / sdf_l2): the same, one launch     (same opt-out)
+    utils.loss.batch_ray_rendering_loss -> losses.batch_ray_rendering_loss (ray_loss, dr / dr_neus): loss and d loss / d y
+                                     in ONE launch; a utils.loss without these names is left as it is   (same opt-out)
     utils.tools.get_gradient     ->  losses.get_gradient: for the fused query_feature -> sdf node ONE forward-kernel launch,
                                      linked to that node so that the eikonal term's backward joins its single fused launch
                                      (lets the eikonal configurations use the fused node)            SHINE_DROPIN_FUSED_GRADIENT
@@ -111,6 +115,8 @@ def _single_thread_backward_wanted():
     return os.path.basename(getattr(main, "__file__", "") or "") in DRIVER_FILES
 
 
+_LOSS_NAMES = ("sdf_bce_loss", "sdf_diff_loss", "batch_ray_rendering_loss")  # utils.loss functions losses.py replaces
+
 _REBOUND = []  # (module, name, original) of rebind_imported_names, for uninstall()
 
 
@@ -131,8 +137,11 @@ def rebind_imported_names(triples):
 
 
 def patch_utils():
-    """Re-bind utils.tools.setup_optimizer / get_gradient and utils.loss.sdf_bce_loss (see the module docstring)."""
+    """Re-bind utils.tools.setup_optimizer / get_gradient and utils.loss.sdf_bce_loss / sdf_diff_loss /
+    batch_ray_rendering_loss (see the module docstring)."""
     import importlib
+
+    import torch
 
     from . import autograd_ops, losses, optim
 
@@ -149,15 +158,16 @@ def patch_utils():
     if ut is not None and not hasattr(ut, "_shine_reference"):
         ut._shine_reference = {"setup_optimizer": ut.setup_optimizer, "get_gradient": ut.get_gradient}
     if ul is not None and not hasattr(ul, "_shine_reference"):
-        ul._shine_reference = {"sdf_bce_loss": ul.sdf_bce_loss}
+        ul._shine_reference = {name: getattr(ul, name) for name in _LOSS_NAMES if hasattr(ul, name)}
     if ut is not None:
         ref_setup = ut._shine_reference["setup_optimizer"]
         if _on("SHINE_DROPIN_FUSED_OPTIMIZER"):
             def setup_optimizer(config, octree_feat, mlp_geo_param, mlp_sem_param, sigma_size):
                 tensors = list(octree_feat) + list(mlp_geo_param or [])
-                if (getattr(config, "opt_adam", True) and not getattr(config, "semantic_on", False)
-                        and not getattr(config, "ray_loss", False) and tensors
-                        and all(p.is_cuda and p.dtype.is_floating_point and p.element_size() == 4 for p in tensors)):
+                if getattr(config, "ray_loss", False):  # (the learnable sigma_size group, utils/tools.py:74-76)
+                    tensors.append(sigma_size if isinstance(sigma_size, torch.Tensor) else None)
+                if (getattr(config, "opt_adam", True) and not getattr(config, "semantic_on", False) and tensors
+                        and all(isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.float32 for p in tensors)):
                     return optim.setup_optimizer(config, octree_feat, mlp_geo_param, mlp_sem_param, sigma_size)
                 return ref_setup(config, octree_feat, mlp_geo_param, mlp_sem_param, sigma_size)
 
@@ -201,12 +211,15 @@ def patch_utils():
             ui.cal_feature_importance = ref_sweep
             _STATUS["cal_feature_importance"] = "off (SHINE_DROPIN_FUSED_IMPORTANCE=0)"
     if ul is not None:
-        if _on("SHINE_DROPIN_FUSED_LOSS"):
-            ul.sdf_bce_loss = losses.sdf_bce_loss
-            _STATUS["sdf_bce_loss"] = True
-        else:
-            ul.sdf_bce_loss = ul._shine_reference["sdf_bce_loss"]
-            _STATUS["sdf_bce_loss"] = "off (SHINE_DROPIN_FUSED_LOSS=0)"
+        for name in _LOSS_NAMES:
+            if name not in ul._shine_reference:
+                continue  # (a utils.loss without it: nothing to re-bind)
+            if _on("SHINE_DROPIN_FUSED_LOSS"):
+                setattr(ul, name, getattr(losses, name))
+                _STATUS[name] = True
+            else:
+                setattr(ul, name, ul._shine_reference[name])
+                _STATUS[name] = "off (SHINE_DROPIN_FUSED_LOSS=0)"
     # names the importing module copied before this ran (drop-in imported after `from utils.tools import *`, shine_incre.py:13-15)
     triples = []
     for mod in (ut, ul, ui):

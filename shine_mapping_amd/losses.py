@@ -1,10 +1,15 @@
-"""utils/loss.py:17-24 and utils/tools.py:175-185 under their reference names (Tier A, the strict drop-in).
+"""utils/loss.py:6-24,82-118 and utils/tools.py:175-185 under their reference names (Tier A, the strict drop-in).
 
 `sdf_bce_loss` is ONE HIP launch that returns the loss and keeps d loss / d pred for its backward (the torch composite is a
 sigmoid, a BCEWithLogits and their two backward launches); `get_gradient` on the output of the fused query_feature -> sdf node
 is ONE launch of the forward kernel's closed-form d pred / d coord build, linked to that node so that the eikonal term's
 backward joins the node's one fused launch (autograd_ops.InterpSdfGradCoord).  Anything else — CPU tensors, other dtypes,
 other reductions, a pred that did not come from the fused node — runs the reference's torch composite, same results.
+
+`sdf_diff_loss` (main_loss_type sdf_l1 / sdf_l2) and `batch_ray_rendering_loss` (ray_loss with dr / dr_neus) are ONE launch
+each as well (csrc/shine_loss_modes.hip): the loss and d loss / d pred (d loss / d y for the rays) — where the composite runs a
+sort, a gather, a cumprod and a dozen elementwise launches forward and more backward.  They take the HIP path for CUDA float32
+inputs of the reference's shapes whose targets (label, weight, depths) need no gradient, with at most 32 samples per ray.
 """
 import ctypes as C
 
@@ -57,6 +62,115 @@ def sdf_bce_loss(pred, label, sigma, weight, weighted=False, bce_reduction="mean
             return ext.bce_loss(pred, label, w, float(sigma), bce_reduction == "sum")
         return _SdfBce.apply(pred, label, w, float(sigma), bce_reduction == "sum")
     return _bce_composite(pred, label, sigma, weight, weighted, bce_reduction)
+
+
+_WORKSPACES = {}  # (device index, stream) -> the zeroed workspace of shine_sdf_diff_loss / shine_ray_render_loss
+
+
+def loss_workspace(device):
+    """SHINE_LOSS_WORKSPACE_BYTES of zeroed device memory for the current stream of `device` (the kernels leave it zero again;
+    calls on one stream never overlap)"""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    key = (idx, _lib.current_stream_handle() if idx == torch.cuda.current_device() else torch.cuda.current_stream(idx).cuda_stream)
+    ws = _WORKSPACES.get(key)
+    if ws is None:
+        ws = _WORKSPACES[key] = torch.zeros(LOSS_WORKSPACE_BYTES // 8, dtype=torch.float64, device=torch.device("cuda", idx))
+    return ws
+
+
+LOSS_WORKSPACE_BYTES = 16384  # include/shine_hip.h SHINE_LOSS_WORKSPACE_BYTES
+RAY_MAX_SAMPLES = 32  # SHINE_RAY_MAX_SAMPLES
+
+
+class _SdfDiff(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, label, weight, scale, l2_loss, ws):
+        p, l, w = pred.detach().contiguous(), label.detach().contiguous(), weight.detach().contiguous()
+        n = p.shape[0]
+        out = torch.empty(n + 1, dtype=torch.float32, device=p.device)  # [d loss / d pred (n) | loss]
+        _lib.check(_lib.lib().shine_sdf_diff_loss(p.data_ptr(), l.data_ptr(), w.data_ptr(), n, float(scale), 1 if l2_loss else 0,
+                                                  out[n:].data_ptr(), out.data_ptr(), ws.data_ptr(), _lib.current_stream_handle()),
+                   "shine_sdf_diff_loss")
+        ctx.dpred = out[:n]
+        return out[n]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return ctx.dpred * g, None, None, None, None, None
+
+
+class _RayRender(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, d_meas, neus_on, ws):
+        xc, yc, dc = x.detach().contiguous(), y.detach().contiguous(), d_meas.detach().contiguous()
+        r, s = yc.shape
+        out = torch.empty(r * s + 1, dtype=torch.float32, device=yc.device)  # [d loss / d y (r * s) | loss]
+        _lib.check(_lib.lib().shine_ray_render_loss(xc.data_ptr(), yc.data_ptr(), dc.data_ptr(), r, s, 1 if neus_on else 0,
+                                                    out[r * s:].data_ptr(), out.data_ptr(), ws.data_ptr(),
+                                                    _lib.current_stream_handle()),
+                   "shine_ray_render_loss")
+        ctx.dy = out[:r * s].view(r, s)
+        return out[r * s]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return None, ctx.dy * g, None, None, None
+
+
+def _f32_cuda_like(t, ref):
+    return isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == ref.device and not t.requires_grad
+
+
+def sdf_diff_loss_composite(pred, label, weight, scale, l2_loss=True):
+    """sdf_diff_loss's torch composite: the batch mean of weight * r^2 (l2) or weight * |r| (l1), r = (pred - label) / scale"""
+    r = (pred - label) / scale
+    per = r ** 2 if l2_loss else r.abs()
+    return (weight * per).sum() / pred.shape[0]
+
+
+def sdf_diff_loss(pred, label, weight, scale, l2_loss=True):
+    """utils/loss.py:6-14 (main_loss_type sdf_l1: l2_loss=False, sdf_l2: True)"""
+    if (isinstance(pred, torch.Tensor) and pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 1 and pred.shape[0] > 0
+            and _f32_cuda_like(label, pred) and label.shape == pred.shape and _f32_cuda_like(weight, pred)
+            and weight.shape == pred.shape and isinstance(scale, (int, float)) and not isinstance(scale, bool) and scale != 0):
+        ws = loss_workspace(pred.device)
+        ext = _ext.module()
+        if ext is not None:  # the C++ node (csrc/shine_torch_ext.cpp)
+            return ext.diff_loss(pred, label, weight, float(scale), bool(l2_loss), ws)
+        return _SdfDiff.apply(pred, label, weight, float(scale), bool(l2_loss), ws)
+    return sdf_diff_loss_composite(pred, label, weight, scale, l2_loss)
+
+
+def batch_ray_rendering_loss_composite(x, y, d_meas, neus_on=True):
+    """batch_ray_rendering_loss's torch composite: per ray the samples in depth order, alphas a (the probabilities, or the
+    clamped neus quotient of neighbours), o = (1 - a) + 1e-10, weights cumprod(o) / o * a; the mean |sum w x - d_meas|"""
+    depth, order = x.sort(dim=1)
+    prob = y.gather(1, order)
+    if neus_on:
+        lo, hi = prob[:, :-1], prob[:, 1:]
+        a = ((hi - lo) / (1.0 - lo + 1e-10)).clamp(0.0, 1.0)
+    else:
+        a = prob
+    o = torch.ones_like(a) - a + 1e-10
+    w = o.cumprod(dim=1) / o * a
+    d = (w * depth[:, :a.shape[1]]).sum(dim=1)
+    return (d - d_meas).abs().mean()
+
+
+def batch_ray_rendering_loss(x, y, d_meas, neus_on=True):
+    """utils/loss.py:82-118: x sample depths [rays, samples], y occupancy probabilities [rays, samples] (the alphas of dr, the
+    neus quotient's inputs of dr_neus), d_meas measured depths [rays]"""
+    if (isinstance(y, torch.Tensor) and y.is_cuda and y.dtype == torch.float32 and y.dim() == 2 and y.shape[0] > 0
+            and 0 < y.shape[1] <= RAY_MAX_SAMPLES and _f32_cuda_like(x, y) and x.shape == y.shape
+            and _f32_cuda_like(d_meas, y) and d_meas.shape == (y.shape[0],)):
+        ws = loss_workspace(y.device)
+        ext = _ext.module()
+        if ext is not None:
+            return ext.ray_render_loss(x, y, d_meas, bool(neus_on), ws)
+        return _RayRender.apply(x, y, d_meas, bool(neus_on), ws)
+    return batch_ray_rendering_loss_composite(x, y, d_meas, neus_on)
 
 
 def get_gradient(inputs, outputs):

@@ -3,6 +3,7 @@
 setup_optimizer builds torch.optim.Adam(betas=(0.9, 0.99), eps=config.adam_eps) over
   group 0: the geo decoder's parameters, lr, weight_decay (L2)                       (:60-63)
   then one group per feature level, leaf level first, lr *= lr_level_reduce_ratio   (:68-72)
+  with ray_loss: a last group holding the learnable sigma_size, lr, no weight decay   (:74-76)
 FusedAdam takes the same param_groups (so step_lr_decay, utils/tools.py:135-155, keeps working on
 ``opt.param_groups``) and applies the dense update to every tensor in ONE kernel, optionally clearing the grads
 in the same pass.  Numerics follow torch.optim.Adam (tests compare the two on the GPU).
@@ -21,7 +22,8 @@ class FusedAdam:
         self.param_groups = []
         for g in param_groups:
             g = dict(g)
-            g["params"] = [p for p in g["params"]]
+            ps = g["params"]
+            g["params"] = [ps] if isinstance(ps, torch.Tensor) else [p for p in ps]  # (a bare tensor is one parameter, as in torch)
             g.setdefault("weight_decay", 0.0)
             self.param_groups.append(g)
         self.betas = betas
@@ -309,9 +311,13 @@ class FusedAdam:
 
 
 def setup_optimizer(config, octree_feat, mlp_geo_param, mlp_sem_param=None, sigma_size=None):
-    """utils/tools.py:57-83 with the fused optimiser (Adam only; opt_adam is True in config defaults, :167)."""
-    if getattr(config, "semantic_on", False) or getattr(config, "ray_loss", False) or not getattr(config, "opt_adam", True):
-        raise NotImplementedError("fused optimiser covers the shipped configs: Adam, no semantic head, no ray loss")
+    """utils/tools.py:57-83 with the fused optimiser (Adam only; opt_adam is True in config defaults, :167).  With ray_loss the
+    learnable sigma_size of the rendering loss is the last group (:74-76)."""
+    if getattr(config, "semantic_on", False) or not getattr(config, "opt_adam", True):
+        raise NotImplementedError("fused optimiser covers Adam without the semantic head")
+    ray_loss = bool(getattr(config, "ray_loss", False))
+    if ray_loss and not isinstance(sigma_size, torch.Tensor):
+        raise ValueError("ray_loss: setup_optimizer needs the learnable sigma_size tensor")
     lr_cur = config.lr
     groups = []
     if mlp_geo_param is not None:
@@ -320,6 +326,8 @@ def setup_optimizer(config, octree_feat, mlp_geo_param, mlp_sem_param=None, sigm
     for i in range(L):
         groups.append({"params": [octree_feat[L - i - 1]], "lr": lr_cur})
         lr_cur *= getattr(config, "lr_level_reduce_ratio", 1.0)
+    if ray_loss:
+        groups.append({"params": [sigma_size], "lr": config.lr})
     return FusedAdam(groups, betas=(0.9, 0.99), eps=getattr(config, "adam_eps", 1e-15))
 
 
