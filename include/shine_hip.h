@@ -248,6 +248,27 @@ int shine_sdf_diff_loss(const float* pred, const float* sdf_label, const float* 
 int shine_ray_render_loss(const float* x, const float* y, const float* d_meas, int64_t rays, int32_t samples, int32_t neus_on,
                           float* loss_out, float* dy_out, void* workspace, void* stream);
 
+/* ---- Tier A: the semantic head (semantic_on), Decoder(is_geo_encoder=False).sem_label_prob / sem_label
+ *      (model/decoder.py:89-101) for 8 -> 32 -> 32 (ReLU, bias) -> nclass_out 32 -> n_class, n_class <= SHINE_SEM_MAX_CLASSES.
+ *      mlp: 6 device pointers W1 [32,8], b1 [32], W2 [32,32], b2 [32], Wc [n_class,32], bc [n_class] (float32, contiguous).
+ *      _forward: logp_out [n, n_class] = log_softmax(Wc h2 + bc) (z - max - log sum exp(z - max)) and / or label_out [n] =
+ *      the argmax of logp (the first index wins ties); either may be NULL, not both.
+ *      _backward: given grad_logp [n, n_class] = d loss / d logp and the saved logp: grad_feat_out [n, 8] (overwritten) or NULL;
+ *      grad_mlp: NULL (a frozen decoder) or 6 outputs shaped like mlp, OVERWRITTEN with bit-reproducible sums.  workspace:
+ *      SHINE_SEM_WORKSPACE_BYTES of 256-byte aligned device memory, zero when first used, left zero again (only read with
+ *      grad_mlp); calls sharing one must not overlap.
+ *      _query_labels: Mesher.query_points(query_sem=True) (utils/mesher.py:33-108): label_out [n] = sem_label(query_feature(coord,
+ *      faster=True)), the interpolation of shine_query_points, in one launch. */
+#define SHINE_SEM_MAX_CLASSES 32
+#define SHINE_SEM_WORKSPACE_BYTES 2621440
+int shine_sem_forward(const float* feat, int64_t n, const float* const* mlp, int32_t n_class, float* logp_out, int64_t* label_out,
+                      void* stream);
+int shine_sem_backward(const float* feat, const float* logp, const float* grad_logp, int64_t n, const float* const* mlp,
+                       int32_t n_class, float* grad_feat_out, float* const* grad_mlp, void* workspace, void* stream);
+int shine_sem_query_labels(const shine_tables* t, const shine_step_config* cfg, const float* coord, int64_t n,
+                           const float* const* feats, const int64_t* rows, const float* const* mlp, int32_t n_class,
+                           int64_t* label_out, void* stream);
+
 /* ---- Tier A (strict drop-in): the backward of FeatureOctree.query_feature as autograd derives it from
  *      model/feature_octree.py:222-234, and its own backward (needed by get_gradient(create_graph=True),
  *      utils/tools.py:175-185, when the eikonal term is differentiated, shine_batch.py:182-185).

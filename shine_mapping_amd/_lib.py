@@ -176,6 +176,10 @@ _SIGNATURES = {
     "shine_bce_loss": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float, C.c_int32, _P, _P, _P]),
     "shine_sdf_diff_loss": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float, C.c_int32, _P, _P, _P, _P]),
     "shine_ray_render_loss": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "shine_sem_forward": (C.c_int, [_P, C.c_int64, C.POINTER(_P), C.c_int32, _P, _P, _P]),
+    "shine_sem_backward": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(_P), C.c_int32, _P, C.POINTER(_P), _P, _P]),
+    "shine_sem_query_labels": (C.c_int, [_P, C.POINTER(StepConfig), _P, C.c_int64, C.POINTER(_P), C.POINTER(C.c_int64),
+                                         C.POINTER(_P), C.c_int32, _P, _P]),
     "shine_iter_graph_create": (C.c_int, [C.c_int32, C.POINTER(_P)]),
     "shine_iter_graph_destroy": (C.c_int, [_P]),
     "shine_iter_graph_commit": (C.c_int, [_P]),

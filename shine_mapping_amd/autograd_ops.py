@@ -573,3 +573,71 @@ class ShineTrainStep(torch.autograd.Function):
             raise RuntimeError("ShineTrainStep: backward through the fused node a second time (its buffers are freed)")
         flat.mul_(grad_loss.to(torch.float32))
         return (None,) * 7 + tuple(views)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Tier A: the semantic head (semantic_on)
+# ----------------------------------------------------------------------------------------------------------------------
+
+SEM_MAX_CLASSES = 32  # include/shine_hip.h SHINE_SEM_MAX_CLASSES
+SEM_WORKSPACE_BYTES = 2621440  # SHINE_SEM_WORKSPACE_BYTES
+_SEM_WORKSPACES = {}  # (device index, stream) -> the zeroed workspace of shine_sem_backward
+
+
+def sem_workspace(device):
+    """SHINE_SEM_WORKSPACE_BYTES of zeroed device memory for the current stream of `device` (the backward leaves its ticket
+    counters zero again; launches on one stream never overlap)"""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    key = (idx, _lib.current_stream_handle() if idx == torch.cuda.current_device() else torch.cuda.current_stream(idx).cuda_stream)
+    ws = _SEM_WORKSPACES.get(key)
+    if ws is None:
+        ws = _SEM_WORKSPACES[key] = torch.zeros(SEM_WORKSPACE_BYTES // 8, dtype=torch.float64, device=torch.device("cuda", idx))
+    return ws
+
+
+def sem_forward(feat, mlp, want_logp=True, want_label=False):
+    """(logp [N, C] | None, label [N] int64 | None) of shine_sem_forward; feat and the six tensors CUDA float32 contiguous"""
+    f = _f32c(feat)
+    w = [p.detach() for p in mlp]
+    n, C = f.shape[0], w[4].shape[0]
+    logp = torch.empty((n, C), dtype=torch.float32, device=f.device) if want_logp else None
+    label = torch.empty(n, dtype=torch.int64, device=f.device) if want_label else None
+    _lib.check(_lib.lib().shine_sem_forward(f.data_ptr(), n, _lib.ptr_array([p.data_ptr() for p in w]), C,
+                                            logp.data_ptr() if logp is not None else None,
+                                            label.data_ptr() if label is not None else None, _stream()),
+               "shine_sem_forward")
+    return logp, label
+
+
+class SemLabelProb(torch.autograd.Function):
+    """logp [N, C] = log_softmax(Wc relu(W2 relu(W1 feat + b1) + b2) + bc) — Decoder.sem_label_prob (model/decoder.py:89-97)
+    of the semantic decoder as ONE launch (shine_sem_forward); backward is ONE launch (shine_sem_backward: d loss / d feat and
+    the six weight grads, bit-reproducible).  Inputs: feat [N, 8], W1, b1, W2, b2, Wc [C, 32], bc [C].  Once differentiable.
+    The Python counterpart of the C++ extension's node."""
+
+    @staticmethod
+    def forward(ctx, feat, *mlp):
+        logp, _ = sem_forward(feat, mlp)
+        ctx.save_for_backward(_f32c(feat), logp, *[p.detach() for p in mlp])
+        return logp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        f, logp, *w = ctx.saved_tensors
+        want_f = ctx.needs_input_grad[0]
+        want_w = any(ctx.needs_input_grad[1:])
+        n, C = f.shape[0], logp.shape[1]
+        df = torch.empty((n, 8), dtype=torch.float32, device=f.device) if want_f else None
+        gw = [torch.empty_like(p, memory_format=torch.contiguous_format) for p in w] if want_w else None
+        gc = _f32c(g)
+        _lib.check(
+            _lib.lib().shine_sem_backward(
+                f.data_ptr(), logp.data_ptr(), gc.data_ptr(), n, _lib.ptr_array([p.data_ptr() for p in w]), C,
+                df.data_ptr() if df is not None else None, _lib.ptr_array([t.data_ptr() for t in gw]) if want_w else None,
+                sem_workspace(f.device).data_ptr(), _stream(),
+            ),
+            "shine_sem_backward",
+        )
+        grads = tuple(t if need else None for t, need in zip(gw, ctx.needs_input_grad[1:])) if want_w else (None,) * len(w)
+        return (df,) + grads

@@ -14,6 +14,8 @@
 //   bce_loss         sdf_bce_loss (utils/loss.py:17-24): shine_bce_loss, loss and d loss / d pred in one launch
 //   diff_loss        sdf_diff_loss (utils/loss.py:6-14): shine_sdf_diff_loss, loss and d loss / d pred in one launch
 //   ray_render_loss  batch_ray_rendering_loss (utils/loss.py:82-118): shine_ray_render_loss, loss and d loss / d y in one launch
+//   sem_label_prob   Decoder.sem_label_prob of the semantic decoder (model/decoder.py:89-97): shine_sem_forward, its backward
+//                    shine_sem_backward (d loss / d feat and the six weight grads in one launch); sem_label: labels only
 //   cal_regularization  FeatureOctree.cal_regularization (model/feature_octree.py:246-255): a node only while a gradient is live
 //   adam_step        FusedAdam.step (utils/tools.py:57-83's Adam): shine_adam_step without Python-side pointer arrays
 //
@@ -336,6 +338,47 @@ struct ScaledGradNode : public Node {
   void release_variables() override { dgrad.reset(); }
 };
 
+// logp = sem_label_prob(feat): once differentiable (the backward launch is not itself differentiable, so a double backward raises)
+struct SemLabelProbNode : public Node {
+  std::string name() const override { return "SemLabelProb[ext]"; }
+  Tensor feat, logp, ws;
+  std::vector<Tensor> mlp;
+  bool want_feat = false, want_w = false;
+  variable_list apply(variable_list&& grads) override {
+    if (at::GradMode::is_enabled())
+      throw std::runtime_error("SemLabelProb is differentiable once (a double backward through the semantic head is not implemented)");
+    variable_list out(7);
+    if (!grads[0].defined()) return out;
+    Tensor g = f32c(grads[0]);
+    const int64_t n = feat.size(0), C = logp.size(1);
+    Tensor df = want_feat ? at::empty({n, 8}, feat.options()) : Tensor();
+    std::vector<Tensor> gw;
+    std::vector<float*> gp;
+    if (want_w)
+      for (auto& p : mlp) {
+        gw.push_back(at::empty(p.sizes(), p.options()));
+        gp.push_back(gw.back().data_ptr<float>());
+      }
+    std::vector<const float*> mp;
+    for (auto& p : mlp) mp.push_back(p.data_ptr<float>());
+    check(shine_sem_backward(feat.data_ptr<float>(), logp.data_ptr<float>(), g.data_ptr<float>(), n, mp.data(), (int32_t)C,
+                             want_feat ? df.data_ptr<float>() : nullptr, want_w ? gp.data() : nullptr, ws.data_ptr(),
+                             cur_stream(feat)),
+          "shine_sem_backward");
+    if (want_feat) out[0] = df;
+    if (want_w)
+      for (int k = 0; k < 6; ++k)
+        if (should_compute_output(1 + k)) out[1 + k] = gw[k];
+    return out;
+  }
+  void release_variables() override {
+    feat.reset();
+    logp.reset();
+    ws.reset();
+    mlp.clear();
+  }
+};
+
 // reg = cal_regularization() (model/feature_octree.py:246-255; autograd_ops.OctreeRegularizer): the rows the octree's last
 // query addressed are flagged (shine_mark_touched) and summed by one row-parallel launch that clears the flags again.  A node
 // exists only while a level's features_last_frame is still a detached copy (`live`): from the second frame on the reference holds
@@ -604,6 +647,65 @@ Tensor ray_render_loss(const Tensor& x, const Tensor& y, const Tensor& d_meas, b
   return loss;
 }
 
+void check_sem(const Tensor& f, const std::vector<Tensor>& mlp) {
+  TORCH_CHECK(f.is_cuda() && f.scalar_type() == at::kFloat && f.dim() == 2 && f.size(1) == 8, "sem head: feat [N, 8] CUDA float32");
+  TORCH_CHECK(mlp.size() == 6, "sem head: W1, b1, W2, b2, Wc, bc");
+  TORCH_CHECK(mlp[4].dim() == 2 && mlp[4].size(0) >= 1 && mlp[4].size(0) <= SHINE_SEM_MAX_CLASSES, "sem head: 1..32 classes");
+  for (auto& p : mlp)
+    TORCH_CHECK(p.is_cuda() && p.get_device() == f.get_device() && p.scalar_type() == at::kFloat && p.is_contiguous(),
+                "sem head: CUDA float32 contiguous parameters on the input's device");
+}
+
+// -> logp [N, C] with a SemLabelProbNode when a gradient is wanted.  ws: SHINE_SEM_WORKSPACE_BYTES of zeroed device memory.
+Tensor sem_label_prob(const Tensor& feat, const std::vector<Tensor>& mlp, const Tensor& ws) {
+  check_sem(feat, mlp);
+  TORCH_CHECK(ws.is_cuda() && ws.get_device() == feat.get_device() && ws.numel() * ws.element_size() >= SHINE_SEM_WORKSPACE_BYTES,
+              "sem workspace: SHINE_SEM_WORKSPACE_BYTES of zeroed device memory on the input's device");
+  Tensor f, logp;
+  std::vector<Tensor> w;
+  {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    f = f32c(feat.detach());
+    for (auto& p : mlp) w.push_back(p.detach());
+    const int64_t n = f.size(0), C = w[4].size(0);
+    logp = at::empty({n, C}, f.options());
+    std::vector<const float*> mp;
+    for (auto& p : w) mp.push_back(p.data_ptr<float>());
+    check(shine_sem_forward(f.data_ptr<float>(), n, mp.data(), (int32_t)C, logp.data_ptr<float>(), nullptr, cur_stream(f)),
+          "shine_sem_forward");
+  }
+  variable_list inputs = {feat};
+  inputs.insert(inputs.end(), mlp.begin(), mlp.end());
+  if (at::GradMode::is_enabled() && requires_any(feat, mlp)) {
+    auto node = make_node<SemLabelProbNode>(inputs);
+    node->feat = f;
+    node->logp = logp.detach();  // (an alias: the output itself would hold its own node)
+    node->ws = ws;
+    node->mlp = w;
+    node->want_feat = feat.requires_grad();
+    bool ww = false;
+    for (auto& p : mlp) ww = ww || p.requires_grad();
+    node->want_w = ww;
+    torch::autograd::create_gradient_edge(logp, node);
+  }
+  return logp;
+}
+
+// -> label [N] int64 (no graph)
+Tensor sem_label(const Tensor& feat, const std::vector<Tensor>& mlp) {
+  check_sem(feat, mlp);
+  at::AutoDispatchBelowADInplaceOrView guard;
+  Tensor f = f32c(feat.detach());
+  const int64_t n = f.size(0);
+  Tensor label = at::empty({n}, f.options().dtype(at::kLong));
+  std::vector<const float*> mp;
+  for (auto& p : mlp) mp.push_back(p.data_ptr<float>());
+  check(shine_sem_forward(f.data_ptr<float>(), n, mp.data(), (int32_t)mlp[4].size(0), nullptr, label.data_ptr<int64_t>(),
+                          cur_stream(f)),
+        "shine_sem_forward");
+  return label;
+}
+
 // FeatureOctree.cal_regularization for the coordinates of the octree's last query.  flags: one uint8 per row and level, all zero
 // (left zero again).  live[s]: level s's features_last_frame is a detached copy (its gradient does not cancel).
 Tensor cal_regularization(const std::shared_ptr<TierAState>& st, const Tensor& coord, const std::vector<Tensor>& feats,
@@ -738,6 +840,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bce_loss", &bce_loss);
   m.def("diff_loss", &diff_loss);
   m.def("ray_render_loss", &ray_render_loss);
+  m.def("sem_label_prob", &sem_label_prob);
+  m.def("sem_label", &sem_label);
   m.def("cal_regularization", &cal_regularization);
   m.def("adam_step", &adam_step);
   m.def("config_bytes", []() { return (int64_t)sizeof(shine_step_config); });

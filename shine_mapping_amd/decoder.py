@@ -6,8 +6,9 @@ reference's checkpoints load with ``load_state_dict``): ``layers.{0,1}``, ``lout
 one launch each — get_gradient(create_graph=True), utils/tools.py:175-185, differentiates it twice) for the
 decoder shape every shipped config uses (8 -> 32 -> 32 -> 1 with bias) on CUDA float32 input; the benchmarked
 tier never calls it — the fused HIP step reads the six parameter tensors directly (ops.train_step).
-The out-of-scope heads (time-conditioned, semantic; flags off in every shipped yaml) and other decoder shapes
-are plain torch composites, as in the reference.
+`sem_label_prob` / `sem_label` of the semantic decoder (semantic_on) are HIP launches for the same hidden shape with up to 32
+classes (csrc/shine_semantic.hip).  The time-conditioned head and other decoder shapes are plain torch composites, as in the
+reference.
 """
 import weakref
 
@@ -88,13 +89,51 @@ class Decoder(nn.Module):
 
     # model/decoder.py:89-101
     def sem_label_prob(self, sum_features):
-        h = sum_features
+        """log_softmax over the classes.  The shape of the semantic decoder of every shipped config (8 -> 32 -> 32 -> C <= 32
+        with bias) on CUDA float32 runs as ONE HIP launch whose backward is one more (csrc/shine_semantic.hip: the C++
+        extension's SemLabelProb node, autograd_ops.SemLabelProb without it); anything else is the reference's composite."""
+        mlp = self._sem_params_for(sum_features)
+        if mlp is None:
+            return self._sem_composite(sum_features)
+        ext = _ext.module()
+        if ext is not None:
+            return ext.sem_label_prob(sum_features, mlp, autograd_ops.sem_workspace(sum_features.device))
+        return autograd_ops.SemLabelProb.apply(sum_features, *mlp)
+
+    def sem_label(self, sum_features):
+        """torch.argmax(sem_label_prob(f), dim=1): on the HIP path the labels alone, no [N, C] output and no graph"""
+        mlp = self._sem_params_for(sum_features)
+        if mlp is None:
+            return torch.argmax(self._sem_composite(sum_features), dim=1)
+        with torch.no_grad():
+            ext = _ext.module()
+            if ext is not None:
+                return ext.sem_label(sum_features.detach(), [p.detach() for p in mlp])
+            return autograd_ops.sem_forward(sum_features, mlp, want_logp=False, want_label=True)[1]
+
+    def _sem_composite(self, sum_features):
+        h = sum_features  # the reference's composite
         for l in self.layers:
             h = F.relu(l(h))
         return F.log_softmax(self.nclass_out(h), dim=1)
 
-    def sem_label(self, sum_features):
-        return torch.argmax(self.sem_label_prob(sum_features), dim=1)
+    def sem_params(self):
+        """W1, b1, W2, b2, Wc, bc of the semantic head in the order shine_sem_forward expects"""
+        if not self.fusable or self.nclass_out.out_features > autograd_ops.SEM_MAX_CLASSES:
+            raise NotImplementedError("the HIP semantic head supports 8 -> 32 -> 32 -> C <= 32 with bias")
+        m = self._modules
+        hidden = m["layers"]._modules
+        l0, l1, lc = hidden["0"]._parameters, hidden["1"]._parameters, m["nclass_out"]._parameters
+        return [l0["weight"], l0["bias"], l1["weight"], l1["bias"], lc["weight"], lc["bias"]]
+
+    def _sem_params_for(self, f):
+        """the six tensors when `f` and the head take the HIP path, else None"""
+        if not (self.fusable and self.nclass_out.out_features <= autograd_ops.SEM_MAX_CLASSES and isinstance(f, torch.Tensor)
+                and f.is_cuda and f.dtype == torch.float32 and f.dim() == 2 and f.shape[1] == _lib.FEATURE_DIM
+                and f.shape[0] > 0):
+            return None
+        mlp = self.sem_params()
+        return mlp if self._params_on(f.device, mlp) else None
 
     # ---- fused-path plumbing
     def _params_on(self, device, mlp=None) -> bool:

@@ -17,8 +17,9 @@ Four FUNCTIONS of the reference's own `utils` modules are additionally re-bound 
 for anything it does not cover, each with an opt-out environment variable (= "0"):
 
     utils.tools.setup_optimizer  ->  optim.setup_optimizer: the same Adam groups (utils/tools.py:57-83) as ONE fused launch per
-                                     step instead of torch's multi-tensor Adam (ray_loss: with the learnable sigma_size
-                                     group, :74-76)                                       SHINE_DROPIN_FUSED_OPTIMIZER
+                                     step instead of torch's multi-tensor Adam (semantic_on: with the semantic decoder's
+                                     group, :64-66; ray_loss: with the learnable sigma_size group, :74-76)
+                                                                                          SHINE_DROPIN_FUSED_OPTIMIZER
     utils.loss.sdf_bce_loss      ->  losses.sdf_bce_loss: loss and d loss / d pred in ONE launch      SHINE_DROPIN_FUSED_LOSS
     utils.loss.sdf_diff_loss     ->  losses.sdf_diff_loss (sdf_l1 / sdf_l2): the same, one launch     (same opt-out)
     utils.loss.batch_ray_rendering_loss -> losses.batch_ray_rendering_loss (ray_loss, dr / dr_neus): loss and d loss / d y
@@ -96,7 +97,9 @@ def status():
     """what patch_utils() re-bound (name -> True / the reason it did not)"""
     import torch
 
-    return dict(_STATUS, single_thread_backward=not torch.autograd.is_multithreading_enabled())
+    # (methods of the replaced Decoder, not re-bound names: the semantic head's HIP launches for the shipped decoder shape)
+    return dict(_STATUS, single_thread_backward=not torch.autograd.is_multithreading_enabled(),
+                sem_label_prob=_INSTALLED and "HIP (csrc/shine_semantic.hip) for 8 -> 32 -> 32 -> C <= 32, else the composite")
 
 
 def _on(var):
@@ -164,9 +167,12 @@ def patch_utils():
         if _on("SHINE_DROPIN_FUSED_OPTIMIZER"):
             def setup_optimizer(config, octree_feat, mlp_geo_param, mlp_sem_param, sigma_size):
                 tensors = list(octree_feat) + list(mlp_geo_param or [])
+                semantic_on = bool(getattr(config, "semantic_on", False))
+                if semantic_on:  # (the semantic decoder's group, utils/tools.py:64-66)
+                    tensors += list(mlp_sem_param or [])
                 if getattr(config, "ray_loss", False):  # (the learnable sigma_size group, utils/tools.py:74-76)
                     tensors.append(sigma_size if isinstance(sigma_size, torch.Tensor) else None)
-                if (getattr(config, "opt_adam", True) and not getattr(config, "semantic_on", False) and tensors
+                if (getattr(config, "opt_adam", True) and not (semantic_on and getattr(config, "ray_loss", False)) and tensors
                         and all(isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.float32 for p in tensors)):
                     return optim.setup_optimizer(config, octree_feat, mlp_geo_param, mlp_sem_param, sigma_size)
                 return ref_setup(config, octree_feat, mlp_geo_param, mlp_sem_param, sigma_size)

@@ -3,7 +3,8 @@
 `query_points` keeps the reference's argument list and return convention (numpy arrays; `sdf_pred` is the NEGATED
 decoder output, `mc_mask` says whether the point's node exists at the marching-cubes check level) but runs each
 chunk as ONE launch of `shine_query_points` (csrc/shine_query.hip): no `[N,8]` index tensors, no `[N,F]` features
-and no per-level host round trips.  Marching cubes itself (skimage, utils/mesher.py:262-292) and the open3d
+and no per-level host round trips.  With `query_sem` the semantic labels are ONE more launch per chunk
+(`shine_sem_query_labels`, csrc/shine_semantic.hip: interpolation, semantic decoder, argmax).  Marching cubes itself (skimage, utils/mesher.py:262-292) and the open3d
 bounding-box plumbing stay with the caller: they are outside the hot path.
 """
 from __future__ import annotations
@@ -38,6 +39,27 @@ def query_points_device(octree, decoder, coord, check_level=0, negate=True, quer
         "shine_query_points",
     )
     return sdf, (mask.bool() if mask is not None else None)
+
+
+def query_labels_device(octree, sem_decoder, coord):
+    """Semantic labels of `coord [N,3]` (device, scaled to [-1,1]): sem_label(query_feature(coord, True)) (utils/mesher.py:72-73,
+    :98) as ONE launch of shine_sem_query_labels (csrc/shine_semantic.hip); int64 [N] on the device."""
+    t = octree._require_tables()
+    coord = octree._check_coord(coord.detach())
+    n = coord.shape[0]
+    label = torch.empty(n, dtype=torch.int64, device=coord.device)
+    mlp = [p.detach() for p in sem_decoder.sem_params()]
+    if not sem_decoder._params_on(coord.device, mlp):
+        raise ValueError("the semantic decoder's parameters must be CUDA float32 contiguous on the coordinates' device")
+    cfg = octree.step_config()
+    _lib.check(
+        _lib.lib().shine_sem_query_labels(
+            t.handle, C.byref(cfg), coord.data_ptr(), n, octree.feature_ptrs(), octree.row_counts(),
+            _lib.ptr_array([p.data_ptr() for p in mlp]), int(mlp[4].shape[0]), label.data_ptr(), _stream(),
+        ),
+        "shine_sem_query_labels",
+    )
+    return label
 
 
 class Mesher:
@@ -77,8 +99,6 @@ class Mesher:
 
     def query_points(self, coord, bs, query_sdf=True, query_sem=False, query_mask=True):
         """utils/mesher.py:33-108.  Returns (sdf_pred, sem_pred, mc_mask) as numpy arrays (None when not asked for)."""
-        if query_sem:
-            raise NotImplementedError("semantic decoding is outside the SDF hot path (SURVEY.md §8): use the reference's Mesher")
         if getattr(self.config, "time_conditioned", False):
             raise NotImplementedError("time-conditioned decoding is outside the SDF hot path")
         sample_count = coord.shape[0]
@@ -88,18 +108,27 @@ class Mesher:
         with torch.no_grad():
             if iter_n > 1:  # chunked: the reference fills float64 numpy buffers (:43-53)
                 sdf_pred = np.zeros(sample_count) if query_sdf else None
+                sem_pred = np.zeros(sample_count) if query_sem else None
                 mc_mask = np.zeros(sample_count) if query_mask else None
                 for i in range(iter_n):
                     head, tail = i * bs, min((i + 1) * bs, sample_count)
-                    sdf, mask = query_points_device(self.octree, self.geo_decoder, coord[head:tail].to(dev),
-                                                    check_level, True, query_sdf, query_mask)
+                    chunk = coord[head:tail].to(dev)
+                    if query_sdf or query_mask:
+                        sdf, mask = query_points_device(self.octree, self.geo_decoder, chunk, check_level, True, query_sdf,
+                                                        query_mask)
                     if query_sdf:
                         sdf_pred[head:tail] = sdf.cpu().numpy()
+                    if query_sem:
+                        sem_pred[head:tail] = query_labels_device(self.octree, self.sem_decoder, chunk).cpu().numpy()
                     if query_mask:
                         mc_mask[head:tail] = mask.cpu().numpy()
             else:
-                sdf, mask = query_points_device(self.octree, self.geo_decoder, coord.to(dev), check_level, True,
-                                                query_sdf, query_mask)
+                sdf = mask = None
+                if query_sdf or query_mask:
+                    sdf, mask = query_points_device(self.octree, self.geo_decoder, coord.to(dev), check_level, True,
+                                                    query_sdf, query_mask)
                 sdf_pred = sdf.cpu().numpy() if query_sdf else None
+                # (the reference's unchunked branch returns the int64 array of .cpu().numpy(), :98)
+                sem_pred = query_labels_device(self.octree, self.sem_decoder, coord.to(dev)).cpu().numpy() if query_sem else None
                 mc_mask = mask.cpu().numpy() if query_mask else None
-        return sdf_pred, None, mc_mask
+        return sdf_pred, sem_pred, mc_mask

@@ -2,6 +2,7 @@
 
 setup_optimizer builds torch.optim.Adam(betas=(0.9, 0.99), eps=config.adam_eps) over
   group 0: the geo decoder's parameters, lr, weight_decay (L2)                       (:60-63)
+  with semantic_on: the semantic decoder's parameters, lr, weight_decay (L2)          (:64-66)
   then one group per feature level, leaf level first, lr *= lr_level_reduce_ratio   (:68-72)
   with ray_loss: a last group holding the learnable sigma_size, lr, no weight decay   (:74-76)
 FusedAdam takes the same param_groups (so step_lr_decay, utils/tools.py:135-155, keeps working on
@@ -311,17 +312,23 @@ class FusedAdam:
 
 
 def setup_optimizer(config, octree_feat, mlp_geo_param, mlp_sem_param=None, sigma_size=None):
-    """utils/tools.py:57-83 with the fused optimiser (Adam only; opt_adam is True in config defaults, :167).  With ray_loss the
-    learnable sigma_size of the rendering loss is the last group (:74-76)."""
-    if getattr(config, "semantic_on", False) or not getattr(config, "opt_adam", True):
-        raise NotImplementedError("fused optimiser covers Adam without the semantic head")
+    """utils/tools.py:57-83 with the fused optimiser (Adam only; opt_adam is True in config defaults, :167).  With semantic_on
+    the semantic decoder's parameters are the second group (:64-66); with ray_loss the learnable sigma_size of the rendering
+    loss is the last group (:74-76)."""
+    semantic_on = bool(getattr(config, "semantic_on", False))
     ray_loss = bool(getattr(config, "ray_loss", False))
+    if not getattr(config, "opt_adam", True):
+        raise NotImplementedError("fused optimiser covers Adam (opt_adam), not SGD")
+    if semantic_on and ray_loss:  # (the reference's shapes do not match there either, shine_batch.py:133)
+        raise NotImplementedError("fused optimiser: semantic_on together with ray_loss is not supported")
     if ray_loss and not isinstance(sigma_size, torch.Tensor):
         raise ValueError("ray_loss: setup_optimizer needs the learnable sigma_size tensor")
     lr_cur = config.lr
     groups = []
     if mlp_geo_param is not None:
         groups.append({"params": mlp_geo_param, "lr": lr_cur, "weight_decay": config.weight_decay})
+    if semantic_on and mlp_sem_param is not None:  # (:64-66; the head's lout never receives a grad and is skipped, as by torch)
+        groups.append({"params": mlp_sem_param, "lr": lr_cur, "weight_decay": config.weight_decay})
     L = config.tree_level_feat
     for i in range(L):
         groups.append({"params": [octree_feat[L - i - 1]], "lr": lr_cur})

@@ -240,3 +240,14 @@ def draw_batch(pool, n, gen=None):
     """LiDARDataset.get_batch, point-sample branch (dataset/lidar_dataset.py:430-450)."""
     idx = torch.randint(0, pool.sdf_label.shape[0], (n,), device=pool.sdf_label.device, generator=gen)
     return pool.coord[idx, :], pool.sdf_label[idx], pool.weight[idx]
+
+
+def semantic_labels(coord, weight, n_class=21, cell=0.02):
+    """Class labels for samples, the way dataSampler.sample assigns them (utils/data_sampler.py:59,70): a surface sample
+    (weight > 0) carries the class of the point it was drawn around — here a class in 1..n_class-1 that is a fixed function of
+    the sample's cell of size `cell`, so any batch drawn from a pool is labelled consistently — and clearance / free-space
+    samples carry 0.  int64 [N] on coord's device."""
+    q = torch.floor(coord.detach() / cell).to(torch.int64)
+    h = (q[:, 0] * 73856093) ^ (q[:, 1] * 19349663) ^ (q[:, 2] * 83492791)
+    lab = 1 + torch.remainder(h, n_class - 1)
+    return torch.where(weight > 0, lab, torch.zeros_like(lab))
