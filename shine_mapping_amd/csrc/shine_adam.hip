@@ -36,17 +36,6 @@ struct AdamArgs {
   const float* lr_dev;    // [n_seg] or null
 };
 
-struct AdamScalars {
-  float b1, b2, eps, bc1, bc2_sqrt;
-};
-__device__ __forceinline__ void adam1(float& p, float& g, float& m, float& v, const AdamScalars& a, float lr, float wd) {
-  const float gg = g + wd * p;
-  m = a.b1 * m + (1.0f - a.b1) * gg;
-  v = a.b2 * v + (1.0f - a.b2) * gg * gg;
-  const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-  p -= (lr / a.bc1) * (m / denom);
-}
-
 // graph-replayable form: one thread counts the step and derives the bias corrections (adam_advance, shine_internal.hpp) —
 // unless the fused step that precedes the optimiser in the iteration already did (cfg->adam_state): then there is no launch
 __global__ void k_adam_prep(long long* step_state, float b1, float b2) { adam_advance(step_state, b1, b2); }

@@ -79,6 +79,17 @@ __device__ __forceinline__ int probe(const LevelDev& L, unsigned long long key) 
   return -1;
 }
 
+// FeatureOctree.get_indices of one level (model/feature_octree.py:199-218): quantise, Morton code, probe
+__device__ __forceinline__ int level_slot(const LevelDev& Lv, float x0, float x1, float x2) {
+  return probe(Lv, morton3(quantize(x0, Lv.res), quantize(x1, Lv.res), quantize(x2, Lv.res)));
+}
+
+// the eight corner ids of a table slot (corner c = 4*cx + 2*cy + cz)
+__device__ __forceinline__ void corner_ids(const int4* vals, unsigned int slot, int (&ids)[8]) {
+  const int4 i0 = vals[2u * slot], i1 = vals[2u * slot + 1u];
+  ids[0] = i0.x, ids[1] = i0.y, ids[2] = i0.z, ids[3] = i0.w, ids[4] = i1.x, ids[5] = i1.y, ids[6] = i1.z, ids[7] = i1.w;
+}
+
 // ---- FeatureOctree.interpolat (model/feature_octree.py:172-196), one axis:
 //      u = res*(x*0.5+0.5); d = frac(u); t = 3d^2 - 2d^3 (or d); dt = dt/dx.
 struct Axis {
@@ -169,10 +180,44 @@ __device__ __forceinline__ cfloat* relaunder(cfloat* p) {
   return p;
 }
 
+// The packed decoder (W1, b1, W2, b2, w3, b3) through the constant address space.
+struct MlpDev {
+  cfloat *W1, *B1, *W2, *B2, *W3, *B3;
+};
+__device__ __forceinline__ MlpDev mlp_dev(const float* const (&mlp)[6]) {
+  return {uniform_ro(mlp[0]), uniform_ro(mlp[1]), uniform_ro(mlp[2]), uniform_ro(mlp[3]), uniform_ro(mlp[4]), uniform_ro(mlp[5])};
+}
+
+// ---- Decoder.sdf (model/decoder.py:49-63), lane = point: layer 1 unrolled into h1 = relu(W1 f + b1), then layers 2 + 3 as a
+//      ROLLED loop over the `rows` (= opaque(H)) weight rows of W2 (two s_load_dwordx16 each) that consumes h2 as it is
+//      produced.
+__device__ __forceinline__ float sdf_decode(const MlpDev& w, const float (&f)[F], int rows) {
+  float h1[H];
+  {
+    cfloat *const W1i = relaunder(w.W1), *const B1i = relaunder(w.B1);  // keep the loads inside this point's iteration
+#pragma unroll
+    for (int j = 0; j < H; ++j) {
+      float z = B1i[j];
+#pragma unroll
+      for (int q = 0; q < F; ++q) z = fmaf(W1i[j * F + q], f[q], z);
+      h1[j] = fmaxf(z, 0.f);
+    }
+  }
+  float y = w.B3[0];
+#pragma clang loop vectorize(disable) interleave(disable) unroll_count(2)
+  for (int j = 0; j < rows; ++j) {
+    float z = w.B2[j];
+#pragma unroll
+    for (int k = 0; k < H; ++k) z = fmaf(w.W2[j * H + k], h1[k], z);
+    y = fmaf(w.W3[j], fmaxf(z, 0.f), y);
+  }
+  return y;
+}
+
 // hardware fp32 atomic add (global_atomic_add_f32), no CAS loop
 __device__ __forceinline__ void atomic_add_f32(float* p, float v) { unsafeAtomicAdd(p, v); }
 
-// ---- lane-per-point kernels (shine_step_v0.hip, shine_mlp.hip): decoder weight grads contract over POINTS; the
+// ---- lane-per-point kernels (shine_step_v0.hip, shine_mlp.hip, shine_semantic.hip): decoder weight grads contract over POINTS; the
 //      per-point vectors of one wave are staged in LDS as [64 points][ST] and every lane owns a few output entries.
 constexpr int ST = 75;  // staging row stride in floats (odd -> conflict-free column writes)
 
@@ -183,6 +228,20 @@ __device__ __forceinline__ void contract64(const float* st, int j, int rb, float
   for (int p = 0; p < 64; ++p) {
     const float* row = st + p * ST;
     float l = row[j];
+    if (with_bias) acc_left += l;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) acc[q] = fmaf(l, row[rb + q], acc[q]);
+  }
+}
+
+// contract64 with a bounded unroll: the fully unrolled 64-point loop keeps ~150 LDS results in flight
+template <int NQ>
+__device__ __forceinline__ void contract64r(const float* st, int j, int rb, float (&acc)[NQ], float& acc_left,
+                                            bool with_bias) {
+#pragma clang loop vectorize(disable) interleave(disable) unroll_count(4)
+  for (int p = 0; p < 64; ++p) {
+    const float* row = st + p * ST;
+    const float l = row[j];
     if (with_bias) acc_left += l;
 #pragma unroll
     for (int q = 0; q < NQ; ++q) acc[q] = fmaf(l, row[rb + q], acc[q]);

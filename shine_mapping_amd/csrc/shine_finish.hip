@@ -18,18 +18,6 @@
 
 namespace shine {
 
-struct FinScalars {
-  float b1, b2, eps, bc1, bc2_sqrt;
-};
-
-__device__ __forceinline__ void fin_adam1(float& p, float g, float& m, float& v, const FinScalars& a, float lr, float wd) {
-  const float gg = g + wd * p;
-  m = a.b1 * m + (1.0f - a.b1) * gg;
-  v = a.b2 * v + (1.0f - a.b2) * gg * gg;
-  const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-  p -= (lr / a.bc1) * (m / denom);
-}
-
 // blocks [0, fb): feature rows, one thread per row; blocks [fb, fb + db): decoder, one wave per unit of 8 elements;
 // block fb + db: the loss terms; blocks behind it: the sorted draw of the next iteration (one-launch form of the sampler)
 __global__ __launch_bounds__(256) void k_finish(const FinArgs a, int fb, int db) {
@@ -48,7 +36,7 @@ __global__ __launch_bounds__(256) void k_finish(const FinArgs a, int fb, int db)
     return;
   }
   const float* bc = reinterpret_cast<const float*>(a.step_state + 1);
-  const FinScalars sc = {a.b1, a.b2, a.eps, bc[0], bc[1]};
+  const AdamScalars sc = {a.b1, a.b2, a.eps, bc[0], bc[1]};
   if (threadIdx.x < a.n_seg) s_lr[threadIdx.x] = a.lr_dev[a.seg[threadIdx.x].lr_idx];
   __syncthreads();
   const int lane = threadIdx.x & 63;
@@ -108,7 +96,7 @@ __global__ __launch_bounds__(256) void k_finish(const FinArgs a, int fb, int db)
         }
         const float lr = s_lr[s];
 #pragma unroll
-        for (int q = 0; q < F; ++q) fin_adam1(p[q], g[q], m[q], v[q], sc, lr, S.wd);
+        for (int q = 0; q < F; ++q) adam1(p[q], g[q], m[q], v[q], sc, lr, S.wd);
         pp[0] = make_float4(p[0], p[1], p[2], p[3]);
         pp[1] = make_float4(p[4], p[5], p[6], p[7]);
         mp[0] = make_float4(m[0], m[1], m[2], m[3]);
@@ -163,7 +151,7 @@ __global__ __launch_bounds__(256) void k_finish(const FinArgs a, int fb, int db)
       // FeatureOctree.set_zero (model/feature_octree.py:78-81) zeroes a trash row before the query, i.e. before this update
       float p = u < a.n_levels ? 0.f : S.p[e], m = S.m[e], v = S.v[e];
       const float g = S.g[e] + t;
-      fin_adam1(p, g, m, v, sc, s_lr[s], S.wd);
+      adam1(p, g, m, v, sc, s_lr[s], S.wd);
       S.p[e] = p;
       S.m[e] = m;
       S.v[e] = v;

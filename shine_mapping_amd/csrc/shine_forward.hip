@@ -60,8 +60,7 @@ __global__ __launch_bounds__(256) void k_forward_points(FwdArgs a) {
     for (int s = 0; s < LMAX; ++s) {
       slot[s] = -1;
       if (s < L) {
-        const LevelDev& Lv = a.ls.lv[s];
-        slot[s] = probe(Lv, morton3(quantize(x0, Lv.res), quantize(x1, Lv.res), quantize(x2, Lv.res)));
+        slot[s] = level_slot(a.ls.lv[s], x0, x1, x2);
       }
     }
     float f[F];
@@ -127,8 +126,8 @@ __global__ __launch_bounds__(256) void k_forward_points(FwdArgs a) {
       for (int s = 0; s < L; ++s) {
         if (slot[s] < 0) continue;
         const LevelDev& Lv = a.ls.lv[s];
-        const int4 i0 = Lv.vals[2u * (unsigned int)slot[s]], i1 = Lv.vals[2u * (unsigned int)slot[s] + 1u];
-        const int ids[8] = {i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w};
+        int ids[8];
+        corner_ids(Lv.vals, (unsigned int)slot[s], ids);
         for (int c = 0; c < 8; ++c) {
           const unsigned int row = (unsigned int)ids[c];
           if (atomicExch(a.reg_stamp[s] + row, a.reg_epoch) == a.reg_epoch) continue;
@@ -145,6 +144,8 @@ __global__ __launch_bounds__(256) void k_forward_points(FwdArgs a) {
       }
     }
     if (!with_mlp) continue;
+    // sdf_decode (device.hpp) with t riding on layer 2; kept here: through the shared helpers (interpolation included) the
+    // d pred / d coord builds of this kernel took 2-18 more VGPRs
     float h1[H];
     {
       cfloat *const W1i = relaunder(W1), *const B1i = relaunder(B1);  // keep the loads inside this iteration
@@ -228,15 +229,11 @@ __global__ __launch_bounds__(256) void k_query_indices(FwdArgs a) {
   for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < a.n; p += (long long)gridDim.x * 256) {
     const float x0 = a.coord[3 * p], x1 = a.coord[3 * p + 1], x2 = a.coord[3 * p + 2];
     for (int s = 0; s < L; ++s) {
-      const LevelDev& Lv = a.ls.lv[s];
-      const int slot = probe(Lv, morton3(quantize(x0, Lv.res), quantize(x1, Lv.res), quantize(x2, Lv.res)));
-      int4 v0 = make_int4(-1, -1, -1, -1), v1 = v0;
-      if (slot >= 0) {
-        v0 = Lv.vals[2 * slot];
-        v1 = Lv.vals[2 * slot + 1];
-      }
+      const int slot = level_slot(a.ls.lv[s], x0, x1, x2);
+      int ids[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+      if (slot >= 0) corner_ids(a.ls.lv[s].vals, (unsigned int)slot, ids);
       long long* o = a.idx_out[L - 1 - s] + p * 8;
-      o[0] = v0.x, o[1] = v0.y, o[2] = v0.z, o[3] = v0.w, o[4] = v1.x, o[5] = v1.y, o[6] = v1.z, o[7] = v1.w;
+      for (int c = 0; c < 8; ++c) o[c] = ids[c];
     }
   }
 }

@@ -66,6 +66,19 @@ __device__ inline void adam_advance(long long* state, float b1, float b2) {
   bc[1] = (float)sqrt(1.0 - p2);
 }
 
+// torch.optim.Adam's update of one element (no amsgrad, L2 weight decay; bc1 = 1 - b1^t, bc2_sqrt = sqrt(1 - b2^t)): the one
+// form k_adam (shine_adam.hip) and k_finish (shine_finish.hip) share, bit-identical to torch's.
+struct AdamScalars {
+  float b1, b2, eps, bc1, bc2_sqrt;
+};
+__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamScalars& a, float lr, float wd) {
+  const float gg = g + wd * p;
+  m = a.b1 * m + (1.0f - a.b1) * gg;
+  v = a.b2 * v + (1.0f - a.b2) * gg * gg;
+  const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
+  p -= (lr / a.bc1) * (m / denom);
+}
+
 int set_error(int code, const char* msg);
 int set_hip_error(hipError_t e, const char* what);
 

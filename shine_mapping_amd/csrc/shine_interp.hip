@@ -62,19 +62,14 @@ __global__ __launch_bounds__(256) void k_interp_bwd(InterpArgs a) {
     for (int i = 0; i < F; ++i) og[i] = 0.f;
     for (int s = 0; s < a.n_levels; ++s) {
       const LevelDev& Lv = a.ls.lv[s];
-      unsigned long long key = morton3(quantize(x0, Lv.res), quantize(x1, Lv.res), quantize(x2, Lv.res));
-      const int slot = probe(Lv, key);
+      const int slot = level_slot(Lv, x0, x1, x2);
       Axis X = axis_weight<POLY>(x0, Lv.res, Lv.dres), Y = axis_weight<POLY>(x1, Lv.res, Lv.dres),
            Z = axis_weight<POLY>(x2, Lv.res, Lv.dres);
       float w[8], dw[8][3];
       corner_weights(X.t, Y.t, Z.t, w);
       corner_weight_grads(X, Y, Z, dw);
       int ids[8];
-      if (slot >= 0) {
-        int4 v0 = Lv.vals[2 * slot], v1 = Lv.vals[2 * slot + 1];
-        ids[0] = v0.x; ids[1] = v0.y; ids[2] = v0.z; ids[3] = v0.w;
-        ids[4] = v1.x; ids[5] = v1.y; ids[6] = v1.z; ids[7] = v1.w;
-      }
+      if (slot >= 0) corner_ids(Lv.vals, (unsigned int)slot, ids);
       float csum = 0.f;  // a miss: all eight corners address the trash row (index -1, :205,231), which receives sum_c
       float coefs[8];
       int sids[8];  // scatter targets: -1 = nothing (a miss goes to the trash row below, a padding lane nowhere)

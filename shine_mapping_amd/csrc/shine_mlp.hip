@@ -29,52 +29,18 @@ struct MlpArgs {
   int want_wgrad;
 };
 
-// contract64 (device.hpp) with a bounded unroll: the fully unrolled 64-point loop keeps ~150 LDS results in flight
-template <int NQ>
-__device__ __forceinline__ void contract64r(const float* st, int j, int rb, float (&acc)[NQ], float& acc_left,
-                                            bool with_bias) {
-#pragma clang loop vectorize(disable) interleave(disable) unroll_count(4)
-  for (int p = 0; p < 64; ++p) {
-    const float* row = st + p * ST;
-    const float l = row[j];
-    if (with_bias) acc_left += l;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) acc[q] = fmaf(l, row[rb + q], acc[q]);
-  }
-}
-
 // a rolled loop over weight rows: opaque trip count (device.hpp), and keep the loop vectoriser away from it
 #define ROW_LOOP_STR(x) #x
 #define ROW_LOOP(n) _Pragma(ROW_LOOP_STR(clang loop vectorize(disable) interleave(disable) unroll_count(n)))
 
-// ---- forward: lane = point, everything in registers; layer 1 unrolled (h1 is a register array), layer 2 a rolled loop
-// over its weight rows
+// ---- forward: lane = point, everything in registers (sdf_decode, device.hpp)
 __global__ __launch_bounds__(256) void k_mlp_fwd(MlpArgs a) {
-  cfloat *const W1 = uniform_ro(a.mlp[0]), *const B1 = uniform_ro(a.mlp[1]), *const W2 = uniform_ro(a.mlp[2]),
-               *const B2 = uniform_ro(a.mlp[3]), *const W3 = uniform_ro(a.mlp[4]), *const B3 = uniform_ro(a.mlp[5]);
+  const MlpDev W = mlp_dev(a.mlp);
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long long)gridDim.x * 256) {
     const float4* row = reinterpret_cast<const float4*>(a.feat + i * F);
     const float4 r0 = row[0], r1 = row[1];
     const float f[F] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-    float h1[H];
-    cfloat *const W1i = relaunder(W1), *const B1i = relaunder(B1);
-#pragma unroll
-    for (int k = 0; k < H; ++k) {
-      float z = B1i[k];
-#pragma unroll
-      for (int q = 0; q < F; ++q) z = fmaf(W1i[k * F + q], f[q], z);
-      h1[k] = fmaxf(z, 0.f);
-    }
-    float y = B3[0];
-    const int rows = opaque(H);
-ROW_LOOP(2)
-    for (int j = 0; j < rows; ++j) {
-      float z = B2[j];
-#pragma unroll
-      for (int k = 0; k < H; ++k) z = fmaf(W2[j * H + k], h1[k], z);
-      y = fmaf(W3[j], fmaxf(z, 0.f), y);
-    }
-    a.pred[i] = y;
+    a.pred[i] = sdf_decode(W, f, opaque(H));
   }
 }
 

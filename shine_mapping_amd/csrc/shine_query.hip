@@ -26,11 +26,8 @@ struct QueryArgs {
 template <int L, bool POLY>
 __global__ __launch_bounds__(256) void k_query_points(QueryArgs a) {
   // decoder weights: wave-uniform, read-only -> scalar loads into SGPRs that the FMAs take as operands (device.hpp)
-  cfloat* W1 = nullptr, *B1 = nullptr, *W2 = nullptr, *B2 = nullptr, *W3 = nullptr, *B3 = nullptr;
-  if (a.sdf_out) {  // wave-uniform
-    W1 = uniform_ro(a.mlp[0]), B1 = uniform_ro(a.mlp[1]), W2 = uniform_ro(a.mlp[2]), B2 = uniform_ro(a.mlp[3]);
-    W3 = uniform_ro(a.mlp[4]), B3 = uniform_ro(a.mlp[5]);
-  }
+  MlpDev W = {};
+  if (a.sdf_out) W = mlp_dev(a.mlp);  // wave-uniform
   const int rows = opaque(H);
 
   const long long stride = (long long)gridDim.x * 256;
@@ -43,19 +40,15 @@ __global__ __launch_bounds__(256) void k_query_points(QueryArgs a) {
     // all probes first (independent loads), then the gathers
     int slot[L];
 #pragma unroll
-    for (int s = 0; s < L; ++s) {
-      const LevelDev& Lv = a.ls.lv[s];
-      const unsigned long long key = morton3(quantize(x0, Lv.res), quantize(x1, Lv.res), quantize(x2, Lv.res));
-      slot[s] = probe(Lv, key);
-    }
+    for (int s = 0; s < L; ++s) slot[s] = level_slot(a.ls.lv[s], x0, x1, x2);
 #pragma unroll
     for (int s = 0; s < L; ++s) {
-      const LevelDev& Lv = a.ls.lv[s];
       const bool hit = slot[s] >= 0;
       if (s == a.check_slot) mask = hit;
-      const unsigned int sl = hit ? (unsigned int)slot[s] : 0u;
-      const int4 i0 = Lv.vals[2u * sl], i1 = Lv.vals[2u * sl + 1u];
-      const int ids[8] = {i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w};
+      // (one level of k_forward_points' interpolation; a shared helper raised this kernel's SGPR spills at L = 4)
+      const LevelDev& Lv = a.ls.lv[s];
+      int ids[8];
+      corner_ids(Lv.vals, hit ? (unsigned int)slot[s] : 0u, ids);
       const Axis X = axis_weight<POLY>(x0, Lv.res, Lv.dres), Y = axis_weight<POLY>(x1, Lv.res, Lv.dres),
                  Z = axis_weight<POLY>(x2, Lv.res, Lv.dres);
       float w[8];
@@ -80,27 +73,7 @@ __global__ __launch_bounds__(256) void k_query_points(QueryArgs a) {
         f[7] += wz * r1[c].w;
       }
     }
-    if (a.sdf_out) {
-      float h1[H];
-      cfloat *const W1i = relaunder(W1), *const B1i = relaunder(B1);  // keep the loads inside this iteration
-#pragma unroll
-      for (int j = 0; j < H; ++j) {
-        float z = B1i[j];
-#pragma unroll
-        for (int q = 0; q < F; ++q) z = fmaf(W1i[j * F + q], f[q], z);
-        h1[j] = fmaxf(z, 0.f);
-      }
-      float y = B3[0];
-      // layer 2 + 3 as a ROLLED loop over the 32 weight rows (two s_load_dwordx16 each): h2 is consumed as produced
-#pragma clang loop vectorize(disable) interleave(disable) unroll_count(2)
-      for (int j = 0; j < rows; ++j) {
-        float z = B2[j];
-#pragma unroll
-        for (int k = 0; k < H; ++k) z = fmaf(W2[j * H + k], h1[k], z);
-        y = fmaf(W3[j], fmaxf(z, 0.f), y);
-      }
-      a.sdf_out[p] = a.sign * y;
-    }
+    if (a.sdf_out) a.sdf_out[p] = a.sign * sdf_decode(W, f, rows);
     if (a.mask_out) a.mask_out[p] = mask ? 1 : 0;
   }
 }

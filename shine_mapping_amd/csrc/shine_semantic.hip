@@ -131,19 +131,6 @@ __global__ __launch_bounds__(kThreads) void k_sem_fwd(const float* __restrict__ 
   }
 }
 
-// contraction over the wave's 64 staged points: acc[q] += left[p][j] * right[p][rb + q], acc_left += left[p][j]
-template <int NQ>
-__device__ __forceinline__ void sem_contract(const float* st, int j, int rb, float (&acc)[NQ], float& acc_left) {
-#pragma clang loop vectorize(disable) interleave(disable) unroll_count(4)
-  for (int p = 0; p < 64; ++p) {
-    const float* r = st + p * ST;
-    const float l = r[j];
-    acc_left += l;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) acc[q] = fmaf(l, r[rb + q], acc[q]);
-  }
-}
-
 // ---- backward: one wave = one 64-point tile at a time (staging rows [64][ST] per wave, as shine_mlp.hip's k_mlp_bwd)
 __global__ __launch_bounds__(kThreads) void k_sem_bwd(const float* __restrict__ feat, const float* __restrict__ logp,
                                                       const float* __restrict__ dlogp, long long n, SemArgsPtrs p, int C,
@@ -198,7 +185,7 @@ __global__ __launch_bounds__(kThreads) void k_sem_bwd(const float* __restrict__ 
     }
     wave_lds_fence();
     if (wgrad) {  // dWc += dz (x) h2, dbc += dz
-      sem_contract<16>(st, jj, 32 + hi * 16, accWc, accbc);
+      contract64r<16>(st, jj, 32 + hi * 16, accWc, accbc, true);
       wave_lds_fence();
     }
     // dh2 = Wc^T dz; d2 = m2 .* dh2
@@ -218,7 +205,7 @@ SEM_ROW_LOOP(2)
     for (int k = 0; k < H; ++k) row[32 + k] = h1[k];
     wave_lds_fence();
     if (wgrad) {  // dW2 += d2 (x) h1, db2 += d2
-      sem_contract<16>(st, jj, 32 + hi * 16, accW2, accb2);
+      contract64r<16>(st, jj, 32 + hi * 16, accW2, accb2, true);
       wave_lds_fence();
     }
     // dh1 = W2^T d2; d1 = m1 .* dh1
@@ -252,7 +239,7 @@ SEM_ROW_LOOP(8)
       o[1] = make_float4(df[4], df[5], df[6], df[7]);
     }
     if (wgrad) {  // dW1 += d1 (x) f, db1 += d1
-      sem_contract<4>(st, jj, 32 + hi * 4, accW1, accb1);
+      contract64r<4>(st, jj, 32 + hi * 4, accW1, accb1, true);
     }
     wave_lds_fence();
   }
@@ -354,17 +341,13 @@ __global__ __launch_bounds__(kThreads) void k_sem_query(LevelSet ls, const float
     for (int k = 0; k < F; ++k) f[k] = 0.f;
     int slot[L];
 #pragma unroll
-    for (int s = 0; s < L; ++s) {
-      const LevelDev& Lv = ls.lv[s];
-      slot[s] = probe(Lv, morton3(quantize(x0, Lv.res), quantize(x1, Lv.res), quantize(x2, Lv.res)));
-    }
+    for (int s = 0; s < L; ++s) slot[s] = level_slot(ls.lv[s], x0, x1, x2);
 #pragma unroll
     for (int s = 0; s < L; ++s) {
-      const LevelDev& Lv = ls.lv[s];
       const bool hit = slot[s] >= 0;
-      const unsigned int sl = hit ? (unsigned int)slot[s] : 0u;
-      const int4 i0 = Lv.vals[2u * sl], i1 = Lv.vals[2u * sl + 1u];
-      const int ids[8] = {i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w};
+      const LevelDev& Lv = ls.lv[s];
+      int ids[8];
+      corner_ids(Lv.vals, hit ? (unsigned int)slot[s] : 0u, ids);
       const Axis X = axis_weight<POLY>(x0, Lv.res, Lv.dres), Y = axis_weight<POLY>(x1, Lv.res, Lv.dres),
                  Z = axis_weight<POLY>(x2, Lv.res, Lv.dres);
       float wc[8];

@@ -47,14 +47,14 @@ __global__ __launch_bounds__(256) void k_mark_touched(V1Args a) {
       Lv.keys = a.lv[s].keys;
       Lv.shift = a.lv[s].shift;
       Lv.mask = a.lv[s].mask;
-      const float res = a.lv[s].res;
-      sl = probe(Lv, morton3(quantize(x0, res), quantize(x1, res), quantize(x2, res)));
+      Lv.res = a.lv[s].res;
+      sl = level_slot(Lv, x0, x1, x2);
     }
     if (sl < 0) continue;
-    const int4 v0 = a.lv[s].vals[2 * sl], v1 = a.lv[s].vals[2 * sl + 1];
+    int ids[8];
+    corner_ids(a.lv[s].vals, (unsigned int)sl, ids);
     unsigned char* t = a.touched[s];
-    t[v0.x] = 1; t[v0.y] = 1; t[v0.z] = 1; t[v0.w] = 1;
-    t[v1.x] = 1; t[v1.y] = 1; t[v1.z] = 1; t[v1.w] = 1;
+    for (int c = 0; c < 8; ++c) t[ids[c]] = 1;
   }
 }
 
