@@ -24,11 +24,14 @@ draw, and the grads are exchanged (--exchange).
 ranks on 127.0.0.1; fewer than N visible devices is an error, never a silent fall-back to one rank.
 
 OUTPUT (rank 0, stdout).  The LAST line is the driver's record: ONE compact JSON object (< 4 kB; tests/test_bench_launch.py
-holds the formatter to that) with the contract's fields + `roofline` + `cpu_baseline`.  The default invocation (no --workload,
-one GPU) also runs abbreviated legs of BASELINE configs 3 (`kitti`), 4 (`ncd-incre`, Tier B and Tier A), the map beyond the
-Infinity Cache (`kitti-large`) and rank 0's share of config 5 (`kitti-dp8-rank`); each prints its OWN compact line
-(`{"leg": ...}`) BEFORE the record.  The full (un-cut) records go to --full-record-dir (default gpurun_out/bench_records/).
-DESIGN.md §5 explains every field.
+holds the formatter to that) with the contract's fields + `roofline` + `cpu_baseline`.  A plain run does only what its headline
+figure needs: set-up, preheat, the W warm-up and K timed steps, --dump-outputs, the record (`roofline` and `cpu_baseline` null).
+`--full` measures the rest after the timed steps: the record's `roofline`, `cpu_baseline` and `like_for_like`, the iteration
+with fused Adam (batch workloads), Tier A (ncd-incre); and the default invocation (no --workload, one GPU) then also runs
+abbreviated legs of BASELINE configs 3 (`kitti`), 4 (`ncd-incre`, Tier B and Tier A), the map beyond the Infinity Cache
+(`kitti-large`) and rank 0's share of config 5 (`kitti-dp8-rank`); each prints its OWN compact line (`{"leg": ...}`) BEFORE the
+record.  A `--full` run writes the full (un-cut) records to --full-record-dir (default bench_records/).  DESIGN.md §5 explains
+every field.
 
 `--steps K` is the number of timed steps (one window of K steps; `--repeats R` times R windows of K) and `ms_per_step` the
 time one of them took.  `--dump-outputs DIR` (batch workloads) writes what the last timed step of the requested workload
@@ -306,10 +309,15 @@ def main():
     ap.add_argument("--repeats", type=int, default=1,
                     help="timed windows of exactly --steps steps each (R windows time R x K steps); the line reports the median "
                          "window")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-tier-a", action="store_true", help="ncd-incre: skip the Tier A (unchanged driver's loop) measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: roofline, CPU baseline and "
+                         "like-for-like, the iteration with fused Adam, Tier A (ncd-incre) and, for the default invocation, the "
+                         "abbreviated kitti / ncd-incre / kitti-large / kitti-dp8-rank legs; writes the full records")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-tier-a", action="store_true",
+                    help="--full, ncd-incre: skip the Tier A (unchanged driver's loop) measurement")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="default invocation: skip the abbreviated kitti / ncd-incre legs")
+                    help="--full, default invocation: skip the abbreviated kitti / ncd-incre legs")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying HIP graphs")
     ap.add_argument("--draw-rider", default="auto", choices=["auto", "on", "off"],
                     help="one rank: the step's reduction launch also draws the next batch and clears the next step's bucket (a step = "
@@ -332,8 +340,8 @@ def main():
                          "global batch touched (auto: touched when the dense bucket exceeds 64 MB)")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed (RCCL) and run the data-parallel code path even at world size 1")
-    ap.add_argument("--full-record-dir", default=os.path.join(ROOT, "gpurun_out", "bench_records"),
-                    help="where the un-cut record of every leg is written (the printed lines are cut to < 4 kB)")
+    ap.add_argument("--full-record-dir", default=os.path.join(ROOT, "bench_records"),
+                    help="--full: where the un-cut record of every leg is written (the printed lines are cut to < 4 kB)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="batch workloads: after the timed steps write the last step's loss, predictions and gradients as "
                          "DIR/<name>.npy (<= 64 MB in all); the run's inputs are the same from run to run")
@@ -356,24 +364,28 @@ def main():
     if dist is None:
         torch.cuda.set_device(0)
     dev = torch.device("cuda", local_rank if dist is not None else 0)
-    cb = None if args.no_cpu_baseline else cpu_baseline
-    full_dir = args.full_record_dir
+    full = args.full
+    cb = cpu_baseline if full and not args.no_cpu_baseline else None
+
+    def record_path(name, rec):
+        return write_full(args.full_record_dir, name, rec) if full else None
 
     if incre:
         if args.dump_outputs:
             raise SystemExit("--dump-outputs: batch workloads only (not ncd-incre)")
         if world > 1:
             raise SystemExit("ncd-incre is a single-GPU workload (BASELINE.json config 4)")
-        rec = run_incremental(args, dev, args.steps, args.warmup, cpu_baseline=cb)
-        emit(compact(rec, write_full(full_dir, "ncd-incre", rec)))
+        rec = run_incremental(args, dev, args.steps, args.warmup, cpu_baseline=cb, with_roofline=full, with_tier_a=full)
+        emit(compact(rec, record_path("ncd-incre", rec)))
         return
 
     outputs = {} if args.dump_outputs else None
-    rec = run_batch(args, args.workload, dist, world, rank, dev, args.steps, args.warmup, cpu_baseline=cb, outputs=outputs)
+    rec = run_batch(args, args.workload, dist, world, rank, dev, args.steps, args.warmup, cpu_baseline=cb, outputs=outputs,
+                    with_iteration=full, with_roofline=full)
     if outputs:
         written = dump_outputs(args.dump_outputs, outputs)
         print("dumped %d arrays (%d elements) to %s" % (len(written), sum(written.values()), args.dump_outputs), file=sys.stderr)
-    if default_run and world == 1 and not args.no_extra_configs:
+    if full and default_run and world == 1 and not args.no_extra_configs:
         # BASELINE configs 3, 4 and 5's rank share under the same driver clock: abbreviated legs (fewer steps, shorter CPU
         # samples), each printed as its own compact line BEFORE the record.  A failing leg is reported, never allowed to take
         # the headline line down.
@@ -391,14 +403,14 @@ def main():
         for name, leg in legs:
             benchlib._release(dev)
             try:
-                full = leg()
-                line = compact_dp_rank(full) if name == "kitti-dp8-rank" else compact(full)
+                leg_rec = leg()
+                line = compact_dp_rank(leg_rec) if name == "kitti-dp8-rank" else compact(leg_rec)
             except Exception as e:
-                full = line = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
-            path = write_full(full_dir, name, full)
+                leg_rec = line = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
+            path = record_path(name, leg_rec)
             emit({"leg": name, "full_record": path, **(line if isinstance(line, dict) else {"value": line})})
     if rank == 0:
-        emit(compact(rec, write_full(full_dir, args.workload, rec)))
+        emit(compact(rec, record_path(args.workload, rec)))
     if dist is not None:
         dist.destroy_process_group()
 

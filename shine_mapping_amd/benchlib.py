@@ -163,10 +163,11 @@ def gpu_iteration_n4096(wl, spool_seed, iters=300, n=4096, active_rows=True):
                     "launches per iteration, %d iterations per HIP graph" % unroll}
 
 
-def run_incremental(args, dev, steps, warmup, cpu_baseline=None, cpu_seconds=12.0):
+def run_incremental(args, dev, steps, warmup, cpu_baseline=None, cpu_seconds=12.0, with_roofline=True, with_tier_a=True):
     """BASELINE config 4 (shine_incre.py:86-195): per frame {update -> optimiser re-creation -> pool plan -> 50 x
     {sorted draw, fused step (sum reduction, touched rows), regulariser, fused Adam} as ONE replayed HIP graph ->
-    importance sweep}.  A step = one frame.  -> the bench record (dict)."""
+    importance sweep}.  A step = one frame.  -> the bench record (dict).  The measurements after the timed frames (`roofline`,
+    `tier_a`, `cpu_baseline`) are each left out of the record when switched off."""
     import numpy as np
 
     from shine_mapping_amd import Decoder, FeatureOctree, StepOptions, synth
@@ -300,19 +301,21 @@ def run_incremental(args, dev, steps, warmup, cpu_baseline=None, cpu_seconds=12.
         "final_loss": float(loss),
     }
     # roofline of the dominant kernel at this batch size (HIP events around back-to-back launches of the fused kernel)
-    out["roofline"] = kernel_roofline("ncd-incre", octree, dec, cfg, pool, bs, None)
+    if with_roofline:
+        out["roofline"] = kernel_roofline("ncd-incre", octree, dec, cfg, pool, bs, None)
     # the same configuration through the UNCHANGED driver's names (Tier A: shine_incre.py's loop body verbatim on the drop-in's
     # classes, every launch issued by Python; tools/tier_a_bench.py) next to the fused loop above (Tier B)
-    try:
-        if args.no_tier_a:
-            raise RuntimeError("skipped (--no-tier-a)")
-        from tier_a_bench import tier_a_incremental
+    if with_tier_a:
+        try:
+            if args.no_tier_a:
+                raise RuntimeError("skipped (--no-tier-a)")
+            from tier_a_bench import tier_a_incremental
 
-        n_a = min(len(frames), 8)
-        out["tier_a"] = tier_a_incremental(dev, frames[:n_a], bs=bs, iters=iters, warmup=2, levels=cfg.tree_level_feat)
-        out["tier_a"]["vs_tier_b_frames_per_s"] = out["tier_a"]["frames_per_s"] / out["frames_per_s"]
-    except Exception as e:
-        out["tier_a"] = {"error": "%s: %s" % (type(e).__name__, e)}
+            n_a = min(len(frames), 8)
+            out["tier_a"] = tier_a_incremental(dev, frames[:n_a], bs=bs, iters=iters, warmup=2, levels=cfg.tree_level_feat)
+            out["tier_a"]["vs_tier_b_frames_per_s"] = out["tier_a"]["frames_per_s"] / out["frames_per_s"]
+        except Exception as e:
+            out["tier_a"] = {"error": "%s: %s" % (type(e).__name__, e)}
     if cpu_baseline is not None:
         cb = cpu_baseline(wl, n=bs, seconds=cpu_seconds, regularize=True)
         out["cpu_baseline"] = cb
@@ -567,8 +570,9 @@ DUMP_PREHEAT_STEPS = 400  # the preheat of a run whose outputs are kept: a fixed
 
 
 def run_batch(args, workload, dist, world, rank, dev, steps, warmup, cpu_baseline=None, with_like_for_like=True,
-              with_iteration=True, cpu_seconds=12.0, outputs=None):
-    """One batch-mode workload -> the bench record (dict on rank 0, None elsewhere).
+              with_iteration=True, cpu_seconds=12.0, outputs=None, with_roofline=True):
+    """One batch-mode workload -> the bench record (dict on rank 0, None elsewhere).  What it measures after the timed steps —
+    `roofline`, `iteration_with_fused_adam`, `cpu_baseline`, `like_for_like` — is each None or absent when switched off.
 
     `outputs` (a dict, or None): filled on rank 0 with what the last timed step handed its caller, as host tensors — loss,
     per-point prediction, feature and decoder gradients.  Its inputs are then the same from run to run: the pool is planned
@@ -953,7 +957,8 @@ def run_batch(args, workload, dist, world, rank, dev, steps, warmup, cpu_baselin
         if gather_overflow and rank == 0:
             print("WARNING: a rank touched more rows than a gather message holds during the timed steps", file=sys.stderr)
 
-    roof = kernel_roofline(workload, octree, decoder, cfg, spool, points, None, launch_graph=not args.no_graph)
+    roof = (kernel_roofline(workload, octree, decoder, cfg, spool, points, None, launch_graph=not args.no_graph)
+            if with_roofline else None)
 
     # the reference's whole iteration (timing(s)/total, shine_batch.py:225): step + optimiser.  Fused Adam clears the
     # grads in the same pass.  Reported next to `value`, never instead of it.

@@ -125,3 +125,66 @@ def test_the_printed_record_stays_small_and_strict():
         bench.emit(bench.compact(bad))
     ln = buf.getvalue().strip()
     assert len(ln) < bench.RECORD_LIMIT and json.loads(ln)["roofline"]["frac"] is None
+
+
+def _main_with_recorded_legs(monkeypatch, tmp_path, argv):
+    """bench.main() with the measured legs (benchlib.run_batch / run_incremental / run_dp_rank) replaced by recorders, so that
+    what a command line asks for is visible without a GPU -> (the module, [(leg, workload, kwargs)], printed JSON lines)"""
+    import io
+    from contextlib import redirect_stdout
+
+    import torch
+
+    bench = _load_bench()
+    calls = []
+
+    def record(kind):
+        def leg(*a, **kw):
+            workload = a[1] if kind == "run_batch" else kind
+            calls.append((kind, workload, kw))
+            return {"metric": "trained SDF samples/sec (fwd+bwd)", "value": 1.0, "unit": "samples/s", "ms_per_step": 1.0}
+        return leg
+
+    for kind in ("run_batch", "run_incremental", "run_dp_rank"):
+        monkeypatch.setattr(bench, kind, record(kind))
+    monkeypatch.setattr(bench.benchlib, "_release", lambda dev: None)
+    monkeypatch.setattr(torch.cuda, "set_device", lambda dev: None)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full-record-dir", str(tmp_path / "records")] + argv)
+    buf = io.StringIO()
+    with redirect_stdout(buf):
+        bench.main()
+    return bench, calls, [json.loads(ln) for ln in buf.getvalue().splitlines()]
+
+
+def test_a_plain_run_measures_the_headline_alone(monkeypatch, tmp_path):
+    """the driver's plain command line: the requested workload only, nothing measured after its timed steps, one line, no
+    record files"""
+    _, calls, lines = _main_with_recorded_legs(monkeypatch, tmp_path, ["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert [(k, w) for k, w, _ in calls] == [("run_batch", "maicity")]
+    kw = calls[0][2]
+    assert kw["cpu_baseline"] is None and kw["with_iteration"] is False and kw["with_roofline"] is False
+    assert len(lines) == 1 and lines[0]["value"] == 1.0 and "full_record" not in lines[0]
+    assert not (tmp_path / "records").exists()
+    _, calls, lines = _main_with_recorded_legs(monkeypatch, tmp_path, ["--workload", "ncd-incre", "--steps", "4", "--warmup", "1"])
+    assert [(k, w) for k, w, _ in calls] == [("run_incremental", "run_incremental")]
+    kw = calls[0][2]
+    assert kw["cpu_baseline"] is None and kw["with_roofline"] is False and kw["with_tier_a"] is False
+    assert len(lines) == 1 and not (tmp_path / "records").exists()
+
+
+def test_full_runs_every_leg_and_writes_the_records(monkeypatch, tmp_path):
+    bench, calls, lines = _main_with_recorded_legs(monkeypatch, tmp_path, ["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert [(k, w) for k, w, _ in calls] == [("run_batch", "maicity"), ("run_batch", "kitti"),
+                                             ("run_incremental", "run_incremental"), ("run_batch", "kitti-large"),
+                                             ("run_dp_rank", "run_dp_rank")]
+    kw = calls[0][2]
+    assert kw["cpu_baseline"] is bench.cpu_baseline and kw["with_iteration"] is True and kw["with_roofline"] is True
+    assert calls[2][2]["cpu_baseline"] is bench.cpu_baseline and calls[2][2].get("with_roofline", True)
+    assert [ln.get("leg") for ln in lines] == ["kitti", "ncd-incre", "kitti-large", "kitti-dp8-rank", None]
+    assert sorted(os.listdir(tmp_path / "records")) == sorted(
+        "%s.json" % n for n in ("maicity", "kitti", "ncd-incre", "kitti-large", "kitti-dp8-rank"))
+    _, calls, lines = _main_with_recorded_legs(monkeypatch, tmp_path, ["--workload", "ncd-incre", "--full", "--no-cpu-baseline"])
+    kw = calls[0][2]
+    assert len(calls) == 1 and kw["cpu_baseline"] is None and kw["with_roofline"] is True and kw["with_tier_a"] is True

@@ -10,7 +10,7 @@ R=$PWD
 OUT=$R/gpurun_out/prof
 mkdir -p $OUT
 TAG=${W}_${P}_L${L}
-BENCH="python $R/bench.py --workload $W --points $P --levels $L --no-cpu-baseline --no-extra-configs $*"
+BENCH="python $R/bench.py --workload $W --points $P --levels $L --full --no-cpu-baseline --no-extra-configs $*"
 cd /tmp && export TMPDIR=/tmp
 # counters for the fused step only: on the 288 M-sample pool of kitti-large every kernel of the pool plan was otherwise
 # serialised under the counters too (one SQ pass took 11 minutes in round 5's first collection)

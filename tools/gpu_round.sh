@@ -2,8 +2,9 @@
 # The ONE runner of a round's gpurun calls (from the repo root):   gpurun --timeout T -- 'bash tools/gpu_round.sh <stage>...'
 #   suite      python -m pytest tests -m gpu                      -> gpurun_out/round/pytest_gpu.log
 #   smoke      __graft_entry__.smoke()                            -> .../smoke.log
-#   bench      the driver's form (bench.py --gpus 1 --steps 20 --warmup 5): every leg's line + the record, full records
-#   legs       every batch workload alone (maicity, kitti, kitti-large, ncd-incre) with its own cpu_baseline
+#   bench      the driver's form with --full (bench.py --gpus 1 --steps 20 --warmup 5 --full): every leg's line + the record,
+#              full records
+#   legs       every batch workload alone (maicity, kitti, kitti-large, ncd-incre) with --full: its own cpu_baseline
 #   profiles   tools/collect_profiles.sh for maicity / kitti / kitti-large (kernel stats, timelines, PMC -> JSON bench.py reads)
 #   tiera      tools/tier_a_bench.py + tools/tier_a_hostcost.py (Tier A iteration times, statement by statement)
 #   allowance  the trajectory test alone with -s: the allowance it printed -> .../trajectory_allowance.txt
@@ -16,14 +17,14 @@ for stage in "$@"; do
   case $stage in
     suite) ( time timeout 1800 python -m pytest tests -m gpu -q ) > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log ;;
     smoke) timeout 300 python __graft_entry__.py smoke 2>&1 | tail -1 | tee $O/smoke.log ;;
-    bench) ( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full-record-dir $O/bench_records ) \
+    bench) ( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full --full-record-dir $O/bench_records ) \
              > $O/bench_default_driver_form.json.log 2> $O/bench_default_driver_form.err
            tail -4 $O/bench_default_driver_form.err | grep real; wc -c $O/bench_default_driver_form.json.log
            cut -c1-400 $O/bench_default_driver_form.json.log ;;
     legs)  for w in maicity kitti ncd-incre; do
-             timeout 900 python bench.py --workload $w --no-extra-configs --full-record-dir $O/leg_records > $O/bench_$w.json.log 2> $O/bench_$w.err
+             timeout 900 python bench.py --workload $w --full --no-extra-configs --full-record-dir $O/leg_records > $O/bench_$w.json.log 2> $O/bench_$w.err
            done
-           timeout 900 python bench.py --workload kitti-large --no-extra-configs --no-cpu-baseline --full-record-dir $O/leg_records \
+           timeout 900 python bench.py --workload kitti-large --full --no-extra-configs --no-cpu-baseline --full-record-dir $O/leg_records \
              > $O/bench_kitti-large.json.log 2> $O/bench_kitti-large.err
            cat $O/bench_maicity.json.log $O/bench_kitti.json.log $O/bench_kitti-large.json.log $O/bench_ncd-incre.json.log | cut -c1-300 ;;
     profiles) for spec in "maicity 262144 4" "kitti 1048576 3" "kitti-large 1048576 3"; do
