@@ -526,6 +526,29 @@ int shine_query_points(const shine_tables* t, const shine_step_config* cfg, cons
                        const float* const* feats, const int64_t* rows, const float* const* mlp, int32_t check_level,
                        int32_t negate, float* sdf_out, uint8_t* mask_out, void* stream);
 
+/* ---- meshing: Mesher.mc_mesh (utils/mesher.py:200-222, skimage marching cubes), compute_vertex_normals (:283, :353) and
+ *      filter_isolated_vertices (:240-251) on the device (csrc/shine_mc.hip, csrc/shine_mesh.hip; rules in DESIGN.md "Meshing").
+ *      sdf [nx, ny, nz] f32 C order (z fastest); mask [nx, ny, nz] u8 or NULL: cube (x, y, z) is processed iff mask[x, y, z]
+ *      (its lowest corner) is set.  A value is "in" iff > level.  Sizes and ids are int64 on the grid, int32 in the mesh.
+ *      Workspaces follow rocPRIM's convention: workspace == NULL returns the bytes needed in *workspace_bytes.
+ *      _mc_count: classify + scan; counts_out (HOST int64[2]) = {V, F}; one small device-to-host copy, so it synchronises the
+ *        stream.  SHINE_E_INVALID if V or F >= 2^31 (counts_out still holds them).
+ *      _mc_emit: the same grid, level and workspace right after _mc_count: verts_out [V, 3] f32 index units, (x, y, z);
+ *        faces_out [F, 3] int32, right-hand normal towards decreasing values.  Deterministic (no atomic places an output).
+ *      _mesh_vertex_normals: normals_out [V, 3] f64 = normalised sum of the adjacent faces' (v1 - v0) x (v2 - v0), in face
+ *        order (a vertex without faces gets 0).
+ *      _mesh_cluster_filter: clusters of triangles that share an edge (open3d cluster_connected_triangles); faces_out [kept, 3]
+ *        = the triangles of clusters with >= min_tri triangles, in their order; *kept_out (HOST) = their count (synchronises);
+ *        cluster_out [F] int32 (may be NULL) = cluster id, clusters numbered in the order of their first triangle. -------- */
+int shine_mc_count(const float* sdf, const uint8_t* mask, int64_t nx, int64_t ny, int64_t nz, float level, void* workspace,
+                   size_t* workspace_bytes, int64_t* counts_out, void* stream);
+int shine_mc_emit(const float* sdf, const uint8_t* mask, int64_t nx, int64_t ny, int64_t nz, float level, void* workspace,
+                  size_t workspace_bytes, float* verts_out, int32_t* faces_out, void* stream);
+int shine_mesh_vertex_normals(const double* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, void* workspace,
+                              size_t* workspace_bytes, double* normals_out, void* stream);
+int shine_mesh_cluster_filter(const int32_t* faces, int64_t n_faces, int32_t min_tri, void* workspace, size_t* workspace_bytes,
+                              int32_t* cluster_out, int32_t* faces_out, int64_t* kept_out, void* stream);
+
 /* ---- graph-replayable forms of the two calls whose per-iteration scalars are otherwise baked into a captured HIP
  *      graph: the scalars live in device memory and the kernels advance them, so ONE captured iteration
  *      {draw, shine_train_step, [shine_regularize], Adam} can be replayed for every iteration of a frame.

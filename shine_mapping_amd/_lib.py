@@ -180,6 +180,13 @@ _SIGNATURES = {
     "shine_sem_backward": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(_P), C.c_int32, _P, C.POINTER(_P), _P, _P]),
     "shine_sem_query_labels": (C.c_int, [_P, C.POINTER(StepConfig), _P, C.c_int64, C.POINTER(_P), C.POINTER(C.c_int64),
                                          C.POINTER(_P), C.c_int32, _P, _P]),
+    # meshing (csrc/shine_mc.hip, csrc/shine_mesh.hip)
+    "shine_mc_count": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_float, _P, C.POINTER(C.c_size_t),
+                                 C.POINTER(C.c_int64), _P]),
+    "shine_mc_emit": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_float, _P, C.c_size_t, _P, _P, _P]),
+    "shine_mesh_vertex_normals": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.POINTER(C.c_size_t), _P, _P]),
+    "shine_mesh_cluster_filter": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.POINTER(C.c_size_t), _P, _P, C.POINTER(C.c_int64),
+                                            _P]),
     "shine_iter_graph_create": (C.c_int, [C.c_int32, C.POINTER(_P)]),
     "shine_iter_graph_destroy": (C.c_int, [_P]),
     "shine_iter_graph_commit": (C.c_int, [_P]),

@@ -1,11 +1,17 @@
-"""Forward-only SDF query for meshing — the hot half of the reference's Mesher (utils/mesher.py:33-108).
+"""The reference's Mesher (utils/mesher.py) on the device: the SDF query, marching cubes, vertex normals, the small-cluster
+filter and the PLY output.
 
 `query_points` keeps the reference's argument list and return convention (numpy arrays; `sdf_pred` is the NEGATED
 decoder output, `mc_mask` says whether the point's node exists at the marching-cubes check level) but runs each
 chunk as ONE launch of `shine_query_points` (csrc/shine_query.hip): no `[N,8]` index tensors, no `[N,F]` features
 and no per-level host round trips.  With `query_sem` the semantic labels are ONE more launch per chunk
-(`shine_sem_query_labels`, csrc/shine_semantic.hip: interpolation, semantic decoder, argmax).  Marching cubes itself (skimage, utils/mesher.py:262-292) and the open3d
-bounding-box plumbing stay with the caller: they are outside the hot path.
+(`shine_sem_query_labels`, csrc/shine_semantic.hip: interpolation, semantic decoder, argmax).
+
+`recon_bbx_mesh` / `recon_octree_mesh` / `mc_mesh` keep the reference's surface but never leave the device until the final
+arrays: the query writes straight into a dense device grid, `marching_cubes` (csrc/shine_mc.hip) replaces skimage's, and
+`compute_vertex_normals` / `filter_isolated_vertices` are csrc/shine_mesh.hip.  The rules the marching cubes follows (corner
+sign, vertex placement, degenerate faces, winding, output order) are in DESIGN.md "Meshing".  The mesh comes back as an
+open3d TriangleMesh when open3d can be imported, else as this module's `TriangleMesh`; the PLY writer is plain numpy.
 """
 from __future__ import annotations
 
@@ -62,8 +68,206 @@ def query_labels_device(octree, sem_decoder, coord):
     return label
 
 
+# ---------------------------------------------------------------------------------------------------------------- meshing
+MC_POINT_BYTES = 4 + 4 + 1  # per grid point: the fp32 grid, the vertex-id base and the packed classify byte (csrc/shine_mc.hip)
+QUERY_CHUNK = 1 << 22  # grid points per query launch when a grid is filled (the values do not depend on it)
+
+
+def dense_grid_bytes(shape, with_mask=True, per_point_extra=0):
+    """Device bytes a dense marching-cubes grid of `shape` takes: the grid, the optional mask and marching cubes' workspace, plus
+    `per_point_extra` bytes per point the caller holds at the same time (e.g. query coordinates)."""
+    n = int(np.prod([int(v) for v in shape], dtype=np.int64))
+    return n * (MC_POINT_BYTES + (1 if with_mask else 0) + int(per_point_extra)) + (n // 1024 + 1) * 16 + (1 << 20)
+
+
+def ensure_grid_fits(shape, with_mask=True, per_point_extra=0, free_bytes=None, device=None):
+    """Raise MemoryError naming the grid when dense_grid_bytes(...) exceeds the free device memory (or `free_bytes`)."""
+    need = dense_grid_bytes(shape, with_mask, per_point_extra)
+    if free_bytes is None:
+        free_bytes = torch.cuda.mem_get_info(device)[0]
+    if need > free_bytes:
+        raise MemoryError("marching cubes on a %s grid needs about %.2f GB of device memory, %.2f GB are free: use a coarser "
+                          "mc_res_m or a smaller box" % ("x".join(str(int(v)) for v in shape), need / 1e9, free_bytes / 1e9))
+    return need
+
+
+def _ws(nbytes, device):
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
+def marching_cubes(sdf, mask=None, level=0.0):
+    """Marching cubes of a device grid `sdf [X,Y,Z]` (f32, C order) with an optional mask of the same shape (cube (x,y,z) is
+    processed iff mask[x,y,z]); rules in DESIGN.md "Meshing".  Returns (verts [V,3] f32 index units (x, y, z), faces [F,3]
+    int32) on the device; an empty surface gives zero rows."""
+    if sdf.dim() != 3 or not sdf.is_cuda:
+        raise ValueError("marching_cubes: sdf must be a 3-D CUDA tensor, got %s on %s" % (tuple(sdf.shape), sdf.device))
+    sdf = sdf.detach().float().contiguous()
+    if mask is not None:
+        if tuple(mask.shape) != tuple(sdf.shape):
+            raise ValueError("marching_cubes: mask shape %s != sdf shape %s" % (tuple(mask.shape), tuple(sdf.shape)))
+        mask = mask.detach().to(device=sdf.device, dtype=torch.uint8).contiguous()
+    X, Y, Z = (int(v) for v in sdf.shape)
+    lib, st = _lib.lib(), _stream()
+    mp = mask.data_ptr() if mask is not None else None
+    need = C.c_size_t(0)
+    _lib.check(lib.shine_mc_count(sdf.data_ptr(), mp, X, Y, Z, float(level), None, C.byref(need), None, st), "shine_mc_count")
+    ws = _ws(need.value, sdf.device)
+    counts = (C.c_int64 * 2)()
+    rc = lib.shine_mc_count(sdf.data_ptr(), mp, X, Y, Z, float(level), ws.data_ptr(), C.byref(need), counts, st)
+    _lib.check(rc, "shine_mc_count (%dx%dx%d grid: %d vertices, %d faces)" % (X, Y, Z, counts[0], counts[1]))
+    nv, nf = int(counts[0]), int(counts[1])
+    verts = torch.empty((nv, 3), dtype=torch.float32, device=sdf.device)
+    faces = torch.empty((nf, 3), dtype=torch.int32, device=sdf.device)
+    if nv or nf:
+        _lib.check(lib.shine_mc_emit(sdf.data_ptr(), mp, X, Y, Z, float(level), ws.data_ptr(), need.value, verts.data_ptr(),
+                                     faces.data_ptr(), st), "shine_mc_emit")
+    return verts, faces
+
+
+def vertex_normals_device(verts, faces):
+    """open3d's compute_vertex_normals on device arrays: verts [V,3] f64, faces [F,3] int32 -> normals [V,3] f64."""
+    verts = verts.detach().double().contiguous()
+    faces = faces.detach().to(torch.int32).contiguous()
+    nv, nf = verts.shape[0], faces.shape[0]
+    out = torch.zeros((nv, 3), dtype=torch.float64, device=verts.device)
+    lib, st = _lib.lib(), _stream()
+    need = C.c_size_t(0)
+    _lib.check(lib.shine_mesh_vertex_normals(None, nv, None, nf, None, C.byref(need), None, st), "shine_mesh_vertex_normals")
+    if nv == 0:
+        return out
+    ws = _ws(need.value, verts.device)
+    _lib.check(lib.shine_mesh_vertex_normals(verts.data_ptr(), nv, faces.data_ptr() if nf else None, nf, ws.data_ptr(),
+                                             C.byref(need), out.data_ptr(), st), "shine_mesh_vertex_normals")
+    return out
+
+
+def cluster_filter_device(faces, min_tri, return_clusters=False):
+    """Mesher.filter_isolated_vertices on device faces [F,3] int32: drop the triangles of edge-connected clusters with fewer
+    than `min_tri` triangles (order kept).  With return_clusters, also the cluster id of every input triangle (open3d's
+    numbering: clusters in the order of their first triangle)."""
+    faces = faces.detach().to(torch.int32).contiguous()
+    nf = faces.shape[0]
+    lib, st = _lib.lib(), _stream()
+    need = C.c_size_t(0)
+    _lib.check(lib.shine_mesh_cluster_filter(None, nf, int(min_tri), None, C.byref(need), None, None, None, st),
+               "shine_mesh_cluster_filter")
+    out = torch.empty((nf, 3), dtype=torch.int32, device=faces.device)
+    clusters = torch.empty(nf, dtype=torch.int32, device=faces.device) if return_clusters else None
+    kept = C.c_int64(0)
+    if nf:
+        ws = _ws(need.value, faces.device)
+        _lib.check(lib.shine_mesh_cluster_filter(faces.data_ptr(), nf, int(min_tri), ws.data_ptr(), C.byref(need),
+                                                 clusters.data_ptr() if clusters is not None else None, out.data_ptr(),
+                                                 C.byref(kept), st), "shine_mesh_cluster_filter")
+    out = out[:kept.value]
+    return (out, clusters) if return_clusters else out
+
+
+def remove_vertices_device(verts, faces, drop, *vertex_attrs):
+    """open3d's remove_vertices_by_mask on device arrays: drop the vertices where `drop`, every triangle that uses one, and
+    reindex the rest (torch index ops)."""
+    keep = ~drop.bool()
+    new_id = torch.cumsum(keep.to(torch.int64), 0) - 1
+    f = faces.long()
+    fk = keep[f].all(1)
+    return (verts[keep], new_id[f[fk]].to(torch.int32)) + tuple(a[keep] if a is not None else None for a in vertex_attrs)
+
+
+def write_ply(path, vertex_props, faces=None):
+    """Binary little-endian PLY in plain numpy.  vertex_props: [(name, 1-D array, ply type)], ply type one of double / float /
+    int / uchar; faces [F,3] (written as a uchar count + int indices)."""
+    types = {"double": "<f8", "float": "<f4", "int": "<i4", "uchar": "u1"}
+    n = len(vertex_props[0][1]) if vertex_props else 0
+    rec = np.empty(n, dtype=[(name, types[t]) for name, _, t in vertex_props])
+    for name, arr, _ in vertex_props:
+        rec[name] = np.asarray(arr).reshape(-1)
+    head = ["ply", "format binary_little_endian 1.0", "element vertex %d" % n]
+    head += ["property %s %s" % (t, name) for name, _, t in vertex_props]
+    if faces is not None:
+        faces = np.asarray(faces).reshape(-1, 3)
+        head += ["element face %d" % len(faces), "property list uchar int vertex_indices"]
+    head.append("end_header")
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(head) + "\n").encode())
+        fh.write(rec.tobytes())
+        if faces is not None:
+            fr = np.empty(len(faces), dtype=[("n", "u1"), ("i", "<i4", 3)])
+            fr["n"] = 3
+            fr["i"] = faces
+            fh.write(fr.tobytes())
+
+
+class TriangleMesh:
+    """The part of open3d's TriangleMesh the drivers use, for when open3d cannot be imported: numpy arrays and transform()."""
+
+    def __init__(self, vertices, triangles, vertex_normals=None, vertex_colors=None):
+        self.vertices = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+        self.triangles = np.asarray(triangles, dtype=np.int32).reshape(-1, 3)
+        self.vertex_normals = np.zeros((0, 3)) if vertex_normals is None else np.asarray(vertex_normals, np.float64)
+        self.vertex_colors = np.zeros((0, 3)) if vertex_colors is None else np.asarray(vertex_colors, np.float64)
+        self.vertex_labels = None
+
+    def has_vertex_normals(self):
+        return len(self.vertex_normals) > 0
+
+    def has_vertex_colors(self):
+        return len(self.vertex_colors) > 0
+
+    def transform(self, T):
+        """open3d's TriangleMesh.transform: points through the homogeneous 4x4, normals through its linear part."""
+        T = np.asarray(T, dtype=np.float64)
+        if len(self.vertices):
+            h = self.vertices @ T[:3, :3].T + T[:3, 3]
+            w = self.vertices @ T[3, :3] + T[3, 3]
+            self.vertices = h / w[:, None]
+        if self.has_vertex_normals():
+            self.vertex_normals = self.vertex_normals @ T[:3, :3].T
+        return self
+
+
+def _open3d():
+    try:
+        import open3d as o3d  # noqa: F401
+
+        return o3d
+    except Exception:
+        return None
+
+
+def _sem_color_map():
+    try:
+        from utils.semantic_kitti_utils import sem_kitti_color_map
+
+        return sem_kitti_color_map
+    except Exception:
+        return None
+
+
+def _make_mesh(verts, faces, normals=None, colors=None):
+    o3d = _open3d()
+    if o3d is None:
+        return TriangleMesh(verts, faces, normals, colors)
+    m = o3d.geometry.TriangleMesh(o3d.utility.Vector3dVector(np.asarray(verts, np.float64)),
+                                  o3d.utility.Vector3iVector(np.asarray(faces, np.int32)))
+    if normals is not None:
+        m.vertex_normals = o3d.utility.Vector3dVector(normals)
+    if colors is not None:
+        m.vertex_colors = o3d.utility.Vector3dVector(colors)
+    return m
+
+
+def _transform_device(verts, normals, T):
+    T = torch.as_tensor(np.asarray(T, dtype=np.float64), device=verts.device)
+    h = verts @ T[:3, :3].T + T[:3, 3]
+    w = verts @ T[3, :3] + T[3, 3]
+    verts = h / w[:, None]
+    if normals is not None:
+        normals = normals @ T[:3, :3].T
+    return verts, normals
+
+
 class Mesher:
-    """The query half of utils/mesher.py's Mesher: same constructor arguments, same `query_points`."""
+    """utils/mesher.py's Mesher: same constructor arguments, same methods and defaults."""
 
     def __init__(self, config, octree, geo_decoder, sem_decoder=None):
         self.config = config
@@ -132,3 +336,220 @@ class Mesher:
                 sem_pred = query_labels_device(self.octree, self.sem_decoder, coord.to(dev)).cpu().numpy() if query_sem else None
                 mc_mask = mask.cpu().numpy() if query_mask else None
         return sdf_pred, sem_pred, mc_mask
+
+    # ------------------------------------------------------------------------------------------------ utils/mesher.py:153-367
+    def generate_sdf_map(self, coord, sdf_pred, mc_mask, map_path):
+        """utils/mesher.py:153-175: the query grid as a point cloud (world metres), the SDF in metres as `intensities`, the mask
+        as `labels`, after global_transform; written as binary PLY."""
+        # (coord /= world_scale in the reference: float32)
+        pts = (coord.detach() / self.world_scale).cpu().numpy().astype(np.float64) if torch.is_tensor(coord) else \
+            (np.asarray(coord, np.float32) / np.float32(self.world_scale)).astype(np.float64)
+        sdf_world = np.asarray(sdf_pred, np.float64) * self.config.logistic_gaussian_ratio * self.config.sigma_sigmoid_m
+        T = np.asarray(self.global_transform, np.float64)
+        pts = pts @ T[:3, :3].T + T[:3, 3]
+        props = [("x", pts[:, 0], "float"), ("y", pts[:, 1], "float"), ("z", pts[:, 2], "float"),
+                 ("intensities", sdf_world, "float")]
+        if mc_mask is not None:
+            props.append(("labels", np.asarray(mc_mask).astype(np.int32), "int"))
+        write_ply(map_path, props)
+        print("save the sdf map to %s" % (map_path))
+
+    def assign_to_bbx(self, sdf_pred, sem_pred, mc_mask, voxel_num_xyz):
+        """utils/mesher.py:177-198: the flat query results as [X,Y,Z] grids (numpy or device tensors alike)."""
+        shape = tuple(int(v) for v in voxel_num_xyz)
+        if sdf_pred is not None:
+            sdf_pred = sdf_pred.reshape(shape)
+        if sem_pred is not None:
+            sem_pred = sem_pred.reshape(shape)
+        if mc_mask is not None:
+            mc_mask = mc_mask.reshape(shape).bool() if torch.is_tensor(mc_mask) else mc_mask.reshape(shape).astype(dtype=bool)
+        return sdf_pred, sem_pred, mc_mask
+
+    def mc_mesh(self, mc_sdf, mc_mask, voxel_size, mc_origin):
+        """utils/mesher.py:200-222 with marching_cubes (csrc/shine_mc.hip) at level 0 in place of skimage's: numpy or device
+        grids in, (verts = mc_origin + verts * voxel_size float64 numpy, faces int32 numpy) out; an empty surface gives empty
+        arrays."""
+        verts, faces = self._mc_device(mc_sdf, mc_mask)
+        verts = np.asarray(mc_origin, np.float64) + verts.double().cpu().numpy() * voxel_size
+        return verts, faces.cpu().numpy()
+
+    def _mc_device(self, mc_sdf, mc_mask):
+        dev = self.octree.hier_features[0].device if len(self.octree.hier_features) else torch.device("cuda")
+        sdf = torch.as_tensor(np.asarray(mc_sdf, np.float32) if not torch.is_tensor(mc_sdf) else mc_sdf).to(dev, torch.float32)
+        mask = None
+        if mc_mask is not None:
+            mask = torch.as_tensor(np.asarray(mc_mask, bool) if not torch.is_tensor(mc_mask) else mc_mask).to(dev)
+        return marching_cubes(sdf, mask, 0.0)
+
+    def estimate_vertices_sem(self, mesh, verts, filter_free_space_vertices=True):
+        """utils/mesher.py:224-238: vertex labels (shine_sem_query_labels), colours when the reference's colour map can be
+        imported, then the free-space vertices (label <= 0) removed with their triangles."""
+        dev = self.octree.hier_features[0].device
+        v = torch.as_tensor(np.asarray(verts, np.float64), device=dev)
+        f = torch.as_tensor(np.asarray(mesh.triangles, np.int32), device=dev)
+        v, f, labels, colors = self._sem_device(v, f, filter_free_space_vertices)
+        out = _make_mesh(v.cpu().numpy(), f.cpu().numpy(), None, colors.cpu().numpy() if colors is not None else None)
+        if isinstance(out, TriangleMesh):
+            out.vertex_labels = labels.cpu().numpy()
+        return out
+
+    def _sem_device(self, verts, faces, filter_free_space_vertices):
+        labels = query_labels_device(self.octree, self.sem_decoder, (verts * self.world_scale).float())
+        cmap = _sem_color_map()
+        colors = None
+        if cmap is not None:
+            lut = np.zeros((max(int(k) for k in cmap) + 1, 3), np.float64)
+            for k, c in cmap.items():
+                lut[int(k)] = np.asarray(c, np.float64) / 255.0
+            colors = torch.as_tensor(lut, device=verts.device)[labels]
+        if filter_free_space_vertices:
+            verts, faces, labels, colors = remove_vertices_device(verts, faces, labels <= 0, labels, colors)
+        return verts, faces, labels, colors
+
+    def filter_isolated_vertices(self, mesh, filter_cluster_min_tri=300):
+        """utils/mesher.py:240-251: drop the triangles of edge-connected clusters with fewer than filter_cluster_min_tri
+        triangles (shine_mesh_cluster_filter); vertices are kept."""
+        dev = self.octree.hier_features[0].device
+        f = torch.as_tensor(np.asarray(mesh.triangles, np.int32), device=dev)
+        kept = cluster_filter_device(f, filter_cluster_min_tri).cpu().numpy()
+        o3d = _open3d()
+        mesh.triangles = o3d.utility.Vector3iVector(kept) if o3d is not None and not isinstance(mesh, TriangleMesh) else kept
+        return mesh
+
+    def _finish(self, verts, faces, voxel_size, origin, mesh_path, estimate_sem, estimate_normal, filter_isolated_mesh,
+                filter_free_space_vertices, min_tri):
+        """the tail of recon_bbx_mesh / recon_octree_mesh (utils/mesher.py:270-292, :344-367) on device arrays: world
+        coordinates, [semantics], [normals], [cluster filter], global_transform, PLY."""
+        dev = verts.device
+        v = torch.as_tensor(np.asarray(origin, np.float64), device=dev) + verts.double() * float(voxel_size)
+        f = faces
+        labels = colors = normals = None
+        if estimate_sem:
+            v, f, labels, colors = self._sem_device(v, f, filter_free_space_vertices)
+        if estimate_normal:
+            normals = vertex_normals_device(v, f)
+        if filter_isolated_mesh:
+            f = cluster_filter_device(f, min_tri)
+        v, normals = _transform_device(v, normals, self.global_transform)
+        vn, fn = v.cpu().numpy(), f.cpu().numpy()
+        nn = normals.cpu().numpy() if normals is not None else None
+        cn = colors.cpu().numpy() if colors is not None else None
+        props = [("x", vn[:, 0], "double"), ("y", vn[:, 1], "double"), ("z", vn[:, 2], "double")]
+        if nn is not None:
+            props += [("nx", nn[:, 0], "double"), ("ny", nn[:, 1], "double"), ("nz", nn[:, 2], "double")]
+        if cn is not None:
+            rgb = np.clip(np.round(cn * 255.0), 0, 255).astype(np.uint8)
+            props += [("red", rgb[:, 0], "uchar"), ("green", rgb[:, 1], "uchar"), ("blue", rgb[:, 2], "uchar")]
+        write_ply(mesh_path, props, fn)
+        print("save the mesh to %s\n" % (mesh_path))
+        mesh = _make_mesh(vn, fn, nn, cn)
+        if isinstance(mesh, TriangleMesh) and labels is not None:
+            mesh.vertex_labels = labels.cpu().numpy()
+        return mesh
+
+    def _fill_grid(self, coord, shape, check_level, query_mask):
+        """query_points_device over `coord` in chunks, straight into a device sdf grid and mask grid"""
+        n = coord.shape[0]
+        dev = self.octree.hier_features[0].device
+        sdf = torch.empty(n, dtype=torch.float32, device=dev)
+        mask = torch.empty(n, dtype=torch.bool, device=dev) if query_mask else None
+        with torch.no_grad():
+            for head in range(0, n, QUERY_CHUNK):
+                tail = min(head + QUERY_CHUNK, n)
+                s, m = query_points_device(self.octree, self.geo_decoder, coord[head:tail].to(dev), check_level, True, True,
+                                           query_mask)
+                sdf[head:tail] = s
+                if query_mask:
+                    mask[head:tail] = m
+        return sdf.view(shape), (mask.view(shape) if mask is not None else None)
+
+    def _check_level(self):
+        return min(self.octree.featured_level_num, self.config.mc_vis_level) - 1
+
+    def recon_bbx_mesh(self, bbx, voxel_size, mesh_path, map_path, save_map=False, estimate_sem=False, estimate_normal=True,
+                       filter_isolated_mesh=True, filter_free_space_vertices=True):
+        """utils/mesher.py:253-292 on the device: grid query -> marching cubes -> [semantics] -> [normals] -> [filter with
+        config.min_cluster_vertices] -> global_transform -> PLY."""
+        if getattr(self.config, "time_conditioned", False):
+            raise NotImplementedError("time-conditioned decoding is outside the SDF hot path")
+        min_bound = np.asarray(bbx.get_min_bound(), dtype=np.float64)
+        max_bound = np.asarray(bbx.get_max_bound(), dtype=np.float64)
+        shape = (np.ceil((max_bound - min_bound) / voxel_size) + self.config.pad_voxel * 2).astype(np.int_)
+        shape[2] += 1
+        mask_on = bool(getattr(self.config, "mc_mask_on", True))
+        ensure_grid_fits(shape, mask_on, per_point_extra=12 + 6, device=self.octree.hier_features[0].device)  # (+ the query
+        #                                                                            coordinates and get_query_from_bbx's int16 axes)
+        coord, voxel_num_xyz, voxel_origin = self.get_query_from_bbx(bbx, voxel_size)
+        sdf, mask = self._fill_grid(coord, tuple(int(v) for v in voxel_num_xyz), self._check_level(), mask_on)
+        if save_map:
+            self.generate_sdf_map(coord, sdf.reshape(-1).cpu().numpy(),
+                                  mask.reshape(-1).cpu().numpy() if mask is not None else None, map_path)
+        del coord
+        verts, faces = marching_cubes(sdf, mask, 0.0)
+        del sdf, mask
+        return self._finish(verts, faces, voxel_size, voxel_origin, mesh_path, estimate_sem, estimate_normal,
+                            filter_isolated_mesh, filter_free_space_vertices, getattr(self.config, "min_cluster_vertices", 300))
+
+    def octree_grid_layout(self, query_level, mc_res_m):
+        """utils/mesher.py:297-321's arithmetic (numpy, the reference's op order): (node centres [M,3] scaled, node_res_scaled,
+        voxels per node side k, mc_res_scaled, grid shape [3], shift_coord [M,3] = each node block's offset in the grid)."""
+        nodes = self.octree.get_octree_nodes(query_level)
+        if len(nodes) == 0:
+            raise ValueError("recon_octree_mesh: the octree has no node at level %d" % query_level)
+        min_nodes = np.min(nodes, 0)
+        max_nodes = np.max(nodes, 0)
+        node_res_scaled = 2 ** (1 - query_level)
+        k = int(np.ceil(node_res_scaled / self.world_scale / mc_res_m).astype(dtype=int))
+        mc_res_scaled = node_res_scaled / k
+        shape = ((max_nodes - min_nodes) / mc_res_scaled + k).astype(int)
+        shift = ((nodes - min_nodes) / node_res_scaled * k).astype(int)
+        return nodes, node_res_scaled, k, mc_res_scaled, shape, shift
+
+    def octree_grid_device(self, query_level, mc_res_m):
+        """recon_octree_mesh's dense grid, assembled on the device: every node block of get_octree_nodes(query_level) queried at
+        once (per chunk of nodes) and scattered to its shift_coord offset, instead of one query per node (utils/mesher.py:326-337).
+        Unfilled cells stay 0 with the mask off.  The reference keeps the grid as float16 (:323); the values are rounded the same
+        way (.half().float()) so the meshes agree.  Returns (sdf [X,Y,Z] f32, mask [X,Y,Z] bool, voxel size m, origin m)."""
+        nodes, node_res_scaled, k, mc_res_scaled, shape, shift = self.octree_grid_layout(query_level, mc_res_m)
+        dev = self.octree.hier_features[0].device
+        ensure_grid_fits(shape, True, device=dev)
+        X, Y, Z = (int(v) for v in shape)
+        # the reference's node block: int16 grid coordinates, float32, times mc_res_scaled (:304-313)
+        ax = torch.arange(k, dtype=torch.int16, device=dev)
+        gx, gy, gz = torch.meshgrid(ax, ax, ax, indexing="ij")
+        block = torch.stack((gx.flatten(), gy.flatten(), gz.flatten())).transpose(0, 1).float()
+        block *= mc_res_scaled
+        block64 = block.double()
+        lin_block = ((gx.flatten().long() * Y + gy.flatten().long()) * Z + gz.flatten().long())
+        origins = torch.as_tensor(nodes - 0.5 * (node_res_scaled - mc_res_scaled), dtype=torch.float64, device=dev)
+        base = torch.as_tensor((shift[:, 0].astype(np.int64) * Y + shift[:, 1]) * Z + shift[:, 2], device=dev)
+        sdf = torch.zeros(X * Y * Z, dtype=torch.float32, device=dev)
+        mask = torch.zeros(X * Y * Z, dtype=torch.bool, device=dev)
+        mask_on = bool(getattr(self.config, "mc_mask_on", True))
+        check_level = self._check_level()
+        per = max(1, QUERY_CHUNK // (k ** 3))
+        with torch.no_grad():
+            for h in range(0, len(nodes), per):
+                t = min(h + per, len(nodes))
+                # cur_coord += cur_origin (:329-330): a float32 tensor plus a float64 one, computed in double, stored as float32
+                coord = (block64[None] + origins[h:t, None, :]).float().reshape(-1, 3)
+                s, m = query_points_device(self.octree, self.geo_decoder, coord, check_level, True, True, mask_on)
+                idx = (base[h:t, None] + lin_block[None]).reshape(-1)
+                sdf[idx] = s.half().float()
+                if mask_on:  # (without the mask the reference assigns None, i.e. False, to its bool grid: :336)
+                    mask[idx] = m
+        voxel = mc_res_scaled / self.world_scale
+        origin = (np.min(nodes, 0) - 0.5 * (node_res_scaled - mc_res_scaled)) / self.world_scale
+        return sdf.view(X, Y, Z), mask.view(X, Y, Z), voxel, origin
+
+    def recon_octree_mesh(self, query_level, mc_res_m, mesh_path, map_path, save_map=False, estimate_sem=False,
+                          estimate_normal=True, filter_isolated_mesh=True, filter_free_space_vertices=True):
+        """utils/mesher.py:294-367 on the device (the reference's save_map is commented out there, :342-344, and ignored here
+        too; its cluster filter uses the default 300 triangles, :356)."""
+        if getattr(self.config, "time_conditioned", False):
+            raise NotImplementedError("time-conditioned decoding is outside the SDF hot path")
+        sdf, mask, voxel, origin = self.octree_grid_device(query_level, mc_res_m)
+        verts, faces = marching_cubes(sdf, mask, 0.0)
+        del sdf, mask
+        return self._finish(verts, faces, voxel, origin, mesh_path, estimate_sem, estimate_normal, filter_isolated_mesh,
+                            filter_free_space_vertices, 300)
