@@ -549,6 +549,49 @@ int shine_mesh_vertex_normals(const double* verts, int64_t n_verts, const int32_
 int shine_mesh_cluster_filter(const int32_t* faces, int64_t n_faces, int32_t min_tri, void* workspace, size_t* workspace_bytes,
                               int32_t* cluster_out, int32_t* faces_out, int64_t* kept_out, void* stream);
 
+/* ---- mesh evaluation: eval/eval_utils.py (eval_mesh, nn_correspondance, crop_intersection) on the device
+ *      (csrc/shine_eval.hip; layout and rules in DESIGN.md 3.10).  All geometry is fp64; counts are int64 and < 2^31.
+ *      Workspaces follow rocPRIM's convention: workspace == NULL returns the bytes needed in *workspace_bytes.
+ *      _fine_per_coarse: fine cells per coarse cell edge of the search grid (a compile-time constant of the library).
+ *      _bounds: bounds_out (DEVICE double[6]) = per-axis minimum then maximum of points [n, 3], n > 0.
+ *      _box_mask: drop_out [n] u8 = 0 where min_bound <= p <= max_bound on every axis (HOST double[3] each), else 1.
+ *      _sample_mesh: points_out [n, 3] = uniform samples of the mesh, tri_out [n] (may be NULL) their triangles.  Sample i
+ *        takes (u0, u1, u2) from uniforms [n, 3] or, if NULL, from a counter-based generator of (seed, i): the triangle is
+ *        the first whose cumulative area share is > u0, the point (1 - sqrt u1) v0 + sqrt u1 (1 - u2) v1 + sqrt u1 u2 v2.
+ *        Synchronises the stream (the total area is checked on the host).
+ *      _voxel_down: one point per occupied voxel = the mean of its points, ascending key (ix << 42 | iy << 21 | iz) with
+ *        i = floor((p - origin) / voxel) (HOST origin[3]; the caller guarantees 0 <= i < 2^21).  points_out / keys_out (may be
+ *        NULL) have room for n rows; *n_out (HOST) = rows written (synchronises).  Bit-identical from run to run.
+ *      _grid_count: sorts the reference points by cell (edge `cell`, HOST origin[3], indices < 2^21 guaranteed by the caller);
+ *        counts_out (HOST int64[2]) = {occupied fine cells, occupied coarse cells} (synchronises).
+ *      _grid_emit: right after _grid_count with its workspace: writes the search grid into `grid` (grid == NULL: its size).
+ *      _nn_search: for each query the nearest reference point with squared distance < truncation^2: index_out [n_query]
+ *        (the caller's reference index, -1 if there is none), dist_out (the fp64 distance, or `truncation`), keep_out (1 / 0),
+ *        in the caller's query order.  cells_per_axis (HOST int64[3]) = fine cells that cover the reference set per axis.
+ *        stats_out (DEVICE int32[2], may be NULL) = the largest number of coarse cells probed / fine cells tested by one query.
+ *      _metrics: ONE launch; sums_out (DEVICE double[8]) = sum, sum of squares and count(< threshold) of dist_p, the same of
+ *        dist_r, n_p, n_r. -------- */
+int shine_eval_fine_per_coarse(void);
+int shine_eval_bounds(const double* points, int64_t n, void* workspace, size_t* workspace_bytes, double* bounds_out,
+                      void* stream);
+int shine_eval_box_mask(const double* points, int64_t n, const double* min_bound, const double* max_bound, uint8_t* drop_out,
+                        void* stream);
+int shine_eval_sample_mesh(const double* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, int64_t n, uint64_t seed,
+                           const double* uniforms, void* workspace, size_t* workspace_bytes, double* points_out,
+                           int32_t* tri_out, void* stream);
+int shine_eval_voxel_down(const double* points, int64_t n, const double* origin, double voxel, void* workspace,
+                          size_t* workspace_bytes, double* points_out, uint64_t* keys_out, int64_t* n_out, void* stream);
+int shine_eval_grid_count(const double* ref, int64_t n, const double* origin, double cell, void* workspace,
+                          size_t* workspace_bytes, int64_t* counts_out, void* stream);
+int shine_eval_grid_emit(const double* ref, int64_t n, const void* workspace, size_t workspace_bytes, int64_t n_fine,
+                         int64_t n_coarse, void* grid, size_t* grid_bytes, void* stream);
+int shine_eval_nn_search(const void* grid, int64_t n_ref, int64_t n_fine, int64_t n_coarse, const double* origin, double cell,
+                         const int64_t* cells_per_axis, const double* query, int64_t n_query, double truncation,
+                         void* workspace, size_t* workspace_bytes, int32_t* index_out, double* dist_out, uint8_t* keep_out,
+                         int32_t* stats_out, void* stream);
+int shine_eval_metrics(const double* dist_p, int64_t n_p, const double* dist_r, int64_t n_r, double threshold, void* workspace,
+                       size_t* workspace_bytes, double* sums_out, void* stream);
+
 /* ---- graph-replayable forms of the two calls whose per-iteration scalars are otherwise baked into a captured HIP
  *      graph: the scalars live in device memory and the kernels advance them, so ONE captured iteration
  *      {draw, shine_train_step, [shine_regularize], Adam} can be replayed for every iteration of a frame.

@@ -187,6 +187,21 @@ _SIGNATURES = {
     "shine_mesh_vertex_normals": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.POINTER(C.c_size_t), _P, _P]),
     "shine_mesh_cluster_filter": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.POINTER(C.c_size_t), _P, _P, C.POINTER(C.c_int64),
                                             _P]),
+    # mesh evaluation (csrc/shine_eval.hip)
+    "shine_eval_fine_per_coarse": (C.c_int, []),
+    "shine_eval_bounds": (C.c_int, [_P, C.c_int64, _P, C.POINTER(C.c_size_t), _P, _P]),
+    "shine_eval_box_mask": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P]),
+    "shine_eval_sample_mesh": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_uint64, _P, _P, C.POINTER(C.c_size_t),
+                                         _P, _P, _P]),
+    "shine_eval_voxel_down": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_double), C.c_double, _P, C.POINTER(C.c_size_t), _P, _P,
+                                        C.POINTER(C.c_int64), _P]),
+    "shine_eval_grid_count": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_double), C.c_double, _P, C.POINTER(C.c_size_t),
+                                        C.POINTER(C.c_int64), _P]),
+    "shine_eval_grid_emit": (C.c_int, [_P, C.c_int64, _P, C.c_size_t, C.c_int64, C.c_int64, _P, C.POINTER(C.c_size_t), _P]),
+    "shine_eval_nn_search": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_double), C.c_double,
+                                       C.POINTER(C.c_int64), _P, C.c_int64, C.c_double, _P, C.POINTER(C.c_size_t), _P, _P, _P,
+                                       _P, _P]),
+    "shine_eval_metrics": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_double, _P, C.POINTER(C.c_size_t), _P, _P]),
     "shine_iter_graph_create": (C.c_int, [C.c_int32, C.POINTER(_P)]),
     "shine_iter_graph_destroy": (C.c_int, [_P]),
     "shine_iter_graph_commit": (C.c_int, [_P]),

@@ -280,6 +280,7 @@ class Mesher:
         self.world_scale = config.scale
         self.ts = 0
         self.global_transform = np.eye(4)
+        self.last_mesh_device = None  # (verts f64, faces int32) of the last mesh _finish made, on the device
 
     def get_query_from_bbx(self, bbx, voxel_size):
         """utils/mesher.py:110-152: grid query points of a box (anything with get_min_bound()/get_max_bound(), e.g. an
@@ -431,6 +432,7 @@ class Mesher:
         if filter_isolated_mesh:
             f = cluster_filter_device(f, min_tri)
         v, normals = _transform_device(v, normals, self.global_transform)
+        self.last_mesh_device = (v, f)  # fp64 vertices + int32 faces, still on the device (evaluation.eval_mesh takes the pair)
         vn, fn = v.cpu().numpy(), f.cpu().numpy()
         nn = normals.cpu().numpy() if normals is not None else None
         cn = colors.cpu().numpy() if colors is not None else None
