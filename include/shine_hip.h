@@ -592,6 +592,41 @@ int shine_eval_nn_search(const void* grid, int64_t n_ref, int64_t n_fine, int64_
 int shine_eval_metrics(const double* dist_p, int64_t n_p, const double* dist_r, int64_t n_r, double threshold, void* workspace,
                        size_t* workspace_bytes, double* sums_out, void* stream);
 
+/* ---- the frame front-end (csrc/shine_frame.hip): LiDARDataset.process_frame (dataset/lidar_dataset.py:115-290) and
+ *      dataSampler.sample (utils/data_sampler.py:18-139) on the device.  Sizes are < 2^31 rows; workspace == NULL returns the
+ *      bytes needed in *workspace_bytes.
+ *      _frame_filter: preprocess_kitti + the crop box in ONE launch: keeps, in input order, the points with z > min_z,
+ *        |p| >= min_range, -pc_radius <= x, y <= pc_radius and min_z <= z <= max_z (all inclusive but the first; fp64, no
+ *        fused multiply-add, so the kept set equals numpy's).  points: n rows of `stride` (3 or 4) float32 elements, or fp64
+ *        with is_fp64 != 0; points_out [n][3] fp64 has room for every row; *n_out (HOST) = rows kept (synchronises).
+ *      _ray_sample: ONE launch, no workspace.  points [m][3] fp32 in the scaled space, origin HOST float[3]; per ray surface_n
+ *        samples with label uniform in [-surface_range, surface_range), clearance_n with label in (-surface_range -
+ *        clearance_dist, -surface_range], free_n with ratio uniform in [free_begin_ratio, free_end_dist / dist + 1]; all
+ *        lengths already scaled, fp32 in the reference's operation order (ratio = disp / dist + 1, point = rel * ratio +
+ *        origin, depth = dist * ratio / scale).  Outputs in ray-major order, sample j of ray i at i * S + j, S = surface_n +
+ *        clearance_n + free_n: coord_out [mS][3], sdf_label_out, weight_out (+1 surface, -1 otherwise), sample_depth_out
+ *        (metres), sem_label_out (labels[i] on surface samples, 0 elsewhere; needs labels), origin_out [mS][3], time_out
+ *        (= time_value), ray_depth_out [m]; the last five may be NULL (skipped).  uniforms == NULL: sample t = i * S + j
+ *        draws the 24-bit uniform of counter t from the sorted sampler's generator keyed by (seed, stream_id) — the same bits
+ *        on every run and for every launch geometry; otherwise uniforms holds the reference's draws in ITS order: m * surface_n
+ *        surface draws, then m * clearance_n, then m * free_n, each block sample-major (element k * m + ray).  m == 0: nothing
+ *        is launched.
+ *      _pool_window_filter: the sliding window of the batch-mode pool: keeps, in order, the rows with |coord - origin| < radius
+ *        (fp32; origin HOST float[3]) of n_arrays <= 6 parallel arrays of n rows of words[k] (1 or 3) 4-byte words, src[k] ->
+ *        dst[k] (not in place; coord may be one of the src).  One mask launch, one compaction launch; *n_out (HOST) = rows
+ *        kept (synchronises). -------- */
+int shine_frame_filter(const void* points, int64_t n, int32_t is_fp64, int32_t stride, double min_z, double max_z,
+                       double min_range, double pc_radius, void* workspace, size_t* workspace_bytes, double* points_out,
+                       int64_t* n_out, void* stream);
+int shine_ray_sample(const float* points, int64_t m, const float* origin, int32_t surface_n, int32_t clearance_n, int32_t free_n,
+                     float surface_range, float clearance_dist, float free_begin_ratio, float free_end_dist, float scale,
+                     const int32_t* labels, uint64_t seed, uint64_t stream_id, const float* uniforms, float time_value,
+                     float* coord_out, float* sdf_label_out, float* weight_out, float* sample_depth_out, int32_t* sem_label_out,
+                     float* origin_out, float* time_out, float* ray_depth_out, void* stream);
+int shine_pool_window_filter(const float* coord, int64_t n, const float* origin, float radius, int32_t n_arrays,
+                             const void* const* src, void* const* dst, const int32_t* words, void* workspace,
+                             size_t* workspace_bytes, int64_t* n_out, void* stream);
+
 /* ---- graph-replayable forms of the two calls whose per-iteration scalars are otherwise baked into a captured HIP
  *      graph: the scalars live in device memory and the kernels advance them, so ONE captured iteration
  *      {draw, shine_train_step, [shine_regularize], Adam} can be replayed for every iteration of a frame.

@@ -202,6 +202,15 @@ _SIGNATURES = {
                                        C.POINTER(C.c_int64), _P, C.c_int64, C.c_double, _P, C.POINTER(C.c_size_t), _P, _P, _P,
                                        _P, _P]),
     "shine_eval_metrics": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_double, _P, C.POINTER(C.c_size_t), _P, _P]),
+    # the frame front-end (csrc/shine_frame.hip)
+    "shine_frame_filter": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, _P,
+                                     C.POINTER(C.c_size_t), _P, C.POINTER(C.c_int64), _P]),
+    "shine_ray_sample": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                   C.c_float, C.c_float, C.c_float, _P, C.c_uint64, C.c_uint64, _P, C.c_float, _P, _P, _P, _P,
+                                   _P, _P, _P, _P, _P]),
+    "shine_pool_window_filter": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_float), C.c_float, C.c_int32, C.POINTER(_P),
+                                           C.POINTER(_P), C.POINTER(C.c_int32), _P, C.POINTER(C.c_size_t),
+                                           C.POINTER(C.c_int64), _P]),
     "shine_iter_graph_create": (C.c_int, [C.c_int32, C.POINTER(_P)]),
     "shine_iter_graph_destroy": (C.c_int, [_P]),
     "shine_iter_graph_commit": (C.c_int, [_P]),

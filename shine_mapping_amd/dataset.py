@@ -1,0 +1,604 @@
+"""LiDARDataset (dataset/lidar_dataset.py) on the device: point-cloud files and poses in, training-sample pools out.
+
+    from shine_mapping_amd.dataset import LiDARDataset      # instead of: from dataset.lidar_dataset import LiDARDataset
+    dataset = LiDARDataset(config, octree)
+    for frame_id in ...:
+        dataset.process_frame(frame_id, incremental_on=False)
+    coord, sdf_label, origin, ts, normal_label, sem_label, weight = dataset.get_batch()
+
+Same constructor arguments, attributes and methods as the reference class; no open3d, natsort or pyquaternion.  A frame runs
+    read (.bin / .ply) -> shine_frame_filter (z, range, crop box; fp64) -> evaluation.voxel_down_sample or a seeded random subset
+    -> pose transform (fp64) -> map copy (voxel means, boxes) -> scale, fp32 -> shine_ray_sample (ONE launch, written straight
+    into the pools) -> FeatureOctree.update -> pool replace / shine_pool_window_filter + append
+on the device (csrc/shine_frame.hip).  Differences from the reference, all deliberate:
+  * the samples come from a counter-based generator keyed by (config.seed, frame id, sample), not from torch's global stream: a
+    run is reproducible whatever else draws random numbers;
+  * voxel-down-sampled clouds are in ascending voxel-key order (open3d's order is that of a hash map);
+  * `rand_downsample` keeps exactly int(n * rand_down_r) points (open3d keeps the first int(n * r) of a shuffle: the same count);
+  * batch-mode pools grow in capacity-doubling buffers; the `*_pool` attributes are views of the used part and are REPLACED by
+    every process_frame (do not keep them across frames);
+  * in incremental mode without `ray_loss` the two depth pools stay empty (nothing reads them);
+  * `estimate_normal`, `filter_noise`, `semantic_on`, `.pcd` files, `sapce_carving_sample` and `behind_dropoff_on` are refused.
+"""
+from __future__ import annotations
+
+import csv
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import evaluation as ev
+
+_U64 = (1 << 64) - 1
+UNSUPPORTED = ("estimate_normal", "filter_noise", "semantic_on", "behind_dropoff_on")
+
+
+def natural_key(name):
+    """sort key that orders file names as 1, 2, ... 9, 10 (natsort's default for plain names)"""
+    return [int(t) if t.isdigit() else t.lower() for t in re.split(r"(\d+)", name)]
+
+
+def _rows_to_pose(values):
+    pose = np.zeros((4, 4))
+    pose[0, 0:4] = values[0:4]
+    pose[1, 0:4] = values[4:8]
+    pose[2, 0:4] = values[8:12]
+    pose[3, 3] = 1.0
+    return pose
+
+
+def read_calib_file(filename):
+    """KITTI calib.txt: {key: 4x4} (utils/pose.py:7-30)"""
+    calib = {}
+    with open(filename) as fh:
+        for line in fh:
+            if not line.strip():
+                continue
+            key, content = line.strip().split(":")
+            calib[key] = _rows_to_pose([float(v) for v in content.strip().split()])
+    return calib
+
+
+def read_poses_file(filename, calibration):
+    """KITTI poses.txt: the lidar pose in the world frame, Tr^-1 . P . Tr per line (utils/pose.py:33-58)"""
+    Tr = calibration["Tr"]
+    Tr_inv = np.linalg.inv(Tr)
+    poses = []
+    with open(filename) as fh:
+        for line in fh:
+            if not line.strip():
+                continue
+            pose = _rows_to_pose([float(v) for v in line.strip().split()])
+            poses.append(np.matmul(Tr_inv, np.matmul(pose, Tr)))
+    return poses
+
+
+def quaternion_rotation_matrix(w, x, y, z):
+    """rotation matrix of the quaternion (w, x, y, z), normalised first (pyquaternion's Quaternion.rotation_matrix)"""
+    n = np.sqrt(w * w + x * x + y * y + z * z)
+    if n > 0:
+        w, x, y, z = w / n, x / n, y / n, z / n
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def csv_odom_to_transforms(path):
+    """tx,ty,tz,qx,qy,qz,qw CSV (utils/pose.py:61-87).  The reference hands the four values to Quaternion(array) in the order
+    qx, qy, qz, qw, and that constructor reads a 4-array as (w, x, y, z): the column named qx is used as w, qy as x, qz as y
+    and qw as z.  Kept as it is, so that a driver sees the poses the reference would have produced from the same file."""
+    poses = []
+    with open(path, mode="r") as fh:
+        reader = csv.reader(fh)
+        header = next(reader)
+        header[0] = "ts"
+        for row in reader:
+            if not row:
+                continue
+            odom = {l: row[i] for i, l in enumerate(header)}
+            q = [float(odom[l]) for l in ("qx", "qy", "qz", "qw")]
+            tf = np.eye(4)
+            tf[0:3, 3] = [float(odom[l]) for l in ("tx", "ty", "tz")]
+            tf[0:3, 0:3] = quaternion_rotation_matrix(q[0], q[1], q[2], q[3])
+            poses.append(tf)
+    return poses
+
+
+class BoundingBox:
+    """what Mesher.recon_bbx_mesh takes: get_min_bound() / get_max_bound() (numpy fp64 [3]); empty until the first extend"""
+
+    def __init__(self, min_bound=None, max_bound=None):
+        self.min_bound = None if min_bound is None else np.asarray(min_bound, dtype=np.float64).copy()
+        self.max_bound = None if max_bound is None else np.asarray(max_bound, dtype=np.float64).copy()
+
+    def is_empty(self):
+        return self.min_bound is None
+
+    def get_min_bound(self):
+        return np.zeros(3) if self.min_bound is None else self.min_bound
+
+    def get_max_bound(self):
+        return np.zeros(3) if self.max_bound is None else self.max_bound
+
+    def extend(self, lo, hi):
+        if self.min_bound is None:
+            self.min_bound, self.max_bound = np.array(lo, dtype=np.float64), np.array(hi, dtype=np.float64)
+        else:
+            self.min_bound, self.max_bound = np.minimum(self.min_bound, lo), np.maximum(self.max_bound, hi)
+        return self
+
+
+class PointCloud:
+    """the merged map cloud: fp64 [n,3] device chunks, concatenated when `points` is read"""
+
+    def __init__(self, points=None):
+        self._chunks = [] if points is None else [points]
+
+    def __iadd__(self, other):
+        self._chunks += other._chunks
+        return self
+
+    def __len__(self):
+        return sum(int(c.shape[0]) for c in self._chunks)
+
+    @property
+    def points(self):
+        if len(self._chunks) > 1:
+            self._chunks = [torch.cat(self._chunks, 0)]
+        return self._chunks[0] if self._chunks else torch.empty((0, 3), dtype=torch.float64)
+
+    def get_min_bound(self):
+        return ev.bounds(self.points)[0]
+
+    def get_max_bound(self):
+        return ev.bounds(self.points)[1]
+
+
+def _ws(nbytes, device):
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
+def frame_filter(points, min_z, max_z, min_range, pc_radius):
+    """preprocess_kitti + the crop box (shine_frame_filter): points = device [n,3] / [n,4] float32 or float64, contiguous.  Keeps,
+    in input order, z > min_z, |p| >= min_range, |x|, |y| <= pc_radius, min_z <= z <= max_z.  -> fp64 [k,3] on the device."""
+    if not points.is_cuda:
+        raise _lib.ShineHipError("frame_filter runs on the device only (there is no CPU path)")
+    if points.dim() != 2 or points.shape[1] not in (3, 4) or points.dtype not in (torch.float32, torch.float64):
+        raise ValueError("frame_filter: expected [n,3] or [n,4] float32 / float64 points, got %s %s" % (tuple(points.shape), points.dtype))
+    points = points.contiguous()
+    n = int(points.shape[0])
+    out = torch.empty((n, 3), dtype=torch.float64, device=points.device)
+    if n == 0:
+        return out
+    lib, st = _lib.lib(), _lib.current_stream_handle()
+    need = C.c_size_t(0)
+    args = (n, int(points.dtype == torch.float64), int(points.shape[1]), float(min_z), float(max_z), float(min_range),
+            float(pc_radius))
+    _lib.check(lib.shine_frame_filter(None, *args, None, C.byref(need), None, None, st), "shine_frame_filter")
+    ws = _ws(need.value, points.device)
+    kept = C.c_int64(0)
+    _lib.check(lib.shine_frame_filter(points.data_ptr(), *args, ws.data_ptr(), C.byref(need), out.data_ptr(), C.byref(kept), st),
+               "shine_frame_filter")
+    return out[:kept.value]
+
+
+class SamplerParams:
+    """dataSampler's constants (utils/data_sampler.py:26-37): the scaled lengths are products in double, rounded to fp32 once —
+    what `tensor * python_float` does in the reference"""
+
+    def __init__(self, config):
+        s = float(config.scale)
+        self.ns = int(config.surface_sample_n)
+        self.nc = int(getattr(config, "clearance_sample_n", 0))
+        self.nf = int(config.free_sample_n)
+        self.S = self.ns + self.nc + self.nf
+        self.scale = s
+        self.surface_range = float(config.surface_sample_range_m) * s
+        self.clearance_dist = float(getattr(config, "clearance_dist_m", 0.0)) * s
+        self.free_begin_ratio = float(config.free_sample_begin_ratio)
+        self.free_end_dist = float(config.free_sample_end_dist_m) * s
+
+
+def ray_sample(points, origin, params, seed=0, stream_id=0, uniforms=None, labels=None, time_value=0.0, out=None,
+               depths=True, origin_time=True):
+    """dataSampler.sample in ONE launch (shine_ray_sample).  points [m,3] float32 on the device (scaled space), origin = three
+    floats (host), params = SamplerParams (or anything with its fields).  uniforms: None — the counter-based generator keyed by
+    (seed, stream_id) — or a device float32 [m * S] tensor in the reference's draw order.  labels: int32 [m] or None.
+    `out`: dict of preallocated contiguous tensors to write into (views of the pools); missing ones are allocated.  -> dict with
+    coord [mS,3], sdf_label, weight [mS], and, as asked for, sample_depth [mS], ray_depth [m], origin [mS,3], time [mS],
+    sem_label [mS] int32 — ray-major (sample j of ray i at i * S + j)."""
+    if not points.is_cuda:
+        raise _lib.ShineHipError("ray_sample runs on the device only (there is no CPU path)")
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("ray_sample: points must be [m,3] float32 (config.dtype float32 is the only sample type), got %s %s"
+                         % (tuple(points.shape), points.dtype))
+    points = points.contiguous()
+    dev, m, S = points.device, int(points.shape[0]), int(params.S)
+    want = {"coord": ((m * S, 3), torch.float32), "sdf_label": ((m * S,), torch.float32), "weight": ((m * S,), torch.float32)}
+    if depths:
+        want["sample_depth"] = ((m * S,), torch.float32)
+        want["ray_depth"] = ((m,), torch.float32)
+    if origin_time:
+        want["origin"] = ((m * S, 3), torch.float32)
+        want["time"] = ((m * S,), torch.float32)
+    if labels is not None:
+        labels = labels.to(device=dev, dtype=torch.int32).contiguous()
+        if labels.numel() != m:
+            raise ValueError("ray_sample: labels must hold one int per ray")
+        want["sem_label"] = ((m * S,), torch.int32)
+    res = {}
+    for name, (shape, dtype) in want.items():
+        t = out.get(name) if out else None
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        elif tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
+            raise ValueError("ray_sample: out[%r] must be a contiguous %s %s tensor on %s" % (name, shape, dtype, dev))
+        res[name] = t
+    if uniforms is not None:
+        uniforms = uniforms.to(device=dev, dtype=torch.float32).contiguous()
+        if uniforms.numel() != m * S:
+            raise ValueError("ray_sample: uniforms must hold m * S values")
+
+    def p(name):
+        t = res.get(name)
+        return t.data_ptr() if t is not None and t.numel() else None
+
+    o3 = (C.c_float * 3)(*[float(v) for v in origin])
+    _lib.check(_lib.lib().shine_ray_sample(
+        points.data_ptr() if m else None, m, o3, params.ns, params.nc, params.nf, params.surface_range, params.clearance_dist,
+        params.free_begin_ratio, params.free_end_dist, params.scale, labels.data_ptr() if labels is not None and m else None,
+        int(seed) & _U64, int(stream_id) & _U64, uniforms.data_ptr() if uniforms is not None and m else None, float(time_value),
+        p("coord"), p("sdf_label"), p("weight"), p("sample_depth"), p("sem_label"), p("origin"), p("time"), p("ray_depth"),
+        _lib.current_stream_handle()), "shine_ray_sample")
+    return res
+
+
+def pool_window_filter(coord, origin, radius, arrays):
+    """the sliding window of the batch-mode pool (shine_pool_window_filter): the rows with |coord - origin| < radius (fp32) of up
+    to six parallel device arrays ([n] or [n,3], 4-byte elements), order kept.  -> (list of new tensors with the capacity of
+    the inputs, rows kept); row k of every output is the same input row."""
+    n = int(coord.shape[0])
+    if len(arrays) < 1 or len(arrays) > 6:
+        raise ValueError("pool_window_filter: 1 to 6 arrays")
+    words = []
+    for a in arrays:
+        if not (a.is_cuda and a.is_contiguous() and a.element_size() == 4 and int(a.shape[0]) == n
+                and (a.dim() == 1 or (a.dim() == 2 and a.shape[1] == 3))):
+            raise ValueError("pool_window_filter: arrays must be contiguous device [n] or [n,3] tensors of 4-byte elements")
+        words.append(1 if a.dim() == 1 else 3)
+    outs = [torch.empty_like(a) for a in arrays]
+    if n == 0:
+        return outs, 0
+    if not (coord.is_cuda and coord.is_contiguous() and coord.dtype == torch.float32 and coord.dim() == 2 and coord.shape[1] == 3):
+        raise ValueError("pool_window_filter: coord must be a contiguous device [n,3] float32 tensor")
+    lib, st = _lib.lib(), _lib.current_stream_handle()
+    o3 = (C.c_float * 3)(*[float(v) for v in origin])
+    src, dst = _lib.ptr_array([a.data_ptr() for a in arrays]), _lib.ptr_array([a.data_ptr() for a in outs])
+    w = (C.c_int32 * len(words))(*words)
+    need = C.c_size_t(0)
+    kept = C.c_int64(0)
+    _lib.check(lib.shine_pool_window_filter(None, n, o3, float(radius), len(arrays), src, dst, w, None, C.byref(need), None, st),
+               "shine_pool_window_filter")
+    ws = _ws(need.value, coord.device)
+    _lib.check(lib.shine_pool_window_filter(coord.data_ptr(), n, o3, float(radius), len(arrays), src, dst, w, ws.data_ptr(),
+                                            C.byref(need), C.byref(kept), st), "shine_pool_window_filter")
+    return outs, int(kept.value)
+
+
+_GOLD, _FNV, _M1, _M2 = 0x9E3779B97F4A7C15, 0x100000001B3, 0xBF58476D1CE4E5B9, 0x94D049BB133111EB
+
+
+def _i64(v):
+    v &= _U64
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def random_subset(n, keep, seed, stream_id, device):
+    """`keep` of n indices, ascending, chosen uniformly: the `keep` smallest of one 64-bit key per index — the splitmix64
+    finaliser of (seed, stream_id, index), the generator of the sorted sampler (csrc/shine_sampler_dev.hpp) in int64 arithmetic
+    (wrapping multiplies, logical shifts spelled out).  The same (seed, stream_id) gives the same subset on every run."""
+    k = torch.arange(n, dtype=torch.int64, device=device)
+    z = (k + _i64((int(stream_id) & _U64) * _FNV + 1)) * _i64(_GOLD) + _i64(int(seed))
+
+    def lsr(v, s):
+        return (v >> s) & ((1 << (64 - s)) - 1)
+
+    z = (z ^ lsr(z, 30)) * _i64(_M1)
+    z = (z ^ lsr(z, 27)) * _i64(_M2)
+    z = z ^ lsr(z, 31)
+    if keep >= n:
+        return k
+    return torch.sort(torch.topk(z, int(keep), largest=False, sorted=False).indices).values
+
+
+def transform_points(points, pose):
+    """open3d's PointCloud.transform with a rigid 4x4 pose: R p + t per point, fp64 on the device, products summed left to right"""
+    x, y, z = points[:, 0], points[:, 1], points[:, 2]
+    T = np.asarray(pose, dtype=np.float64)
+    return torch.stack([x * float(T[r, 0]) + y * float(T[r, 1]) + z * float(T[r, 2]) + float(T[r, 3]) for r in range(3)], 1)
+
+
+def _empty(shape, dtype, device):
+    """a zero-row placeholder on `device`; on a host without a GPU (where only the constructor's host logic can run: poses, frame
+    selection, refusals) it lives in host memory instead of failing"""
+    if torch.device(device).type == "cuda" and not torch.cuda.is_available():
+        device = "cpu"
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
+class _Pool:
+    """one pool on the pool device: a capacity-doubling buffer and the number of rows in use"""
+
+    def __init__(self, shape_tail, dtype, device):
+        self.tail, self.dtype, self.device = tuple(shape_tail), dtype, device
+        self.buf = _empty((0,) + self.tail, dtype, device)
+        self.used = 0
+
+    def view(self):
+        return self.buf[:self.used]
+
+    def reserve(self, extra):
+        """room for `extra` more rows (capacity doubles); -> the view of those rows, which become part of the pool"""
+        need = self.used + int(extra)
+        cap = int(self.buf.shape[0])
+        if need > cap:
+            cap = max(need, 2 * cap, 1024)
+            buf = torch.empty((cap,) + self.tail, dtype=self.dtype, device=self.device)
+            buf[:self.used].copy_(self.buf[:self.used])
+            self.buf = buf
+        tail = self.buf[self.used:need]
+        self.used = need
+        return tail
+
+    def replace(self, tensor, used=None):
+        self.buf = tensor
+        self.used = int(tensor.shape[0]) if used is None else int(used)
+
+
+POOL_NAMES = ("coord", "sdf_label", "weight", "sample_depth", "ray_depth", "origin", "time")
+
+
+class LiDARDataset:
+    def __init__(self, config, octree=None) -> None:
+        for name in UNSUPPORTED:
+            if getattr(config, name, False):
+                raise NotImplementedError(
+                    "shine_mapping_amd.dataset.LiDARDataset does not support config.%s = True%s" % (name, {
+                        "behind_dropoff_on": " (the reference's own sampler raises there: it multiplies an [N,1] weight tensor by an [N] drop-off in place)",
+                        "semantic_on": " (frame-level label files and the learning map are not read; ray_sample itself takes labels)",
+                    }.get(name, "")))
+        self.config = config
+        self.dtype = getattr(config, "dtype", torch.float32)
+        if self.dtype != torch.float32:
+            raise NotImplementedError("shine_mapping_amd.dataset.LiDARDataset: config.dtype must be torch.float32 (the sampler kernel is fp32)")
+        self.device = config.device
+        if torch.device(self.device).type != "cuda":
+            raise _lib.ShineHipError("shine_mapping_amd.dataset.LiDARDataset runs on the device only (config.device = %r; there is no CPU path)" % (self.device,))
+
+        self.calib = {}
+        if getattr(config, "calib_path", "") != "":
+            self.calib = read_calib_file(config.calib_path)
+        else:
+            self.calib["Tr"] = np.eye(4)
+        if config.pose_path.endswith("txt"):
+            self.poses_w = read_poses_file(config.pose_path, self.calib)
+        elif config.pose_path.endswith("csv"):
+            self.poses_w = csv_odom_to_transforms(config.pose_path)
+        else:
+            raise ValueError("Wrong pose file format. Please use either *.txt (KITTI format) or *.csv (xyz+quat format)")
+        self.poses_ref = self.poses_w  # (the reference's aliasing: poses_w is overwritten for the used frames)
+
+        self.pc_filenames = sorted(os.listdir(config.pc_path), key=natural_key)
+        self.total_pc_count = len(self.pc_filenames)
+        self.octree = octree
+        self.last_relative_tran = np.eye(4)
+        self.sampler = SamplerParams(config)
+        self.ray_sample_count = config.surface_sample_n + config.free_sample_n
+        self.seed = int(getattr(config, "seed", 42))
+
+        self.map_down_pc = PointCloud()
+        self.map_bbx = BoundingBox()
+        self.cur_bbx = BoundingBox()
+        self.cur_frame_pc = PointCloud()
+
+        self.used_pc_count = 0
+        begin_flag = False
+        self.begin_pose_inv = np.eye(4)
+        for frame_id in range(self.total_pc_count):
+            if frame_id < config.begin_frame or frame_id > config.end_frame or frame_id % config.every_frame != 0:
+                continue
+            if not begin_flag:  # the first frame used
+                begin_flag = True
+                if getattr(config, "first_frame_ref", True):
+                    self.begin_pose_inv = np.linalg.inv(self.poses_w[frame_id])  # T_rw
+                else:
+                    self.begin_pose_inv[2, 3] += getattr(config, "global_shift_default", 0.0)
+            self.poses_ref[frame_id] = np.matmul(self.begin_pose_inv, self.poses_w[frame_id])
+            self.used_pc_count += 1
+
+        if (self.used_pc_count > getattr(config, "pc_count_gpu_limit", 500)
+                and not getattr(config, "continual_learning_reg", False) and not getattr(config, "window_replay_on", False)):
+            self.pool_device = "cpu"  # (sampling still runs on the device; the pools live in host memory)
+            self.to_cpu = True
+            print("too many scans, use cpu memory")
+        else:
+            self.pool_device = config.device
+            self.to_cpu = False
+
+        self._pools = {n: _Pool((3,) if n in ("coord", "origin") else (), self.dtype, self.pool_device) for n in POOL_NAMES}
+        self.normal_label_pool = _empty((0, 3), self.dtype, self.pool_device)
+        self.color_label_pool = _empty((0, 3), self.dtype, self.pool_device)
+        self.sem_label_pool = _empty((0,), torch.long, self.pool_device)
+        self._publish()
+        self._pool_version = 0
+        self._sorted = None  # (SortedPool, pool version, tables epoch)
+        self._sorted_perm = None
+
+    # ---- pools --------------------------------------------------------------------------------------------------------------
+    def _publish(self):
+        for n in POOL_NAMES:
+            setattr(self, n + "_pool", self._pools[n].view())
+
+    def _kept_pools(self):
+        """the pools batch mode appends to (dataset/lidar_dataset.py:262-271)"""
+        return ("coord", "weight", "sample_depth", "ray_depth") if self.config.ray_loss else \
+            ("coord", "weight", "sdf_label", "origin", "time")
+
+    # ---- files ----------------------------------------------------------------------------------------------------------------
+    def read_point_cloud(self, filename: str):
+        """the raw points of a file on the device: [n,4] float32 (.bin) or [n,3] float64 (.ply)"""
+        if ".bin" in filename:
+            pts = torch.from_numpy(np.fromfile(filename, dtype=np.float32).reshape((-1, 4)))
+        elif ".ply" in filename:
+            pts = torch.from_numpy(np.ascontiguousarray(ev.read_ply(filename)["vertices"], dtype=np.float64))
+        elif ".pcd" in filename:
+            raise NotImplementedError("shine_mapping_amd.dataset.LiDARDataset does not read .pcd files (%s): convert to .ply or "
+                                      "KITTI .bin" % filename)
+        else:
+            raise ValueError("The format of the imported point cloud is wrong (support only *ply and *bin): %s" % filename)
+        return pts.to(self.device)
+
+    def sapce_carving_sample(self, *args, **kwargs):
+        raise NotImplementedError("shine_mapping_amd.dataset.LiDARDataset does not support sapce_carving_sample (deprecated in the "
+                                  "reference; it needs kaolin's ray tracer)")
+
+    # ---- one frame ------------------------------------------------------------------------------------------------------------
+    def frame_points(self, frame_id):
+        """stages 1-3 of process_frame: the frame's points in the SENSOR frame after filter, crop and down-sampling (fp64 device)"""
+        cfg = self.config
+        raw = self.read_point_cloud(os.path.join(cfg.pc_path, self.pc_filenames[frame_id]))
+        pts = frame_filter(raw, cfg.min_z, cfg.max_z, cfg.min_range, cfg.pc_radius)
+        if pts.shape[0] == 0:
+            raise ValueError("frame %d (%s): no point passes min_z / min_range / the crop box" % (frame_id, self.pc_filenames[frame_id]))
+        if cfg.rand_downsample:
+            n = int(pts.shape[0])
+            keep = int(n * cfg.rand_down_r)
+            if keep < n:
+                pts = pts[random_subset(n, keep, self.seed, frame_id, pts.device)]
+        else:
+            pts = ev.voxel_down_sample(pts, cfg.vox_down_m)
+        return pts
+
+    def process_frame(self, frame_id, incremental_on=False):
+        cfg = self.config
+        self.cur_pose_ref = self.poses_ref[frame_id]
+        pts = transform_points(self.frame_points(frame_id), self.cur_pose_ref)
+        frame_origin = (self.cur_pose_ref[:3, 3] * cfg.scale).astype(np.float32)
+
+        # the copy merged into the map cloud
+        self.cur_frame_pc = PointCloud(ev.voxel_down_sample(pts, cfg.map_vox_down_m))
+        self.map_down_pc += self.cur_frame_pc
+        lo, hi = ev.bounds(self.cur_frame_pc.points)
+        self.cur_bbx = BoundingBox(lo, hi)
+        self.map_bbx = BoundingBox(self.map_bbx.min_bound, self.map_bbx.max_bound).extend(lo, hi)  # (running union)
+
+        pts_s = (pts * cfg.scale).to(self.dtype)  # scale in fp64 as open3d does, then the cast of torch.tensor(..., dtype)
+        m, S = int(pts_s.shape[0]), self.sampler.S
+        on_device = not self.to_cpu
+        pools = self._pools
+        point_mode = not cfg.ray_loss
+        if incremental_on:
+            out = None  # fresh tensors replace the pools
+        else:
+            if getattr(cfg, "window_replay_on", False) and pools["coord"].used:
+                if cfg.ray_loss:
+                    raise NotImplementedError("window_replay_on with ray_loss in batch mode: the reference's window filter indexes "
+                                              "the empty sdf_label_pool there and raises; switch one of them off")
+                names = self._kept_pools()
+                outs, kept = pool_window_filter(pools["coord"].view(), frame_origin, cfg.window_radius * cfg.scale,
+                                                [pools[n].view() for n in names])
+                for n, t in zip(names, outs):
+                    pools[n].replace(t, kept)
+            out = None
+            if on_device:  # the sampler writes straight into the pools' tails
+                out = {n: pools[n].reserve(m if n == "ray_depth" else m * S) for n in self._kept_pools()}
+        res = ray_sample(pts_s, frame_origin, self.sampler, seed=self.seed, stream_id=frame_id, time_value=float(frame_id), out=out,
+                         depths=bool(cfg.ray_loss), origin_time=point_mode or incremental_on)
+
+        if self.octree is not None:
+            if cfg.octree_from_surface_samples:
+                # coord[weight > 0]: the first surface_sample_n samples of every ray, in the same order
+                surf = res["coord"].view(m, S, 3)[:, :self.sampler.ns].reshape(-1, 3)
+                self.octree.update(surf, incremental_on)
+            else:
+                self.octree.update(pts_s, incremental_on)
+
+        if incremental_on:
+            for n in POOL_NAMES:
+                t = res.get(n)
+                if t is None:
+                    t = torch.empty((0,) + pools[n].tail, dtype=self.dtype, device=self.device)
+                pools[n].replace(t.to(self.pool_device))
+            self.normal_label_pool = None
+            self.sem_label_pool = None
+        else:
+            if not on_device:
+                for n in self._kept_pools():
+                    pools[n].reserve(res[n].shape[0]).copy_(res[n])
+            self.normal_label_pool = None
+            self.sem_label_pool = None
+        self._publish()
+        self._pool_version += 1
+
+    # ---- batches --------------------------------------------------------------------------------------------------------------
+    def sorted_pool(self):
+        """the point-sample pools as a SortedPool (node order + hash slots), planned when the pools or the octree changed: what
+        loop.GraphedIteration / fused_train_step(pool=...) take, and what get_batch draws through"""
+        from .sampler import SortedPool
+
+        if self.octree is None:
+            raise ValueError("LiDARDataset.sorted_pool needs the octree the dataset was built with")
+        if self.config.ray_loss or self.to_cpu:
+            raise ValueError("LiDARDataset.sorted_pool serves the point-sample pools on the device (not ray_loss, not the CPU pool)")
+        key = (self._pool_version, self.octree._tables_epoch)
+        if self._sorted is None or self._sorted[1] != key:
+            if self._sorted is None:
+                sp = SortedPool(self.octree, self.coord_pool, self.sdf_label_pool, self.weight_pool, seed=self.seed)
+            else:
+                sp = self._sorted[0]
+                sp.rebuild(self.coord_pool, self.sdf_label_pool, self.weight_pool)
+            self._sorted = (sp, key)
+            self._sorted_perm = sp.perm.long()
+        return self._sorted[0]
+
+    def get_batch(self):
+        cfg = self.config
+        if cfg.ray_loss:
+            n_ray = self.ray_depth_pool.shape[0]
+            # (the reference's ray_sample_count = surface_sample_n + free_sample_n is the stride it indexes the pool with)
+            R = self.ray_sample_count
+            ray_index = torch.randint(0, n_ray, (cfg.bs,), device=self.pool_device)
+            index = ((ray_index * R).repeat(R, 1) + torch.arange(0, R, dtype=torch.int64, device=self.pool_device).reshape(-1, 1)
+                     ).transpose(0, 1).reshape(-1)
+            coord = self.coord_pool[index, :].to(self.device)
+            weight = self.weight_pool[index].to(self.device)
+            sample_depth = self.sample_depth_pool[index].to(self.device)
+            ray_depth = self.ray_depth_pool[ray_index].to(self.device)
+            return coord, sample_depth, ray_depth, None, None, weight
+        if self.octree is not None and not self.to_cpu:
+            sp = self.sorted_pool()
+            idx = sp.draw(cfg.bs)
+            coord, sdf_label, weight = sp.get_batch(idx)
+            src = self._sorted_perm[idx.long()]
+            return coord, sdf_label, self.origin_pool[src], self.time_pool[src], None, None, weight
+        n = self.sdf_label_pool.shape[0]
+        index = torch.randint(0, n, (cfg.bs,), device=self.pool_device)
+        return (self.coord_pool[index, :].to(self.device), self.sdf_label_pool[index].to(self.device),
+                self.origin_pool[index].to(self.device), self.time_pool[index].to(self.device), None, None,
+                self.weight_pool[index].to(self.device))
+
+    def write_merged_pc(self, out_path):
+        from .mesher import write_ply
+
+        pts = transform_points(self.map_down_pc.points, np.linalg.inv(self.begin_pose_inv)).cpu().numpy()  # back to the world frame
+        write_ply(out_path, [("x", pts[:, 0], "double"), ("y", pts[:, 1], "double"), ("z", pts[:, 2], "double")])
+        print("save the merged point cloud map to %s\n" % (out_path))
+
+    def __len__(self) -> int:
+        if self.config.ray_loss:
+            return self.ray_depth_pool.shape[0]  # ray count
+        return self.sdf_label_pool.shape[0]  # point sample count

@@ -161,6 +161,14 @@ def make_frames(cfg, frames=100, beams=64, azimuths=450, seed=42, device="cuda")
     """Yield per-frame (coord, sdf_label, weight) in the scaled space, like LiDARDataset.process_frame (:115-233).
     Each segment of the trajectory is a street canyon in its own frame (ground, two facades, boxes); a scan is ray-cast
     against the canyon of the segment the sensor is in."""
+    gen = torch.Generator(device=device).manual_seed(seed + 1) if str(device) != "cpu" else \
+        torch.Generator().manual_seed(seed + 1)
+    for hits, origin, shift in make_scans(cfg, frames, beams, azimuths, seed, device):
+        yield sample_rays((hits - shift) * cfg.scale, (origin - shift) * cfg.scale, cfg, gen)
+
+
+def make_scans(cfg, frames=100, beams=64, azimuths=450, seed=42, device="cuda"):
+    """Yield per-frame (hit points [M,3], sensor origin [3], map centre [3]) in metres: the scans make_frames samples."""
     g = torch.Generator().manual_seed(seed)
     segs = trajectory(cfg.street_len, getattr(cfg, "turns", 0))
     boxes = []
@@ -168,8 +176,6 @@ def make_frames(cfg, frames=100, beams=64, azimuths=450, seed=42, device="cuda")
         lo, hi = _boxes(length, g, n=max(4, int(20 * length / 100.0)) if len(segs) > 1 else 20)
         boxes.append((lo.to(device), hi.to(device)))
     dirs = sensor_dirs(beams, azimuths, device=device)
-    gen = torch.Generator(device=device).manual_seed(seed + 1) if str(device) != "cpu" else \
-        torch.Generator().manual_seed(seed + 1)
     total = sum(sg[3] for sg in segs)
     step = total / max(frames, 1)
     # centre the map on the origin so it fits the [-1,1] cube (the reference shifts by the first pose, first_frame_ref)
@@ -196,7 +202,67 @@ def make_frames(cfg, frames=100, beams=64, azimuths=450, seed=42, device="cuda")
             origin = local_origin @ R.T + base
         else:
             origin = local_origin
-        yield sample_rays((hits - shift) * cfg.scale, (origin - shift) * cfg.scale, cfg, gen)
+        yield hits, origin, shift
+
+
+def write_kitti_drive(folder, cfg, frames=6, beams=64, azimuths=450, seed=42, device="cpu", yaw_per_frame=0.05):
+    """Write make_scans' drive as a KITTI-format folder — velodyne/%06d.bin (float32 x, y, z, intensity in the SENSOR frame),
+    poses.txt (camera-frame poses, 12 values per line) and calib.txt (Tr: lidar -> camera) — the input LiDARDataset reads.
+    The sensor yaws by `yaw_per_frame` rad per frame, so the poses carry a rotation.  Returns a SimpleNamespace with pc_path,
+    pose_path, calib_path and lidar_poses (the [4,4] float64 lidar-to-world poses the files encode: Tr^-1 . P . Tr)."""
+    import os
+
+    import numpy as np
+
+    pc_path = os.path.join(folder, "velodyne")
+    os.makedirs(pc_path, exist_ok=True)
+    # KITTI's axis convention (camera x = -lidar y, y = -lidar z, z = lidar x) plus a small lever arm
+    Tr = np.array([[0.0, -1.0, 0.0, 0.05], [0.0, 0.0, -1.0, -0.08], [1.0, 0.0, 0.0, -0.27], [0.0, 0.0, 0.0, 1.0]])
+    Tr_inv = np.linalg.inv(Tr)
+    poses, lines = [], []
+    for f, (hits, origin, shift) in enumerate(make_scans(cfg, frames, beams, azimuths, seed, device)):
+        yaw = yaw_per_frame * f
+        W = np.eye(4)
+        W[:3, :3] = [[math.cos(yaw), -math.sin(yaw), 0.0], [math.sin(yaw), math.cos(yaw), 0.0], [0.0, 0.0, 1.0]]
+        W[:3, 3] = (origin - shift).double().cpu().numpy()
+        local = ((hits - shift).double().cpu().numpy() - W[:3, 3]) @ W[:3, :3]  # R^T (p - t)
+        scan = np.zeros((local.shape[0], 4), dtype=np.float32)
+        scan[:, :3] = local
+        scan.tofile(os.path.join(pc_path, "%06d.bin" % f))
+        P = Tr @ W @ Tr_inv
+        lines.append(" ".join(repr(float(v)) for v in P[:3].reshape(-1)))
+        poses.append(Tr_inv @ (_pose_from_line(lines[-1]) @ Tr))  # (as a reader of the file computes it)
+    pose_path, calib_path = os.path.join(folder, "poses.txt"), os.path.join(folder, "calib.txt")
+    with open(pose_path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    with open(calib_path, "w") as fh:
+        for key in ("P0", "P1", "P2", "P3"):
+            fh.write("%s: 1.0 0.0 0.0 0.0 0.0 1.0 0.0 0.0 0.0 0.0 1.0 0.0\n" % key)
+        fh.write("Tr: " + " ".join(repr(float(v)) for v in Tr[:3].reshape(-1)) + "\n")
+    return SimpleNamespace(pc_path=pc_path, pose_path=pose_path, calib_path=calib_path, lidar_poses=poses, frames=frames)
+
+
+def dataset_config(kind, drive, device="cuda", **over):
+    """make_config(kind) plus the fields LiDARDataset reads (utils/config.py's names and defaults, the preset's crop radius and
+    minimum range), pointed at a write_kitti_drive folder"""
+    c = make_config(kind, device=device)
+    c.__dict__.update(
+        pc_path=drive.pc_path, pose_path=drive.pose_path, calib_path=drive.calib_path, first_frame_ref=False, begin_frame=0,
+        end_frame=drive.frames - 1, every_frame=1, seed=42, pc_count_gpu_limit=500, global_shift_default=0.0,
+        min_range=c.min_range_m, pc_radius=c.pc_radius_m, min_z=-10.0, max_z=30.0, rand_downsample=False, vox_down_m=0.05,
+        rand_down_r=1.0, map_vox_down_m=0.2, estimate_normal=False, filter_noise=False, semantic_on=False,
+        behind_dropoff_on=False, octree_from_surface_samples=True, clearance_dist_m=0.3, clearance_sample_n=0,
+        continual_learning_reg=False, window_replay_on=False, window_radius=50.0, ray_loss=False)
+    c.__dict__.update(over)
+    return c
+
+
+def _pose_from_line(line):
+    import numpy as np
+
+    P = np.eye(4)
+    P[:3, :] = np.array([float(v) for v in line.split()]).reshape(3, 4)
+    return P
 
 
 def build_workload(kind="maicity", frames=100, device="cuda", seed=42, beams=64, azimuths=450, **over):
