@@ -614,7 +614,25 @@ int shine_eval_metrics(const double* dist_p, int64_t n_p, const double* dist_r, 
  *      _pool_window_filter: the sliding window of the batch-mode pool: keeps, in order, the rows with |coord - origin| < radius
  *        (fp32; origin HOST float[3]) of n_arrays <= 6 parallel arrays of n rows of words[k] (1 or 3) 4-byte words, src[k] ->
  *        dst[k] (not in place; coord may be one of the src).  One mask launch, one compaction launch; *n_out (HOST) = rows
- *        kept (synchronises). -------- */
+ *        kept (synchronises).
+ *      _depth_unproject: a depth image -> the frame's points in ONE launch (what open3d's RGBDImage.create_from_color_and_depth +
+ *        PointCloud.create_from_rgbd_image do in dataset/rgbd_to_kitti_format.py:78-81, then _frame_filter's test).  depth: DEVICE
+ *        image of `height` rows of `width` pixels, row_pitch (>= width) PIXELS from row to row, uint16 or (is_float32 != 0)
+ *        float32; neither the base address nor the pitch need any alignment.  Per pixel of column u, row v:
+ *          d = (float)raw / (float)depth_scale                          fp32, correctly rounded
+ *          valid iff d > 0, d < (float)depth_trunc and d finite         (d >= depth_trunc is dropped, not clamped)
+ *          z = (double)d, x = (u - cx) * z / fx, y = (v - cy) * z / fy  fp64, in this order
+ *          p = M (x, y, z, 1), every row m0 * x + m1 * y + m2 * z + m3 summed left to right, M = cam_to_sensor (HOST 4x4
+ *              row-major, rows 0-2 are read; NULL = identity)
+ *        no fused multiply-add anywhere.  p is kept under exactly _frame_filter's test (z > min_z, |p| >= min_range, |x|, |y| <=
+ *        pc_radius, min_z <= z <= max_z); min_z = -inf, max_z = pc_radius = +inf, min_range = 0 switch it off.  points_out
+ *        [width * height][3] fp64 receives the kept points in ascending pixel index v * width + u, index_out (int32
+ *        [width * height], may be NULL) that pixel index, *n_out (HOST) the count (synchronises).  fx, fy != 0, depth_scale > 0;
+ *        width * height == 0 launches nothing. -------- */
+int shine_depth_unproject(const void* depth, int32_t is_float32, int32_t width, int32_t height, int64_t row_pitch, double fx,
+                          double fy, double cx, double cy, double depth_scale, double depth_trunc, const double* cam_to_sensor,
+                          double min_z, double max_z, double min_range, double pc_radius, void* workspace,
+                          size_t* workspace_bytes, double* points_out, int32_t* index_out, int64_t* n_out, void* stream);
 int shine_frame_filter(const void* points, int64_t n, int32_t is_fp64, int32_t stride, double min_z, double max_z,
                        double min_range, double pc_radius, void* workspace, size_t* workspace_bytes, double* points_out,
                        int64_t* n_out, void* stream);

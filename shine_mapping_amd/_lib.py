@@ -205,6 +205,9 @@ _SIGNATURES = {
     # the frame front-end (csrc/shine_frame.hip)
     "shine_frame_filter": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, _P,
                                      C.POINTER(C.c_size_t), _P, C.POINTER(C.c_int64), _P]),
+    "shine_depth_unproject": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int64] + [C.c_double] * 6
+                              + [C.POINTER(C.c_double)] + [C.c_double] * 4
+                              + [_P, C.POINTER(C.c_size_t), _P, _P, C.POINTER(C.c_int64), _P]),
     "shine_ray_sample": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                    C.c_float, C.c_float, C.c_float, _P, C.c_uint64, C.c_uint64, _P, C.c_float, _P, _P, _P, _P,
                                    _P, _P, _P, _P, _P]),

@@ -1,10 +1,13 @@
 // shine_frame.hip — the frame front-end of LiDARDataset.process_frame (dataset/lidar_dataset.py:115-290, utils/data_sampler.py:18-139)
 // on the device: what turns one scan and one pose into training samples.
 //   shine_frame_filter        preprocess_kitti (z > min_z, |p| >= min_range) + the inclusive crop box, fp64, compacted in input order
+//   shine_depth_unproject     a depth image (uint16 / float32) -> the frame's points: back-projection through the pinhole intrinsics
+//                             (dataset/rgbd_to_kitti_format.py:78-81), the camera-to-sensor matrix and shine_frame_filter's test,
+//                             compacted in pixel order, ONE launch
 //   shine_ray_sample          dataSampler.sample: surface / clearance / free-space samples of every ray, ONE launch, ray-major
 //   shine_pool_window_filter  the sliding window of the batch-mode pool (|coord - origin| < radius), stable, <= 6 parallel arrays
-// All three are streaming kernels: the sampler writes 4-byte words lane-contiguously (the [*,3] rows go through LDS so that its
-// stores are dword-linear too) and has no atomics; the two compactions order their tiles through one chained prefix
+// All four are streaming kernels: the sampler writes 4-byte words lane-contiguously (the [*,3] rows go through LDS so that its
+// stores are dword-linear too) and has no atomics; the three compactions order their tiles through one chained prefix
 // (tile_exclusive_prefix) instead of a scan launch, so the input is read once.
 #include "shine_internal.hpp"
 
@@ -138,6 +141,143 @@ __global__ __launch_bounds__(T) void k_frame_filter(const P* __restrict__ pts, i
       o[0] = x[k];
       o[1] = y[k];
       o[2] = z[k];
+    }
+  if (tile == n_tiles - 1 && threadIdx.x == 0) *total = excl + count;
+}
+
+// ---- shine_depth_unproject -----------------------------------------------------------------------------------------------------
+// Lane-major sibling of tile_ranks: element thread * ITEMS + k of a tile of ITEMS * T elements (every lane owns ITEMS CONSECUTIVE
+// elements, so that it can fetch them in one vector load).  rank[k] = kept elements of the tile in front of that element (input
+// order); returns the tile's kept count.
+template <int ITEMS>
+__device__ __forceinline__ int tile_ranks_lane_major(TileShared& sm, const bool (&keep)[ITEMS], int (&rank)[ITEMS]) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  int in_front = 0, wave_total = 0;  // kept elements of the lanes below this one / of the whole wave
+#pragma unroll
+  for (int k = 0; k < ITEMS; ++k) {
+    const unsigned long long bal = __ballot(keep[k]);
+    in_front += __popcll(bal & below);
+    wave_total += __popcll(bal);
+  }
+  if (lane == 0) sm.cnt[wv] = wave_total;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int run = 0;
+    for (int e = 0; e < T / 64; ++e) {
+      sm.off[e] = run;
+      run += sm.cnt[e];
+    }
+    sm.off[T / 64] = run;
+  }
+  __syncthreads();
+  int own = sm.off[wv] + in_front;
+#pragma unroll
+  for (int k = 0; k < ITEMS; ++k) {
+    rank[k] = own;
+    own += keep[k] ? 1 : 0;
+  }
+  return sm.off[T / 64];
+}
+
+constexpr int DV = 4;  // pixels per lane, one 8-byte (uint16) or 16-byte (float32) load: a 640 x 480 image is 300 tiles of 1024
+
+struct Unproject {
+  double fx, fy, cx, cy;
+  float depth_scale, depth_trunc;
+  double m[12];  // cam_to_sensor, rows 0-2
+  FilterBox box;
+};
+
+template <typename P>
+struct PixelVec;
+template <>
+struct PixelVec<unsigned short> {
+  typedef ushort4 type;
+};
+template <>
+struct PixelVec<float> {
+  typedef float4 type;
+};
+
+// One tile = DV * T consecutive pixels in row-major order (pixel i = row i / width, column i % width, at depth[row * pitch +
+// column]).  A lane whose DV pixels lie in one row at an address aligned to the vector takes them in one load; every other lane
+// (row ends, an unaligned base or pitch, the image's tail) takes them one by one.
+template <typename P>
+__global__ __launch_bounds__(T) void k_depth_unproject(const P* __restrict__ depth, int width, long long pitch, long long n,
+                                                       Unproject q, double* __restrict__ out, int* __restrict__ index_out,
+                                                       unsigned long long* state, unsigned int* counter, long long* total,
+                                                       int n_tiles) {
+#pragma clang fp contract(off)  // (every product and sum below is one correctly rounded IEEE operation, in the order written)
+  typedef typename PixelVec<P>::type V;
+  __shared__ TileShared sm;
+  const int tile = take_ticket(sm, counter);
+  const long long i0 = (long long)tile * (DV * T) + (long long)threadIdx.x * DV;
+  P raw[DV];
+  int col[DV], row[DV];
+  bool keep[DV];
+  int rank[DV];
+  double x[DV], y[DV], z[DV];
+#pragma unroll
+  for (int k = 0; k < DV; ++k) {
+    raw[k] = (P)0;
+    col[k] = 0;
+    row[k] = 0;
+  }
+  if (i0 < n) {
+    const int r0 = (int)(i0 / width), c0 = (int)(i0 - (long long)r0 * width);
+    const P* at = depth + (long long)r0 * pitch + c0;
+    if (i0 + DV <= n && c0 + DV <= width && ((unsigned long long)at & (sizeof(V) - 1)) == 0) {
+      const V v = *(const V*)at;
+      raw[0] = v.x;
+      raw[1] = v.y;
+      raw[2] = v.z;
+      raw[3] = v.w;
+#pragma unroll
+      for (int k = 0; k < DV; ++k) {
+        row[k] = r0;
+        col[k] = c0 + k;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < DV; ++k) {
+        const long long i = i0 + k;
+        if (i < n) {
+          row[k] = (int)(i / width);
+          col[k] = (int)(i - (long long)row[k] * width);
+          raw[k] = depth[(long long)row[k] * pitch + col[k]];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < DV; ++k) {
+    const float d = __fdiv_rn((float)raw[k], q.depth_scale);
+    keep[k] = false;
+    // (a pixel past the image's end holds raw 0 and drops out here; NaN fails d > 0, +inf fails the last test)
+    if (d > 0.0f && d < q.depth_trunc && d <= 3.402823466e+38f) {
+      const double zc = (double)d;
+      const double xc = ((double)col[k] - q.cx) * zc / q.fx;
+      const double yc = ((double)row[k] - q.cy) * zc / q.fy;
+      x[k] = q.m[0] * xc + q.m[1] * yc + q.m[2] * zc + q.m[3];
+      y[k] = q.m[4] * xc + q.m[5] * yc + q.m[6] * zc + q.m[7];
+      z[k] = q.m[8] * xc + q.m[9] * yc + q.m[10] * zc + q.m[11];
+      const FilterBox& b = q.box;
+      const double r = __dsqrt_rn(x[k] * x[k] + y[k] * y[k] + z[k] * z[k]);
+      keep[k] = z[k] > b.min_z && r >= b.min_range && x[k] >= -b.radius && x[k] <= b.radius && y[k] >= -b.radius &&
+                y[k] <= b.radius && z[k] >= b.min_z && z[k] <= b.max_z;
+    }
+  }
+  const int count = tile_ranks_lane_major<DV>(sm, keep, rank);
+  const long long excl = tile_exclusive_prefix(sm, state, tile, count);
+#pragma unroll
+  for (int k = 0; k < DV; ++k)
+    if (keep[k]) {
+      double* o = out + (excl + rank[k]) * 3;
+      o[0] = x[k];
+      o[1] = y[k];
+      o[2] = z[k];
+      if (index_out) index_out[excl + rank[k]] = (int)(i0 + k);
     }
   if (tile == n_tiles - 1 && threadIdx.x == 0) *total = excl + count;
 }
@@ -339,6 +479,59 @@ extern "C" int shine_frame_filter(const void* points, int64_t n, int32_t is_fp64
   else
     hipLaunchKernelGGL(k_frame_filter<float>, dim3((unsigned)n_tiles), dim3(T), 0, st, (const float*)points, (int)stride,
                        (long long)n, b, points_out, s.state, s.counter, s.total, (int)n_tiles);
+  SHINE_HIP_CHECK(hipGetLastError());
+  long long total = 0;
+  SHINE_HIP_CHECK(hipMemcpyAsync(&total, s.total, 8, hipMemcpyDeviceToHost, st));
+  SHINE_HIP_CHECK(hipStreamSynchronize(st));
+  *n_out = total;
+  return SHINE_OK;
+}
+
+extern "C" int shine_depth_unproject(const void* depth, int32_t is_float32, int32_t width, int32_t height, int64_t row_pitch,
+                                     double fx, double fy, double cx, double cy, double depth_scale, double depth_trunc,
+                                     const double* cam_to_sensor, double min_z, double max_z, double min_range, double pc_radius,
+                                     void* workspace, size_t* workspace_bytes, double* points_out, int32_t* index_out,
+                                     int64_t* n_out, void* stream) {
+  if (!workspace_bytes || width < 0 || height < 0 || (long long)width * height > MAX_ROWS)
+    return set_error(SHINE_E_INVALID, "shine_depth_unproject: bad size (width, height >= 0, width * height < 2^31, workspace_bytes required)");
+  if (row_pitch < width) return set_error(SHINE_E_INVALID, "shine_depth_unproject: row_pitch must be >= width (in pixels)");
+  const long long n = (long long)width * height;
+  const long long n_tiles = (n + DV * T - 1) / (DV * T);
+  Carve c{(char*)workspace};
+  ChainScratch s = carve_chain(c, n_tiles);
+  if (!workspace) {
+    *workspace_bytes = c.off;
+    return SHINE_OK;
+  }
+  if (*workspace_bytes < c.off) return set_error(SHINE_E_INVALID, "shine_depth_unproject: workspace too small");
+  if (!n_out) return set_error(SHINE_E_INVALID, "shine_depth_unproject: null n_out");
+  if (!(fx != 0.0) || !(fy != 0.0) || fx != fx || fy != fy || cx != cx || cy != cy)
+    return set_error(SHINE_E_INVALID, "shine_depth_unproject: fx and fy must be non-zero, no NaN intrinsics");
+  if (!(depth_scale > 0.0) || depth_trunc != depth_trunc)
+    return set_error(SHINE_E_INVALID, "shine_depth_unproject: depth_scale must be > 0, depth_trunc not NaN");
+  if (!(pc_radius >= 0.0) || !(max_z >= min_z) || min_range != min_range)
+    return set_error(SHINE_E_INVALID, "shine_depth_unproject: pc_radius < 0, max_z < min_z or a NaN bound");
+  *n_out = 0;
+  if (n == 0) return SHINE_OK;
+  if (!depth || !points_out) return set_error(SHINE_E_INVALID, "shine_depth_unproject: null depth or points_out");
+  Unproject q;
+  q.fx = fx;
+  q.fy = fy;
+  q.cx = cx;
+  q.cy = cy;
+  q.depth_scale = (float)depth_scale;
+  q.depth_trunc = (float)depth_trunc;
+  for (int e = 0; e < 12; ++e) q.m[e] = cam_to_sensor ? cam_to_sensor[e] : (e % 5 == 0 ? 1.0 : 0.0);
+  q.box = FilterBox{min_z, max_z, min_range, pc_radius};
+  hipStream_t st = (hipStream_t)stream;
+  SHINE_HIP_CHECK(hipMemsetAsync(s.counter, 0, s.clear_bytes, st));
+  if (is_float32)
+    hipLaunchKernelGGL(k_depth_unproject<float>, dim3((unsigned)n_tiles), dim3(T), 0, st, (const float*)depth, (int)width,
+                       (long long)row_pitch, n, q, points_out, (int*)index_out, s.state, s.counter, s.total, (int)n_tiles);
+  else
+    hipLaunchKernelGGL(k_depth_unproject<unsigned short>, dim3((unsigned)n_tiles), dim3(T), 0, st, (const unsigned short*)depth,
+                       (int)width, (long long)row_pitch, n, q, points_out, (int*)index_out, s.state, s.counter, s.total,
+                       (int)n_tiles);
   SHINE_HIP_CHECK(hipGetLastError());
   long long total = 0;
   SHINE_HIP_CHECK(hipMemcpyAsync(&total, s.total, 8, hipMemcpyDeviceToHost, st));

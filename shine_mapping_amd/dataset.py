@@ -379,20 +379,10 @@ class LiDARDataset:
         if torch.device(self.device).type != "cuda":
             raise _lib.ShineHipError("shine_mapping_amd.dataset.LiDARDataset runs on the device only (config.device = %r; there is no CPU path)" % (self.device,))
 
-        self.calib = {}
-        if getattr(config, "calib_path", "") != "":
-            self.calib = read_calib_file(config.calib_path)
-        else:
-            self.calib["Tr"] = np.eye(4)
-        if config.pose_path.endswith("txt"):
-            self.poses_w = read_poses_file(config.pose_path, self.calib)
-        elif config.pose_path.endswith("csv"):
-            self.poses_w = csv_odom_to_transforms(config.pose_path)
-        else:
-            raise ValueError("Wrong pose file format. Please use either *.txt (KITTI format) or *.csv (xyz+quat format)")
+        self.poses_w = self._read_poses(config)
         self.poses_ref = self.poses_w  # (the reference's aliasing: poses_w is overwritten for the used frames)
 
-        self.pc_filenames = sorted(os.listdir(config.pc_path), key=natural_key)
+        self.pc_filenames = self._list_frames(config)
         self.total_pc_count = len(self.pc_filenames)
         self.octree = octree
         self.last_relative_tran = np.eye(4)
@@ -449,6 +439,24 @@ class LiDARDataset:
             ("coord", "weight", "sdf_label", "origin", "time")
 
     # ---- files ----------------------------------------------------------------------------------------------------------------
+    # (the two things a subclass with another kind of frame file replaces, next to frame_points: rgbd.RGBDDataset)
+    def _read_poses(self, config):
+        """the sensor poses in the world frame, one 4x4 per frame (dataset/lidar_dataset.py:47-57)"""
+        self.calib = {}
+        if getattr(config, "calib_path", "") != "":
+            self.calib = read_calib_file(config.calib_path)
+        else:
+            self.calib["Tr"] = np.eye(4)
+        if config.pose_path.endswith("txt"):
+            return read_poses_file(config.pose_path, self.calib)
+        if config.pose_path.endswith("csv"):
+            return csv_odom_to_transforms(config.pose_path)
+        raise ValueError("Wrong pose file format. Please use either *.txt (KITTI format) or *.csv (xyz+quat format)")
+
+    def _list_frames(self, config):
+        """the frame files in natural order"""
+        return sorted(os.listdir(config.pc_path), key=natural_key)
+
     def read_point_cloud(self, filename: str):
         """the raw points of a file on the device: [n,4] float32 (.bin) or [n,3] float64 (.ply)"""
         if ".bin" in filename:
@@ -472,6 +480,11 @@ class LiDARDataset:
         cfg = self.config
         raw = self.read_point_cloud(os.path.join(cfg.pc_path, self.pc_filenames[frame_id]))
         pts = frame_filter(raw, cfg.min_z, cfg.max_z, cfg.min_range, cfg.pc_radius)
+        return self._down_sample(pts, frame_id)
+
+    def _down_sample(self, pts, frame_id):
+        """stage 3: the filtered points of a frame -> the seeded random subset or the voxel means"""
+        cfg = self.config
         if pts.shape[0] == 0:
             raise ValueError("frame %d (%s): no point passes min_z / min_range / the crop box" % (frame_id, self.pc_filenames[frame_id]))
         if cfg.rand_downsample:

@@ -317,3 +317,135 @@ def semantic_labels(coord, weight, n_class=21, cell=0.02):
     h = (q[:, 0] * 73856093) ^ (q[:, 1] * 19349663) ^ (q[:, 2] * 83492791)
     lab = 1 + torch.remainder(h, n_class - 1)
     return torch.where(weight > 0, lab, torch.zeros_like(lab))
+
+
+# ---- a synthetic RGB-D drive (config/rgbd/*.yaml: Neural-RGBD / Replica rooms) ---------------------------------------------------
+PRESETS["rgbd"] = dict(tree_level_world=12, tree_level_feat=4, leaf_vox_size=0.02, sigma_sigmoid_m=0.02,
+                       surface_sample_range_m=0.05, surface_sample_n=3, free_sample_n=3, free_sample_begin_ratio=0.5,
+                       free_sample_end_dist_m=0.3, ekional_loss_on=False, weight_e=0.1, loss_reduction="mean",
+                       pc_radius_m=5.0, min_range_m=0.2, street_len=8.0, turns=0, lr=0.01)
+
+ROOM = dict(half_width=2.5, facade_h=3.0)  # the street canyon of cast_scan at the size of a room
+GROUND, FACADE, BOX, MISS = 0, 1, 2, 3  # what a pixel's ray meets first
+
+
+def room_boxes(length=8.0, n=8, seed=42):
+    """n axis-aligned boxes standing on the ground of a room `length` long -> (lo [n,3], hi [n,3]) float64 numpy"""
+    import numpy as np
+
+    g = torch.Generator().manual_seed(seed)
+    r = torch.rand((5, n), generator=g, dtype=torch.float64).numpy()
+    cx, cy = 1.0 + r[0] * (length - 2.0), (r[1] * 2 - 1) * 1.6
+    sx, sy, sz = 0.3 + 0.5 * r[2], 0.3 + 0.5 * r[3], 0.3 + 0.7 * r[4]
+    return np.stack((cx - sx / 2, cy - sy / 2, np.zeros(n)), 1), np.stack((cx + sx / 2, cy + sy / 2, sz), 1)
+
+
+def cast_depth(origin, dirs, lo, hi, half_width=ROOM["half_width"], facade_h=ROOM["facade_h"]):
+    """cast_scan's intersection maths per ray, in float64 numpy, WITHOUT its range cut: the ray parameter t of the first surface
+    along origin + t * dirs (inf: nothing is met) and which kind it is (GROUND / FACADE / BOX / MISS).  dirs need not be unit
+    vectors: with the pixel directions ((u - cx) / fx, (v - cy) / fy, 1) rotated into the world, t IS the z-depth."""
+    import numpy as np
+
+    o = np.asarray(origin, dtype=np.float64)
+    d = np.asarray(dirs, dtype=np.float64)
+    inf = np.full(d.shape[0], np.inf)
+    dz = d[:, 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.where(dz < -1e-6, -o[2] / dz, inf)
+        kind = np.where(np.isfinite(t), GROUND, MISS)
+        for sgn in (-1.0, 1.0):
+            dy = d[:, 1]
+            tf = np.where(dy * sgn > 1e-6, (sgn * half_width - o[1]) / dy, inf)
+            zf = o[2] + tf * dz
+            tf = np.where((zf >= 0) & (zf <= facade_h), tf, inf)
+            kind = np.where(tf < t, FACADE, kind)
+            t = np.minimum(t, tf)
+        inv = 1.0 / np.where(np.abs(d) < 1e-9, 1e-9, d)
+        t0 = (lo[None] - o[None, None]) * inv[:, None]
+        t1 = (hi[None] - o[None, None]) * inv[:, None]
+        tn = np.minimum(t0, t1).max(-1)
+        tx = np.maximum(t0, t1).min(-1)
+        tb = np.where((tx >= tn) & (tn > 0), tn, np.inf).min(-1)
+    kind = np.where(tb < t, BOX, kind)
+    return np.minimum(t, tb), kind
+
+
+def camera_pose(position, yaw, pitch_down):
+    """sensor-to-world pose [4,4] of a camera at `position` heading `yaw` (rad, about world z) and looking `pitch_down` rad below
+    the horizon.  The sensor frame is the converter's flipped camera frame (x right, y up, z backwards: dataset/
+    rgbd_to_kitti_format.py:42), so the camera looks along the sensor's -z."""
+    import numpy as np
+
+    fwd = np.array([math.cos(yaw) * math.cos(pitch_down), math.sin(yaw) * math.cos(pitch_down), -math.sin(pitch_down)])
+    right = np.array([math.sin(yaw), -math.cos(yaw), 0.0])
+    up = np.cross(right, fwd)
+    W = np.eye(4)
+    W[:3, 0], W[:3, 1], W[:3, 2], W[:3, 3] = right, up, -fwd, position
+    return W
+
+
+def write_rgbd_drive(folder, cfg=None, frames=6, width=160, height=120, focal=130.0, fmt="npy", seed=42, max_depth_m=5.0,
+                     max_range_m=8.0, depth_scale=1000.0, yaw_per_frame=0.12, pitch_down=0.35, step_m=0.25):
+    """Write a pinhole camera's pass through a room (ground, two facades, boxes: cast_depth) as an RGB-D folder in the Neural-RGBD
+    layout — depth/%06d.npy or .png (uint16 millimetres; 0 where the ray meets nothing or only beyond max_range_m, which lies
+    beyond max_depth_m so that some pixels carry a depth the reader must drop), focal.txt (one focal length; cx = (W - 1) / 2,
+    cy = (H - 1) / 2) and poses.txt (four lines per sensor-to-world matrix).  The camera advances step_m per frame, sways, and
+    turns by yaw_per_frame.  `cfg` is accepted for symmetry with write_kitti_drive (not read).  Returns a SimpleNamespace with
+    depth_path, intrinsic_path, pose_path, poses ([4,4] float64 as a reader of the file gets them), frames, width, height, focal,
+    depth_scale, max_depth_m, exact_depths ([H,W] float64 z-depths before rounding, inf = nothing met), kinds ([H,W] of GROUND /
+    FACADE / BOX / MISS), boxes (lo, hi) and the ROOM sizes."""
+    import os
+
+    import numpy as np
+
+    if fmt not in ("npy", "png"):
+        raise ValueError("write_rgbd_drive: fmt must be 'npy' or 'png'")
+    depth_path = os.path.join(folder, "depth")
+    os.makedirs(depth_path, exist_ok=True)
+    lo, hi = room_boxes(seed=seed)
+    cx, cy = (width - 1.0) / 2.0, (height - 1.0) / 2.0
+    u, v = np.meshgrid(np.arange(width, dtype=np.float64), np.arange(height, dtype=np.float64))
+    cam_dirs = np.stack(((u - cx) / focal, (v - cy) / focal, np.ones_like(u)), -1).reshape(-1, 3)
+    flipped = cam_dirs * np.array([1.0, -1.0, -1.0])  # the flip: camera frame -> sensor frame
+    poses, lines, exact, kinds = [], [], [], []
+    for f in range(frames):
+        W = camera_pose([0.4 + step_m * f, 0.3 * math.sin(0.4 * f), 1.2], -0.3 + yaw_per_frame * f, pitch_down)
+        text = "\n".join(" ".join(repr(float(x)) for x in row) for row in W)
+        W = np.array([[float(x) for x in row.split()] for row in text.split("\n")])  # (as a reader of the file gets it)
+        t, kind = cast_depth(W[:3, 3], flipped @ W[:3, :3].T, lo, hi)
+        raw = np.where(t < max_range_m, np.rint(t * depth_scale), 0.0).astype(np.uint16).reshape(height, width)
+        name = os.path.join(depth_path, "%06d.%s" % (f, fmt))
+        if fmt == "npy":
+            np.save(name, raw)
+        else:
+            from PIL import Image
+
+            Image.fromarray(raw).save(name)
+        poses.append(W)
+        lines.append(text)
+        exact.append(t.reshape(height, width))
+        kinds.append(kind.reshape(height, width))
+    intrinsic_path, pose_path = os.path.join(folder, "focal.txt"), os.path.join(folder, "poses.txt")
+    with open(intrinsic_path, "w") as fh:
+        fh.write(repr(float(focal)) + "\n")
+    with open(pose_path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    return SimpleNamespace(depth_path=depth_path, intrinsic_path=intrinsic_path, pose_path=pose_path, poses=poses, frames=frames,
+                           width=width, height=height, focal=float(focal), depth_scale=float(depth_scale),
+                           max_depth_m=float(max_depth_m), exact_depths=exact, kinds=kinds, boxes=(lo, hi), room=dict(ROOM))
+
+
+def rgbd_config(kind, drive, device="cuda", **over):
+    """dataset_config's sibling for RGBDDataset: make_config(kind) ("rgbd": the process / sampler / octree values of
+    config/rgbd/rgbd_batch.yaml) plus the fields RGBDDataset reads, pointed at a write_rgbd_drive folder"""
+    c = make_config(kind, device=device)
+    c.__dict__.update(
+        depth_path=drive.depth_path, intrinsic_path=drive.intrinsic_path, is_focal_file=True, pose_path=drive.pose_path,
+        pose_kitti_format=False, max_depth_m=drive.max_depth_m, first_frame_ref=False, begin_frame=0, end_frame=drive.frames - 1,
+        every_frame=1, seed=42, pc_count_gpu_limit=500, global_shift_default=0.0, min_range=c.min_range_m, pc_radius=c.pc_radius_m,
+        min_z=-10.0, max_z=30.0, rand_downsample=False, vox_down_m=0.01, rand_down_r=0.2, map_vox_down_m=0.05,
+        estimate_normal=False, filter_noise=False, semantic_on=False, behind_dropoff_on=False, octree_from_surface_samples=True,
+        clearance_dist_m=0.3, clearance_sample_n=0, continual_learning_reg=False, window_replay_on=False, window_radius=50.0,
+        ray_loss=False)
+    c.__dict__.update(over)
+    return c
