@@ -549,6 +549,28 @@ int shine_mesh_vertex_normals(const double* verts, int64_t n_verts, const int32_
 int shine_mesh_cluster_filter(const int32_t* faces, int64_t n_faces, int32_t min_tri, void* workspace, size_t* workspace_bytes,
                               int32_t* cluster_out, int32_t* faces_out, int64_t* kept_out, void* stream);
 
+/* ---- meshing a brick set (csrc/shine_mc_sparse.hip): marching cubes over n bricks of brick^3 values inside a
+ *      VIRTUAL grid [nx, ny, nz] that is never allocated; the result is bit for bit what _mc_count / _mc_emit give on the dense
+ *      grid that holds the bricks and is 0 (value and mask) everywhere else, in the same order.
+ *      values [n, brick, brick, brick] f32 (z fastest), mask the same shape u8 or NULL (then every cube whose lowest corner a
+ *      brick covers is processed); origins (HOST int64 [n, 3]) = each brick's lowest point: multiples of brick, inside the
+ *      grid, no two equal.  brick is 1..32; nx * ny * nz must be < 2^60 (it is an index space only); n < 2^31.  Bricks may
+ *      reach beyond the grid: what lies outside is ignored.  Everything above is checked on the host before a device is touched.
+ *      _mc_sparse_count: workspace == NULL returns the bytes needed (proportional to n * (brick + 1)^3) in *workspace_bytes.
+ *        Otherwise: brick table, classify, scan; counts_out (HOST int64[2]) = {R, F}: R vertex RECORDS (a vertex on a brick face
+ *        counts once per brick that uses it: V <= R) and F faces.  Synchronises the stream.  SHINE_E_INVALID if R or F >= 2^31.
+ *      _mc_sparse_emit: the same bricks, grid, level and workspace right after _mc_sparse_count, with its R and F.  scratch ==
+ *        NULL returns the bytes needed (proportional to R + F) in *scratch_bytes.  Otherwise verts_out (room for [R, 3] f32)
+ *        receives the V vertices, *n_verts_out (HOST) = V, faces_out [F, 3] int32.  Two radix sorts put both in the dense
+ *        order (vertices by owner point, then corner / +x / +y / +z; faces by cube, then table order): deterministic, no
+ *        atomic places an output.  Synchronises the stream. -------- */
+int shine_mc_sparse_count(const float* values, const uint8_t* mask, const int64_t* origins, int64_t n, int32_t brick, int64_t nx,
+                          int64_t ny, int64_t nz, float level, void* workspace, size_t* workspace_bytes, int64_t* counts_out,
+                          void* stream);
+int shine_mc_sparse_emit(const float* values, const uint8_t* mask, int64_t n, int32_t brick, int64_t nx, int64_t ny, int64_t nz,
+                         float level, void* workspace, size_t workspace_bytes, int64_t n_records, int64_t n_faces, void* scratch,
+                         size_t* scratch_bytes, float* verts_out, int32_t* faces_out, int64_t* n_verts_out, void* stream);
+
 /* ---- mesh evaluation: eval/eval_utils.py (eval_mesh, nn_correspondance, crop_intersection) on the device
  *      (csrc/shine_eval.hip; layout and rules in DESIGN.md 3.10).  All geometry is fp64; counts are int64 and < 2^31.
  *      Workspaces follow rocPRIM's convention: workspace == NULL returns the bytes needed in *workspace_bytes.

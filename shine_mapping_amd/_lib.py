@@ -187,6 +187,11 @@ _SIGNATURES = {
     "shine_mesh_vertex_normals": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.POINTER(C.c_size_t), _P, _P]),
     "shine_mesh_cluster_filter": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.POINTER(C.c_size_t), _P, _P, C.POINTER(C.c_int64),
                                             _P]),
+    # marching cubes over a brick set (csrc/shine_mc_sparse.hip)
+    "shine_mc_sparse_count": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                        C.c_float, _P, C.POINTER(C.c_size_t), C.POINTER(C.c_int64), _P]),
+    "shine_mc_sparse_emit": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_float, _P, C.c_size_t,
+                                       C.c_int64, C.c_int64, _P, C.POINTER(C.c_size_t), _P, _P, C.POINTER(C.c_int64), _P]),
     # mesh evaluation (csrc/shine_eval.hip)
     "shine_eval_fine_per_coarse": (C.c_int, []),
     "shine_eval_bounds": (C.c_int, [_P, C.c_int64, _P, C.POINTER(C.c_size_t), _P, _P]),

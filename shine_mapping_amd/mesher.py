@@ -12,6 +12,10 @@ arrays: the query writes straight into a dense device grid, `marching_cubes` (cs
 `compute_vertex_normals` / `filter_isolated_vertices` are csrc/shine_mesh.hip.  The rules the marching cubes follows (corner
 sign, vertex placement, degenerate faces, winding, output order) are in DESIGN.md "Meshing".  The mesh comes back as an
 open3d TriangleMesh when open3d can be imported, else as this module's `TriangleMesh`; the PLY writer is plain numpy.
+
+A map whose dense grid does not fit the device is meshed from BRICKS instead (`marching_cubes_sparse`, csrc/shine_mc_sparse.hip):
+only the node blocks (octree route) or the tiles near existing nodes (box route) are queried and kept, and the mesh is the dense
+route's bit for bit.  `recon_octree_mesh` / `recon_bbx_mesh` pick the route with their `sparse` keyword.
 """
 from __future__ import annotations
 
@@ -122,6 +126,137 @@ def marching_cubes(sdf, mask=None, level=0.0):
         _lib.check(lib.shine_mc_emit(sdf.data_ptr(), mp, X, Y, Z, float(level), ws.data_ptr(), need.value, verts.data_ptr(),
                                      faces.data_ptr(), st), "shine_mc_emit")
     return verts, faces
+
+
+MC_SPARSE_MAX_BRICK = 32  # csrc/shine_mc_sparse.hip: one workgroup stages a brick and its apron, (B + 1)^3 floats, in LDS
+BOX_BRICK = 8  # tile edge of the box route's bricks
+
+
+def marching_cubes_sparse(values, mask, origins, shape, level=0.0):
+    """Marching cubes of a brick set: `values [n,B,B,B]` (device f32), `mask` the same shape or None, `origins [n,3]` ints
+    (multiples of B inside the grid, no two equal), inside a virtual grid `shape = (X, Y, Z)` that is never allocated.  A point
+    no brick covers has value 0 and mask 0; with mask None every cube whose lowest corner a brick covers is processed.  Returns
+    what `marching_cubes` returns on that dense grid, bit for bit and in the same order: (verts [V,3] f32 index units of the
+    virtual grid, faces [F,3] int32)."""
+    if values.dim() != 4 or not values.is_cuda or not (values.shape[1] == values.shape[2] == values.shape[3]):
+        raise ValueError("marching_cubes_sparse: values must be a CUDA tensor [n, B, B, B], got %s on %s"
+                         % (tuple(values.shape), values.device))
+    values = values.detach().float().contiguous()
+    n, B = int(values.shape[0]), int(values.shape[1])
+    if mask is not None:
+        if tuple(mask.shape) != tuple(values.shape):
+            raise ValueError("marching_cubes_sparse: mask shape %s != values shape %s" % (tuple(mask.shape), tuple(values.shape)))
+        mask = mask.detach().to(device=values.device, dtype=torch.uint8).contiguous()
+    org = origins.detach().cpu().numpy() if torch.is_tensor(origins) else np.asarray(origins)
+    org = np.ascontiguousarray(org, dtype=np.int64).reshape(-1, 3)
+    if org.shape[0] != n:
+        raise ValueError("marching_cubes_sparse: %d origins for %d bricks" % (org.shape[0], n))
+    X, Y, Z = (int(v) for v in shape)
+    dev = values.device
+    verts = torch.empty((0, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((0, 3), dtype=torch.int32, device=dev)
+    lib, st = _lib.lib(), _stream()
+    vp, mp = (values.data_ptr() if n else None), (mask.data_ptr() if mask is not None and n else None)
+    op = org.ctypes.data_as(C.POINTER(C.c_int64))
+    need = C.c_size_t(0)
+    _lib.check(lib.shine_mc_sparse_count(vp, mp, op, n, B, X, Y, Z, float(level), None, C.byref(need), None, st),
+               "shine_mc_sparse_count")
+    if n == 0:
+        return verts, faces
+    ws = _ws(need.value, dev)
+    counts = (C.c_int64 * 2)()
+    rc = lib.shine_mc_sparse_count(vp, mp, op, n, B, X, Y, Z, float(level), ws.data_ptr(), C.byref(need), counts, st)
+    _lib.check(rc, "shine_mc_sparse_count (%d bricks of %d^3 in %dx%dx%d: %d vertex records, %d faces)"
+               % (n, B, X, Y, Z, counts[0], counts[1]))
+    nr, nf = int(counts[0]), int(counts[1])
+    if nr == 0 and nf == 0:
+        return verts, faces
+    sneed = C.c_size_t(0)
+    nv = C.c_int64(0)
+    _lib.check(lib.shine_mc_sparse_emit(vp, mp, n, B, X, Y, Z, float(level), ws.data_ptr(), need.value, nr, nf, None,
+                                        C.byref(sneed), None, None, C.byref(nv), st), "shine_mc_sparse_emit")
+    scratch = _ws(sneed.value, dev)
+    verts = torch.empty((nr, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+    _lib.check(lib.shine_mc_sparse_emit(vp, mp, n, B, X, Y, Z, float(level), ws.data_ptr(), need.value, nr, nf, scratch.data_ptr(),
+                                        C.byref(sneed), verts.data_ptr(), faces.data_ptr(), C.byref(nv), st),
+               "shine_mc_sparse_emit")
+    del scratch, ws
+    # (a vertex on a brick face has one record per brick that uses it: V <= records; the copy lets the larger buffer go)
+    return (verts if nv.value == nr else verts[:nv.value].clone()), faces
+
+
+def brick_edge(k):
+    """Brick edge for node blocks of k^3 points: k itself up to MC_SPARSE_MAX_BRICK, else its largest divisor that fits (each
+    block is then cut into (k / edge)^3 bricks)."""
+    k = int(k)
+    return max(b for b in range(1, min(k, MC_SPARSE_MAX_BRICK) + 1) if k % b == 0)
+
+
+def octree_brick_table(k, shift):
+    """Brick origins of octree_grid_layout's node blocks (`shift [M,3]`, multiples of k): (brick edge B, origins [M * q^3, 3]
+    int64 with q = k / B), block-major, a block's bricks in (x, y, z) order — the order split_blocks cuts the values in."""
+    B = brick_edge(k)
+    q = int(k) // B
+    ax = np.arange(q, dtype=np.int64) * B
+    off = np.stack(np.meshgrid(ax, ax, ax, indexing="ij"), -1).reshape(-1, 3)
+    shift = np.asarray(shift, dtype=np.int64).reshape(-1, 3)
+    return B, (shift[:, None, :] + off[None]).reshape(-1, 3)
+
+
+def split_blocks(t, B):
+    """[M, k, k, k] -> [M * q^3, B, B, B] (q = k / B), bricks in octree_brick_table's order"""
+    M, k = int(t.shape[0]), int(t.shape[1])
+    if B == k:
+        return t
+    q = k // B
+    return t.view(M, q, B, q, B, q, B).permute(0, 1, 3, 5, 2, 4, 6).reshape(M * q ** 3, B, B, B)
+
+
+def box_candidate_tiles(nodes, node_res_scaled, world_scale, voxel_origin, voxel_size, shape, B=BOX_BRICK):
+    """Tiles (B^3 points, tile coordinates [T,3] int64, sorted) of a box grid — point (i, j, l) at voxel_origin + (i, j, l) *
+    voxel_size metres — that may hold a point inside one of `nodes` (centres [M,3] in scaled coordinates, edge
+    node_res_scaled).  A superset: every node's index range is widened by one point per side, which covers the fp32 rounding of
+    get_query_from_bbx's coordinates (relative error 2^-22 on indices < 2^15)."""
+    shape = np.asarray(shape, dtype=np.int64)
+    nodes = np.asarray(nodes, dtype=np.float64).reshape(-1, 3)
+    ntile = (shape + B - 1) // B
+    if len(nodes) == 0 or (shape <= 0).any():
+        return np.zeros((0, 3), np.int64)
+    lo = ((nodes - 0.5 * node_res_scaled) / world_scale - np.asarray(voxel_origin, np.float64)) / voxel_size
+    hi = ((nodes + 0.5 * node_res_scaled) / world_scale - np.asarray(voxel_origin, np.float64)) / voxel_size
+    i0 = np.floor(lo).astype(np.int64) - 1
+    i1 = np.ceil(hi).astype(np.int64) + 1
+    keep = ((i1 >= 0) & (i0 <= shape - 1)).all(1)
+    i0, i1 = np.clip(i0[keep], 0, shape - 1), np.clip(i1[keep], 0, shape - 1)
+    if len(i0) == 0:
+        return np.zeros((0, 3), np.int64)
+    t0, t1 = i0 // B, i1 // B
+    span = int((t1 - t0).max()) + 1
+    ax = np.arange(span, dtype=np.int64)
+    off = np.stack(np.meshgrid(ax, ax, ax, indexing="ij"), -1).reshape(-1, 3)
+    keys = []
+    for o in off:  # (span is 1-3 for the shipped settings: a node is about as wide as a tile)
+        t = t0 + o
+        ok = (t <= t1).all(1)
+        t = t[ok]
+        keys.append((t[:, 0] * ntile[1] + t[:, 1]) * ntile[2] + t[:, 2])
+    keys = np.unique(np.concatenate(keys))
+    return np.stack((keys // (ntile[1] * ntile[2]), keys // ntile[2] % ntile[1], keys % ntile[2]), 1)
+
+
+def with_upper_neighbours(tiles, ntile):
+    """`tiles` plus their 7 neighbours towards +x / +y / +z inside the tile grid: the cubes on a tile's upper faces read those
+    tiles' values.  Sorted, unique."""
+    tiles = np.asarray(tiles, dtype=np.int64).reshape(-1, 3)
+    ntile = np.asarray(ntile, dtype=np.int64)
+    if len(tiles) == 0:
+        return tiles
+    off = np.stack(np.meshgrid([0, 1], [0, 1], [0, 1], indexing="ij"), -1).reshape(-1, 3)
+    t = (tiles[:, None, :] + off[None]).reshape(-1, 3)
+    t = t[(t < ntile).all(1)]
+    keys = np.unique((t[:, 0] * ntile[1] + t[:, 1]) * ntile[2] + t[:, 2])
+    return np.stack((keys // (ntile[1] * ntile[2]), keys // ntile[2] % ntile[1], keys % ntile[2]), 1)
 
 
 def vertex_normals_device(verts, faces):
@@ -468,10 +603,62 @@ class Mesher:
     def _check_level(self):
         return min(self.octree.featured_level_num, self.config.mc_vis_level) - 1
 
+    def _bbx_layout(self, bbx, voxel_size):
+        """get_query_from_bbx's grid without its points: (shape [3], voxel_origin [3] metres)"""
+        min_bound = np.asarray(bbx.get_min_bound(), dtype=np.float64).copy()
+        max_bound = np.asarray(bbx.get_max_bound(), dtype=np.float64)
+        shape = (np.ceil((max_bound - min_bound) / voxel_size) + self.config.pad_voxel * 2).astype(np.int_)
+        voxel_origin = min_bound - self.config.pad_voxel * voxel_size
+        voxel_origin[2] -= voxel_size
+        shape[2] += 1
+        return shape, voxel_origin
+
+    def bbx_bricks_device(self, bbx, voxel_size):
+        """recon_bbx_mesh's grid as bricks: the BOX_BRICK^3 tiles that may hold a point whose node exists at the mask's check
+        level (box_candidate_tiles) plus their upper neighbours, each queried at its own points with get_query_from_bbx's fp32
+        arithmetic — so every value a processed cube reads is the dense grid's, bit for bit.  Returns (values [n,B,B,B] f32, mask
+        [n,B,B,B] u8, origins [n,3] int64, shape, voxel_origin)."""
+        shape, voxel_origin = self._bbx_layout(bbx, voxel_size)
+        B = BOX_BRICK
+        dev = self.octree.hier_features[0].device
+        check_level = self._check_level()
+        level = self.octree.max_level - check_level
+        node_res_scaled = 2 ** (1 - level)
+        tiles = box_candidate_tiles(self.octree.get_octree_nodes(level), node_res_scaled, self.world_scale, voxel_origin, voxel_size,
+                                    shape, B)
+        tiles = with_upper_neighbours(tiles, (np.asarray(shape, np.int64) + B - 1) // B)
+        origins = tiles * B
+        n = len(origins)
+        values = torch.empty((n, B, B, B), dtype=torch.float32, device=dev)
+        mask = torch.zeros((n, B, B, B), dtype=torch.uint8, device=dev)
+        ax = torch.arange(B, dtype=torch.int64, device=dev)
+        gx, gy, gz = torch.meshgrid(ax, ax, ax, indexing="ij")
+        local = torch.stack((gx.flatten(), gy.flatten(), gz.flatten()), 1)
+        org_dev = torch.as_tensor(origins, device=dev)
+        top = torch.as_tensor(np.asarray(shape, np.int64) - 1, device=dev)
+        origin_t = torch.tensor(voxel_origin, dtype=self.dtype, device=dev)
+        per = max(1, QUERY_CHUNK // (B ** 3))
+        with torch.no_grad():
+            for h in range(0, n, per):
+                t = min(h + per, n)
+                # (points of a tile beyond the grid are never read: they are queried at the grid's last point)
+                idx = torch.minimum(org_dev[h:t, None, :] + local[None], top).reshape(-1, 3)
+                coord = idx.float()  # get_query_from_bbx: int16 indices -> float32, * voxel_size, + origin, * world_scale
+                coord *= voxel_size
+                coord += origin_t
+                coord *= self.world_scale
+                s, m = query_points_device(self.octree, self.geo_decoder, coord, check_level, True, True, True)
+                values[h:t] = s.view(-1, B, B, B)
+                mask[h:t] = m.view(-1, B, B, B)
+        return values, mask, origins, tuple(int(v) for v in shape), voxel_origin
+
     def recon_bbx_mesh(self, bbx, voxel_size, mesh_path, map_path, save_map=False, estimate_sem=False, estimate_normal=True,
-                       filter_isolated_mesh=True, filter_free_space_vertices=True):
+                       filter_isolated_mesh=True, filter_free_space_vertices=True, sparse=None):
         """utils/mesher.py:253-292 on the device: grid query -> marching cubes -> [semantics] -> [normals] -> [filter with
-        config.min_cluster_vertices] -> global_transform -> PLY."""
+        config.min_cluster_vertices] -> global_transform -> PLY.  `sparse`: False = the dense grid (MemoryError when it does
+        not fit), True = bricks (bbx_bricks_device + marching_cubes_sparse: the same mesh, memory proportional to the tiles
+        near the map's nodes), None = dense when it fits, else bricks.  The brick route needs config.mc_mask_on and cannot
+        save the SDF map."""
         if getattr(self.config, "time_conditioned", False):
             raise NotImplementedError("time-conditioned decoding is outside the SDF hot path")
         min_bound = np.asarray(bbx.get_min_bound(), dtype=np.float64)
@@ -479,6 +666,23 @@ class Mesher:
         shape = (np.ceil((max_bound - min_bound) / voxel_size) + self.config.pad_voxel * 2).astype(np.int_)
         shape[2] += 1
         mask_on = bool(getattr(self.config, "mc_mask_on", True))
+        if sparse and not mask_on:
+            raise ValueError("recon_bbx_mesh: sparse=True needs config.mc_mask_on (without the mask every cube of the box is "
+                             "processed, so no tile can be left out)")
+        if sparse is None and mask_on:
+            try:
+                ensure_grid_fits(shape, mask_on, per_point_extra=12 + 6, device=self.octree.hier_features[0].device)
+            except MemoryError:
+                sparse = True
+        if sparse:
+            if save_map:
+                raise ValueError("recon_bbx_mesh: save_map=True cannot be combined with the brick route (sparse=True, or a box "
+                                 "whose dense grid does not fit): there is no sparse SDF map")
+            values, mask, origins, bshape, voxel_origin = self.bbx_bricks_device(bbx, voxel_size)
+            verts, faces = marching_cubes_sparse(values, mask, origins, bshape, 0.0)
+            del values, mask
+            return self._finish(verts, faces, voxel_size, voxel_origin, mesh_path, estimate_sem, estimate_normal,
+                                filter_isolated_mesh, filter_free_space_vertices, getattr(self.config, "min_cluster_vertices", 300))
         ensure_grid_fits(shape, mask_on, per_point_extra=12 + 6, device=self.octree.hier_features[0].device)  # (+ the query
         #                                                                            coordinates and get_query_from_bbx's int16 axes)
         coord, voxel_num_xyz, voxel_origin = self.get_query_from_bbx(bbx, voxel_size)
@@ -544,12 +748,57 @@ class Mesher:
         origin = (np.min(nodes, 0) - 0.5 * (node_res_scaled - mc_res_scaled)) / self.world_scale
         return sdf.view(X, Y, Z), mask.view(X, Y, Z), voxel, origin
 
+    def octree_bricks_device(self, query_level, mc_res_m):
+        """octree_grid_device's grid as bricks: every node block queried exactly as there (the same coordinates, .half().float()
+        rounding, mc_mask_on handling and chunking) and KEPT as a brick instead of being scattered into a dense grid, which is
+        never allocated.  Blocks wider than MC_SPARSE_MAX_BRICK are cut into bricks of brick_edge(k).  Returns (values
+        [n,B,B,B] f32, mask [n,B,B,B] u8, origins [n,3] int64, shape, voxel size m, origin m)."""
+        nodes, node_res_scaled, k, mc_res_scaled, shape, shift = self.octree_grid_layout(query_level, mc_res_m)
+        dev = self.octree.hier_features[0].device
+        B, brick_origins = octree_brick_table(k, shift)
+        M = len(nodes)
+        ax = torch.arange(k, dtype=torch.int16, device=dev)
+        gx, gy, gz = torch.meshgrid(ax, ax, ax, indexing="ij")
+        block = torch.stack((gx.flatten(), gy.flatten(), gz.flatten())).transpose(0, 1).float()
+        block *= mc_res_scaled
+        block64 = block.double()
+        origins = torch.as_tensor(nodes - 0.5 * (node_res_scaled - mc_res_scaled), dtype=torch.float64, device=dev)
+        values = torch.empty((M, k, k, k), dtype=torch.float32, device=dev)
+        mask = torch.zeros((M, k, k, k), dtype=torch.uint8, device=dev)
+        mask_on = bool(getattr(self.config, "mc_mask_on", True))
+        check_level = self._check_level()
+        per = max(1, QUERY_CHUNK // (k ** 3))
+        with torch.no_grad():
+            for h in range(0, M, per):
+                t = min(h + per, M)
+                coord = (block64[None] + origins[h:t, None, :]).float().reshape(-1, 3)
+                s, m = query_points_device(self.octree, self.geo_decoder, coord, check_level, True, True, mask_on)
+                values[h:t] = s.half().float().view(-1, k, k, k)
+                if mask_on:
+                    mask[h:t] = m.view(-1, k, k, k)
+        voxel = mc_res_scaled / self.world_scale
+        origin = (np.min(nodes, 0) - 0.5 * (node_res_scaled - mc_res_scaled)) / self.world_scale
+        return split_blocks(values, B), split_blocks(mask, B), brick_origins, tuple(int(v) for v in shape), voxel, origin
+
     def recon_octree_mesh(self, query_level, mc_res_m, mesh_path, map_path, save_map=False, estimate_sem=False,
-                          estimate_normal=True, filter_isolated_mesh=True, filter_free_space_vertices=True):
+                          estimate_normal=True, filter_isolated_mesh=True, filter_free_space_vertices=True, sparse=None):
         """utils/mesher.py:294-367 on the device (the reference's save_map is commented out there, :342-344, and ignored here
-        too; its cluster filter uses the default 300 triangles, :356)."""
+        too; its cluster filter uses the default 300 triangles, :356).  `sparse`: False = the dense grid over the nodes'
+        bounding box (MemoryError when it does not fit), True = the node blocks as bricks (octree_bricks_device +
+        marching_cubes_sparse: the same mesh, memory proportional to the nodes), None = dense when it fits, else bricks."""
         if getattr(self.config, "time_conditioned", False):
             raise NotImplementedError("time-conditioned decoding is outside the SDF hot path")
+        if sparse is None:
+            try:
+                ensure_grid_fits(self.octree_grid_layout(query_level, mc_res_m)[4], True, device=self.octree.hier_features[0].device)
+            except MemoryError:
+                sparse = True
+        if sparse:
+            values, mask, origins, shape, voxel, origin = self.octree_bricks_device(query_level, mc_res_m)
+            verts, faces = marching_cubes_sparse(values, mask, origins, shape, 0.0)
+            del values, mask
+            return self._finish(verts, faces, voxel, origin, mesh_path, estimate_sem, estimate_normal, filter_isolated_mesh,
+                                filter_free_space_vertices, 300)
         sdf, mask, voxel, origin = self.octree_grid_device(query_level, mc_res_m)
         verts, faces = marching_cubes(sdf, mask, 0.0)
         del sdf, mask
