@@ -584,6 +584,9 @@ int shine_mc_sparse_emit(const float* values, const uint8_t* mask, int64_t n, in
  *      _voxel_down: one point per occupied voxel = the mean of its points, ascending key (ix << 42 | iy << 21 | iz) with
  *        i = floor((p - origin) / voxel) (HOST origin[3]; the caller guarantees 0 <= i < 2^21).  points_out / keys_out (may be
  *        NULL) have room for n rows; *n_out (HOST) = rows written (synchronises).  Bit-identical from run to run.
+ *      shine_voxel_down_attr: _voxel_down with n_attr (1..4) fp64 attribute columns carried along (attrs [n, n_attr]): keys, output
+ *        order and point means are _voxel_down's bits; attrs_out [v][a] = (sum of attrs[i][a] over the voxel's points in input
+ *        order) / count, in fp64 — the order open3d's voxel_down_sample accumulates colours in.  attrs_out has room for n rows.
  *      _grid_count: sorts the reference points by cell (edge `cell`, HOST origin[3], indices < 2^21 guaranteed by the caller);
  *        counts_out (HOST int64[2]) = {occupied fine cells, occupied coarse cells} (synchronises).
  *      _grid_emit: right after _grid_count with its workspace: writes the search grid into `grid` (grid == NULL: its size).
@@ -603,6 +606,9 @@ int shine_eval_sample_mesh(const double* verts, int64_t n_verts, const int32_t* 
                            int32_t* tri_out, void* stream);
 int shine_eval_voxel_down(const double* points, int64_t n, const double* origin, double voxel, void* workspace,
                           size_t* workspace_bytes, double* points_out, uint64_t* keys_out, int64_t* n_out, void* stream);
+int shine_voxel_down_attr(const double* points, const double* attrs, int32_t n_attr, int64_t n, const double* origin, double voxel,
+                          void* workspace, size_t* workspace_bytes, double* points_out, double* attrs_out, uint64_t* keys_out,
+                          int64_t* n_out, void* stream);
 int shine_eval_grid_count(const double* ref, int64_t n, const double* origin, double cell, void* workspace,
                           size_t* workspace_bytes, int64_t* counts_out, void* stream);
 int shine_eval_grid_emit(const double* ref, int64_t n, const void* workspace, size_t workspace_bytes, int64_t n_fine,
@@ -621,6 +627,13 @@ int shine_eval_metrics(const double* dist_p, int64_t n_p, const double* dist_r, 
  *        |p| >= min_range, -pc_radius <= x, y <= pc_radius and min_z <= z <= max_z (all inclusive but the first; fp64, no
  *        fused multiply-add, so the kept set equals numpy's).  points: n rows of `stride` (3 or 4) float32 elements, or fp64
  *        with is_fp64 != 0; points_out [n][3] fp64 has room for every row; *n_out (HOST) = rows kept (synchronises).
+ *      _sem_frame_filter: _frame_filter's sibling for a labelled scan (preprocess_sem_kitti, dataset/lidar_dataset.py:341-362, then
+ *        the crop box), ONE launch.  labels [n] uint32 (DEVICE), lut DEVICE int32[65536]: raw 16-bit id -> class, < 0 = unknown.
+ *        Per point s = label & 0xFFFF, r = sqrt(x*x + y*y + z*z) (fp64, no fused multiply-add),
+ *          pass = r >= range_min && (!filter_moving || s < 100) && (!filter_outlier || s != 1)
+ *          keep = pass && |x|, |y| <= pc_radius && min_z <= z <= max_z                 (all inclusive: open3d's crop)
+ *        points_out [n][3] fp64 and class_out [n] int32 (= lut[s]) receive the kept points in input order; *n_out (HOST) = rows
+ *        kept, *n_unknown_out (HOST) = points with pass && lut[s] < 0, cropped or not (synchronises).
  *      _ray_sample: ONE launch, no workspace.  points [m][3] fp32 in the scaled space, origin HOST float[3]; per ray surface_n
  *        samples with label uniform in [-surface_range, surface_range), clearance_n with label in (-surface_range -
  *        clearance_dist, -surface_range], free_n with ratio uniform in [free_begin_ratio, free_end_dist / dist + 1]; all
@@ -658,6 +671,10 @@ int shine_depth_unproject(const void* depth, int32_t is_float32, int32_t width, 
 int shine_frame_filter(const void* points, int64_t n, int32_t is_fp64, int32_t stride, double min_z, double max_z,
                        double min_range, double pc_radius, void* workspace, size_t* workspace_bytes, double* points_out,
                        int64_t* n_out, void* stream);
+int shine_sem_frame_filter(const void* points, int64_t n, int32_t is_fp64, int32_t stride, const uint32_t* labels,
+                           const int32_t* lut, double range_min, int32_t filter_moving, int32_t filter_outlier, double min_z,
+                           double max_z, double pc_radius, void* workspace, size_t* workspace_bytes, double* points_out,
+                           int32_t* class_out, int64_t* n_out, int64_t* n_unknown_out, void* stream);
 int shine_ray_sample(const float* points, int64_t m, const float* origin, int32_t surface_n, int32_t clearance_n, int32_t free_n,
                      float surface_range, float clearance_dist, float free_begin_ratio, float free_end_dist, float scale,
                      const int32_t* labels, uint64_t seed, uint64_t stream_id, const float* uniforms, float time_value,

@@ -200,6 +200,8 @@ _SIGNATURES = {
                                          _P, _P, _P]),
     "shine_eval_voxel_down": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_double), C.c_double, _P, C.POINTER(C.c_size_t), _P, _P,
                                         C.POINTER(C.c_int64), _P]),
+    "shine_voxel_down_attr": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_double), C.c_double, _P, C.POINTER(C.c_size_t),
+                                        _P, _P, _P, C.POINTER(C.c_int64), _P]),
     "shine_eval_grid_count": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_double), C.c_double, _P, C.POINTER(C.c_size_t),
                                         C.POINTER(C.c_int64), _P]),
     "shine_eval_grid_emit": (C.c_int, [_P, C.c_int64, _P, C.c_size_t, C.c_int64, C.c_int64, _P, C.POINTER(C.c_size_t), _P]),
@@ -210,6 +212,9 @@ _SIGNATURES = {
     # the frame front-end (csrc/shine_frame.hip)
     "shine_frame_filter": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, _P,
                                      C.POINTER(C.c_size_t), _P, C.POINTER(C.c_int64), _P]),
+    "shine_sem_frame_filter": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_double, C.c_int32, C.c_int32, C.c_double,
+                                         C.c_double, C.c_double, _P, C.POINTER(C.c_size_t), _P, _P, C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int64), _P]),
     "shine_depth_unproject": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int64] + [C.c_double] * 6
                               + [C.POINTER(C.c_double)] + [C.c_double] * 4
                               + [_P, C.POINTER(C.c_size_t), _P, _P, C.POINTER(C.c_int64), _P]),

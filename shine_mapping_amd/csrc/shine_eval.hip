@@ -236,6 +236,41 @@ __global__ void k_voxel_mean(const double* __restrict__ p, const unsigned long l
   if (keys_out) keys_out[o] = keys[j];
 }
 
+constexpr int MAX_ATTR = 4;
+
+// k_voxel_mean with n_attr (1..MAX_ATTR) fp64 attribute columns carried along: the same point sums in the same order (the point
+// means are k_voxel_mean's bits), and per column the sum over the run in the caller's point order, divided by the count
+__global__ void k_voxel_mean_attr(const double* __restrict__ p, const double* __restrict__ attrs, int n_attr,
+                                  const unsigned long long* __restrict__ keys, const unsigned long long* __restrict__ vals,
+                                  const unsigned char* __restrict__ flags, const int* __restrict__ rank, long long n,
+                                  double* __restrict__ out, double* __restrict__ attrs_out,
+                                  unsigned long long* __restrict__ keys_out) {
+  const long long j = (long long)blockIdx.x * T + threadIdx.x;
+  if (j >= n || !flags[j]) return;
+  double x = 0.0, y = 0.0, z = 0.0;
+  double a[MAX_ATTR] = {0.0, 0.0, 0.0, 0.0};
+  long long e = j;
+  do {
+    const long long i = (long long)vals[e];
+    x += p[3 * i];
+    y += p[3 * i + 1];
+    z += p[3 * i + 2];
+#pragma unroll
+    for (int k = 0; k < MAX_ATTR; ++k)
+      if (k < n_attr) a[k] += attrs[i * n_attr + k];
+    ++e;
+  } while (e < n && !flags[e]);
+  const double c = (double)(e - j);
+  const long long o = rank[j];
+  out[3 * o] = x / c;
+  out[3 * o + 1] = y / c;
+  out[3 * o + 2] = z / c;
+#pragma unroll
+  for (int k = 0; k < MAX_ATTR; ++k)
+    if (k < n_attr) attrs_out[o * n_attr + k] = a[k] / c;
+  if (keys_out) keys_out[o] = keys[j];
+}
+
 // ---------------------------------------------------------------- nearest neighbour: the grid
 // sort key of a fine cell (ix, iy, iz): the coarse cell (ix >> 2, ...) in bits 6.., the fine cell inside it in bits 0..5
 __device__ __forceinline__ unsigned long long grid_key(unsigned long long ix, unsigned long long iy, unsigned long long iz) {
@@ -564,6 +599,18 @@ int run_count(const int* rank, const unsigned char* flags, long long n, hipStrea
     SHINE_HIP_CHECK(hipGetLastError());                                                       \
   } while (0)
 
+// the front of both voxel down-samplers: keys, the stable sort of (key, index), run flags and run ranks
+int voxel_runs(const GridScratch& s, const double* points, long long nn, const double* origin, double voxel, hipStream_t st) {
+  const Vec3 o{origin[0], origin[1], origin[2]};
+  LAUNCH(k_voxel_keys, nn, points, nn, o, voxel, s.k0, s.v0);
+  size_t tb = s.tmp_bytes;
+  SHINE_HIP_CHECK(shine::prim_sort_pairs_u64(s.tmp, tb, s.k0, s.k1, s.v0, s.v1, (size_t)nn, 0u, 63u, st));
+  LAUNCH(k_run_flags, nn, (const unsigned long long*)s.k1, nn, 0, s.fflag);
+  tb = s.tmp_bytes;
+  SHINE_HIP_CHECK(shine::prim_scan_flags(s.tmp, tb, s.fflag, s.frank, (size_t)nn, st));
+  return SHINE_OK;
+}
+
 }  // namespace
 
 extern "C" int shine_eval_fine_per_coarse(void) { return FINE_PER_COARSE; }
@@ -647,17 +694,38 @@ extern "C" int shine_eval_voxel_down(const double* points, int64_t n, const doub
   *n_out = 0;
   if (n == 0) return SHINE_OK;
   if (!points || !points_out) return shine::set_error(SHINE_E_INVALID, "shine_eval_voxel_down: null argument");
-  const Vec3 o{origin[0], origin[1], origin[2]};
   const long long nn = n;
-  LAUNCH(k_voxel_keys, nn, points, nn, o, voxel, s.k0, s.v0);
-  size_t tb = s.tmp_bytes;
-  SHINE_HIP_CHECK(shine::prim_sort_pairs_u64(s.tmp, tb, s.k0, s.k1, s.v0, s.v1, (size_t)nn, 0u, 63u, st));
-  LAUNCH(k_run_flags, nn, (const unsigned long long*)s.k1, nn, 0, s.fflag);
-  tb = s.tmp_bytes;
-  SHINE_HIP_CHECK(shine::prim_scan_flags(s.tmp, tb, s.fflag, s.frank, (size_t)nn, st));
+  if (int rc = voxel_runs(s, points, nn, origin, voxel, st)) return rc;
   // points_out has room for n rows (the caller cuts it to *n_out)
   LAUNCH(k_voxel_mean, nn, points, (const unsigned long long*)s.k1, (const unsigned long long*)s.v1,
          (const unsigned char*)s.fflag, (const int*)s.frank, nn, points_out, (unsigned long long*)keys_out);
+  return run_count(s.frank, s.fflag, nn, st, n_out);
+}
+
+extern "C" int shine_voxel_down_attr(const double* points, const double* attrs, int32_t n_attr, int64_t n, const double* origin,
+                                     double voxel, void* workspace, size_t* workspace_bytes, double* points_out,
+                                     double* attrs_out, uint64_t* keys_out, int64_t* n_out, void* stream) {
+  if (!workspace_bytes || bad_count(n)) return shine::set_error(SHINE_E_INVALID, "shine_voxel_down_attr: bad size (n must be < 2^31)");
+  if (n_attr < 1 || n_attr > MAX_ATTR) return shine::set_error(SHINE_E_INVALID, "shine_voxel_down_attr: n_attr must be 1..4");
+  // (the checks that are host arithmetic come first: the scratch size below is rocPRIM's answer for the current device)
+  if (workspace && (!n_out || !origin || !(voxel > 0.0)))
+    return shine::set_error(SHINE_E_INVALID, "shine_voxel_down_attr: null argument or voxel <= 0");
+  if (workspace && n > 0 && (!points || !attrs || !points_out || !attrs_out))
+    return shine::set_error(SHINE_E_INVALID, "shine_voxel_down_attr: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  GridScratch s;
+  if (int rc = grid_scratch(workspace, n, st, &s)) return rc;
+  if (!workspace) {
+    *workspace_bytes = s.bytes;
+    return SHINE_OK;
+  }
+  if (*workspace_bytes < s.bytes) return shine::set_error(SHINE_E_INVALID, "shine_voxel_down_attr: workspace too small");
+  *n_out = 0;
+  if (n == 0) return SHINE_OK;
+  const long long nn = n;
+  if (int rc = voxel_runs(s, points, nn, origin, voxel, st)) return rc;  // (shine_eval_voxel_down's keys, in its order)
+  LAUNCH(k_voxel_mean_attr, nn, points, attrs, (int)n_attr, (const unsigned long long*)s.k1, (const unsigned long long*)s.v1,
+         (const unsigned char*)s.fflag, (const int*)s.frank, nn, points_out, attrs_out, (unsigned long long*)keys_out);
   return run_count(s.frank, s.fflag, nn, st, n_out);
 }
 

@@ -1,13 +1,15 @@
 // shine_frame.hip — the frame front-end of LiDARDataset.process_frame (dataset/lidar_dataset.py:115-290, utils/data_sampler.py:18-139)
 // on the device: what turns one scan and one pose into training samples.
 //   shine_frame_filter        preprocess_kitti (z > min_z, |p| >= min_range) + the inclusive crop box, fp64, compacted in input order
+//   shine_sem_frame_filter    preprocess_sem_kitti (|p| >= range_min, label < 100, label != 1) + the learning map + the inclusive crop
+//                             box, fp64, points and classes compacted in input order, ONE launch
 //   shine_depth_unproject     a depth image (uint16 / float32) -> the frame's points: back-projection through the pinhole intrinsics
 //                             (dataset/rgbd_to_kitti_format.py:78-81), the camera-to-sensor matrix and shine_frame_filter's test,
 //                             compacted in pixel order, ONE launch
 //   shine_ray_sample          dataSampler.sample: surface / clearance / free-space samples of every ray, ONE launch, ray-major
 //   shine_pool_window_filter  the sliding window of the batch-mode pool (|coord - origin| < radius), stable, <= 6 parallel arrays
-// All four are streaming kernels: the sampler writes 4-byte words lane-contiguously (the [*,3] rows go through LDS so that its
-// stores are dword-linear too) and has no atomics; the three compactions order their tiles through one chained prefix
+// All five are streaming kernels: the sampler writes 4-byte words lane-contiguously (the [*,3] rows go through LDS so that its
+// stores are dword-linear too) and has no atomics; the four compactions order their tiles through one chained prefix
 // (tile_exclusive_prefix) instead of a scan launch, so the input is read once.
 #include "shine_internal.hpp"
 
@@ -141,6 +143,68 @@ __global__ __launch_bounds__(T) void k_frame_filter(const P* __restrict__ pts, i
       o[0] = x[k];
       o[1] = y[k];
       o[2] = z[k];
+    }
+  if (tile == n_tiles - 1 && threadIdx.x == 0) *total = excl + count;
+}
+
+// ---- shine_sem_frame_filter ----------------------------------------------------------------------------------------------------
+// k_frame_filter's sibling for a labelled scan (dataset/lidar_dataset.py:341-362, then the crop of :138-142): the label test runs on
+// the raw 16-bit id, the kept points carry lut[id].  `unknown` counts the points that pass the label test with an id the map does
+// not hold (the reference raises KeyError for those before it crops): one atomic per wave that saw any.
+struct SemFilter {
+  double range_min, min_z, max_z, radius;
+  int filter_moving, filter_outlier;
+};
+
+template <typename P>
+__global__ __launch_bounds__(T) void k_sem_frame_filter(const P* __restrict__ pts, int stride,
+                                                        const unsigned int* __restrict__ labels, const int* __restrict__ lut,
+                                                        long long n, SemFilter f, double* __restrict__ out,
+                                                        int* __restrict__ class_out, unsigned long long* state,
+                                                        unsigned int* counter, long long* total, unsigned long long* unknown,
+                                                        int n_tiles) {
+#pragma clang fp contract(off)  // (as k_frame_filter: the kept set is compared exactly with numpy's)
+  __shared__ TileShared sm;
+  const int tile = take_ticket(sm, counter);
+  const long long base = (long long)tile * (FI * T);
+  double x[FI], y[FI], z[FI];
+  int cls[FI];
+  bool keep[FI];
+  int rank[FI];
+  int n_unknown = 0;
+#pragma unroll
+  for (int k = 0; k < FI; ++k) {
+    const long long i = base + k * T + threadIdx.x;
+    keep[k] = false;
+    cls[k] = 0;
+    if (i < n) {
+      x[k] = (double)pts[i * stride];
+      y[k] = (double)pts[i * stride + 1];
+      z[k] = (double)pts[i * stride + 2];
+      const unsigned int s = labels[i] & 0xFFFFu;
+      const double r = __dsqrt_rn(x[k] * x[k] + y[k] * y[k] + z[k] * z[k]);
+      const bool pass = r >= f.range_min && (!f.filter_moving || s < 100u) && (!f.filter_outlier || s != 1u);
+      if (pass) {
+        cls[k] = lut[s];
+        n_unknown += cls[k] < 0 ? 1 : 0;
+      }
+      keep[k] = pass && x[k] >= -f.radius && x[k] <= f.radius && y[k] >= -f.radius && y[k] <= f.radius && z[k] >= f.min_z &&
+                z[k] <= f.max_z;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n_unknown += __shfl_xor(n_unknown, o, 64);
+  if ((threadIdx.x & 63) == 0 && n_unknown > 0) atomicAdd(unknown, (unsigned long long)n_unknown);
+  const int count = tile_ranks<FI>(sm, keep, rank);
+  const long long excl = tile_exclusive_prefix(sm, state, tile, count);
+#pragma unroll
+  for (int k = 0; k < FI; ++k)
+    if (keep[k]) {
+      double* o = out + (excl + rank[k]) * 3;
+      o[0] = x[k];
+      o[1] = y[k];
+      o[2] = z[k];
+      class_out[excl + rank[k]] = cls[k];
     }
   if (tile == n_tiles - 1 && threadIdx.x == 0) *total = excl + count;
 }
@@ -428,10 +492,11 @@ struct Carve {
 
 constexpr long long MAX_ROWS = (1ll << 31) - 1;  // (the tile ranks and the tile count are ints)
 
-// the chained prefix's scratch: {counter, total} in one 256-byte slot, then one state word per tile
+// the chained prefix's scratch: {counter, total, a second count} in one 256-byte slot, then one state word per tile
 struct ChainScratch {
   unsigned int* counter;
   long long* total;
+  unsigned long long* extra;  // (shine_sem_frame_filter's unknown-id count: bytes 16..23, next to total so that one copy fetches both)
   unsigned long long* state;
   size_t clear_bytes;
 };
@@ -440,6 +505,7 @@ ChainScratch carve_chain(Carve& c, long long n_tiles) {
   char* head = (char*)c.take(256);
   s.counter = (unsigned int*)head;
   s.total = (long long*)(head ? head + 8 : nullptr);
+  s.extra = (unsigned long long*)(head ? head + 16 : nullptr);
   s.state = (unsigned long long*)c.take((size_t)(n_tiles > 0 ? n_tiles : 1) * 8);
   s.clear_bytes = 256 + (((size_t)(n_tiles > 0 ? n_tiles : 1) * 8 + 255) & ~(size_t)255);
   return s;
@@ -484,6 +550,51 @@ extern "C" int shine_frame_filter(const void* points, int64_t n, int32_t is_fp64
   SHINE_HIP_CHECK(hipMemcpyAsync(&total, s.total, 8, hipMemcpyDeviceToHost, st));
   SHINE_HIP_CHECK(hipStreamSynchronize(st));
   *n_out = total;
+  return SHINE_OK;
+}
+
+extern "C" int shine_sem_frame_filter(const void* points, int64_t n, int32_t is_fp64, int32_t stride, const uint32_t* labels,
+                                      const int32_t* lut, double range_min, int32_t filter_moving, int32_t filter_outlier,
+                                      double min_z, double max_z, double pc_radius, void* workspace, size_t* workspace_bytes,
+                                      double* points_out, int32_t* class_out, int64_t* n_out, int64_t* n_unknown_out,
+                                      void* stream) {
+  if (!workspace_bytes || n < 0 || n > MAX_ROWS)
+    return set_error(SHINE_E_INVALID, "shine_sem_frame_filter: bad size (0 <= n < 2^31, workspace_bytes required)");
+  if (stride != 3 && stride != 4)
+    return set_error(SHINE_E_INVALID, "shine_sem_frame_filter: stride must be 3 or 4 elements per point");
+  const long long n_tiles = (n + FI * T - 1) / (FI * T);
+  Carve c{(char*)workspace};
+  ChainScratch s = carve_chain(c, n_tiles);
+  if (!workspace) {
+    *workspace_bytes = c.off;
+    return SHINE_OK;
+  }
+  if (*workspace_bytes < c.off) return set_error(SHINE_E_INVALID, "shine_sem_frame_filter: workspace too small");
+  if (!n_out || !n_unknown_out) return set_error(SHINE_E_INVALID, "shine_sem_frame_filter: null n_out or n_unknown_out");
+  if (!(pc_radius >= 0.0) || !(max_z >= min_z) || range_min != range_min)
+    return set_error(SHINE_E_INVALID, "shine_sem_frame_filter: pc_radius < 0, max_z < min_z or a NaN bound");
+  *n_out = 0;
+  *n_unknown_out = 0;
+  if (n == 0) return SHINE_OK;
+  if (!points || !labels || !lut || !points_out || !class_out)
+    return set_error(SHINE_E_INVALID, "shine_sem_frame_filter: null points, labels, lut, points_out or class_out");
+  hipStream_t st = (hipStream_t)stream;
+  SHINE_HIP_CHECK(hipMemsetAsync(s.counter, 0, s.clear_bytes, st));
+  const SemFilter f{range_min, min_z, max_z, pc_radius, filter_moving != 0, filter_outlier != 0};
+  if (is_fp64)
+    hipLaunchKernelGGL(k_sem_frame_filter<double>, dim3((unsigned)n_tiles), dim3(T), 0, st, (const double*)points, (int)stride,
+                       (const unsigned int*)labels, (const int*)lut, (long long)n, f, points_out, (int*)class_out, s.state,
+                       s.counter, s.total, s.extra, (int)n_tiles);
+  else
+    hipLaunchKernelGGL(k_sem_frame_filter<float>, dim3((unsigned)n_tiles), dim3(T), 0, st, (const float*)points, (int)stride,
+                       (const unsigned int*)labels, (const int*)lut, (long long)n, f, points_out, (int*)class_out, s.state,
+                       s.counter, s.total, s.extra, (int)n_tiles);
+  SHINE_HIP_CHECK(hipGetLastError());
+  long long both[2] = {0, 0};  // {total, unknown}
+  SHINE_HIP_CHECK(hipMemcpyAsync(both, s.total, 16, hipMemcpyDeviceToHost, st));
+  SHINE_HIP_CHECK(hipStreamSynchronize(st));
+  *n_out = both[0];
+  *n_unknown_out = both[1];
   return SHINE_OK;
 }
 

@@ -18,7 +18,25 @@ on the device (csrc/shine_frame.hip).  Differences from the re
   * batch-mode pools grow in capacity-doubling buffers; the `*_pool` attributes are views of the used part and are REPLACED by
     every process_frame (do not keep them across frames);
   * in incremental mode without `ray_loss` the two depth pools stay empty (nothing reads them);
-  * `estimate_normal`, `filter_noise`, `semantic_on`, `.pcd` files, `sapce_carving_sample` and `behind_dropoff_on` are refused.
+  * `estimate_normal`, `filter_noise`, `.pcd` files, `sapce_carving_sample` and `behind_dropoff_on` are refused, and so is
+    `semantic_on` without `config.label_path` (there is nothing to read labels from).
+
+With `config.semantic_on` and `config.label_path` a frame also carries a class per point (dataset/lidar_dataset.py:132-136, 166-173,
+197-199, 301-362):
+    read (.bin + label_path/<name with 'bin' -> 'label'>, uint32) -> shine_sem_frame_filter (range, moving, outlier, learning map,
+    crop box; ONE launch) -> voxel means with class / 255 carried as an attribute (shine_voxel_down_attr), class = rint(mean * 255)
+    — the reference's detour through open3d's colour channel — or the seeded subset applied to points and classes alike
+    -> pose transform -> map copy with the class colours averaged per map voxel -> shine_ray_sample(labels=class) into the int32
+    `sem_label` pool, which the window filter compacts with the others -> get_batch returns sem_label (int64).
+The label definition comes from semantic_kitti.LabelMap.from_config(config).  Differences / quirks kept:
+  * the reference calls preprocess_sem_kitti(points, labels, config.min_z, config.min_range, ...) positionally into the parameters
+    (min_range, filter_outlier): the RANGE cut is config.min_z (usually negative: no cut) and the outlier filter is on iff
+    config.min_range is non-zero.  Reproduced as it is, so that a config gives the points the reference would have kept;
+  * the semantic path never applies preprocess_kitti's `z > min_z`: only the crop box (inclusive) bounds z;
+  * a voxel's class is the rounded MEAN of its points' classes (round-half-to-even), not a vote: a voxel holding classes 3 and 4
+    becomes class 4, one holding 2, 9 and 9 becomes class 7.  Kept, as the reference trains on exactly these labels;
+  * ray mode gathers `sem_label_pool[ray_index * ray_sample_count]`: the label of the ray's first surface sample, one per ray;
+  * a raw id the label map does not hold raises ValueError (the reference: KeyError) if it survives the label filters.
 """
 from __future__ import annotations
 
@@ -35,6 +53,7 @@ from . import evaluation as ev
 
 _U64 = (1 << 64) - 1
 UNSUPPORTED = ("estimate_normal", "filter_noise", "semantic_on", "behind_dropoff_on")
+SEMANTIC_NEEDS = " (frame-level label files and the learning map are not read without config.label_path; ray_sample itself takes labels)"
 
 
 def natural_key(name):
@@ -133,23 +152,35 @@ class BoundingBox:
 
 
 class PointCloud:
-    """the merged map cloud: fp64 [n,3] device chunks, concatenated when `points` is read"""
+    """the merged map cloud: fp64 [n,3] device chunks, concatenated when `points` is read; `colors` (fp64 [n,3] in 0..1, one row
+    per point) likewise, None unless every chunk came with colours"""
 
-    def __init__(self, points=None):
+    def __init__(self, points=None, colors=None):
         self._chunks = [] if points is None else [points]
+        self._colors = [] if points is None else [colors]
 
     def __iadd__(self, other):
         self._chunks += other._chunks
+        self._colors += other._colors
         return self
 
     def __len__(self):
         return sum(int(c.shape[0]) for c in self._chunks)
 
+    def _merge(self):
+        if len(self._chunks) > 1:
+            self._colors = [None if any(c is None for c in self._colors) else torch.cat(self._colors, 0)]
+            self._chunks = [torch.cat(self._chunks, 0)]
+
     @property
     def points(self):
-        if len(self._chunks) > 1:
-            self._chunks = [torch.cat(self._chunks, 0)]
+        self._merge()
         return self._chunks[0] if self._chunks else torch.empty((0, 3), dtype=torch.float64)
+
+    @property
+    def colors(self):
+        self._merge()
+        return self._colors[0] if self._colors else None
 
     def get_min_bound(self):
         return ev.bounds(self.points)[0]
@@ -184,6 +215,52 @@ def frame_filter(points, min_z, max_z, min_range, pc_radius):
     _lib.check(lib.shine_frame_filter(points.data_ptr(), *args, ws.data_ptr(), C.byref(need), out.data_ptr(), C.byref(kept), st),
                "shine_frame_filter")
     return out[:kept.value]
+
+
+def sem_frame_filter(points, labels, label_map, range_min, filter_moving, filter_outlier, min_z, max_z, pc_radius):
+    """preprocess_sem_kitti + the learning map + the crop box in one launch (shine_sem_frame_filter).  points = device [n,3] / [n,4]
+    float32 or float64, labels = [n] raw uint32 label words (any 4-byte or wider integer tensor / array; the lower 16 bits are
+    the semantic id), label_map = semantic_kitti.LabelMap.  Keeps, in input order, |p| >= range_min, id < 100 (filter_moving),
+    id != 1 (filter_outlier), |x|, |y| <= pc_radius, min_z <= z <= max_z.  -> (fp64 [k,3], int32 [k] classes) on the device.
+    A raw id the map does not hold, on a point that passes the range / moving / outlier tests, raises ValueError."""
+    if not points.is_cuda:
+        raise _lib.ShineHipError("sem_frame_filter runs on the device only (there is no CPU path)")
+    if points.dim() != 2 or points.shape[1] not in (3, 4) or points.dtype not in (torch.float32, torch.float64):
+        raise ValueError("sem_frame_filter: expected [n,3] or [n,4] float32 / float64 points, got %s %s"
+                         % (tuple(points.shape), points.dtype))
+    points = points.contiguous()
+    n = int(points.shape[0])
+    if not torch.is_tensor(labels):
+        labels = torch.from_numpy(np.ascontiguousarray(np.asarray(labels).astype(np.int64)))
+    if labels.numel() != n:
+        raise ValueError("sem_frame_filter: %d labels for %d points" % (labels.numel(), n))
+    # (torch has no uint32 arithmetic: the 32-bit pattern travels as int32, the kernel reads it unsigned)
+    if labels.dtype != torch.int32:
+        lab = labels.to(torch.int64) & 0xFFFFFFFF
+        labels = torch.where(lab >= (1 << 31), lab - (1 << 32), lab).to(torch.int32)
+    labels = labels.to(points.device).reshape(-1).contiguous()
+    out = torch.empty((n, 3), dtype=torch.float64, device=points.device)
+    cls = torch.empty(n, dtype=torch.int32, device=points.device)
+    if n == 0:
+        return out, cls
+    lut = label_map.device_lut(points.device)
+    lib, st = _lib.lib(), _lib.current_stream_handle()
+    need = C.c_size_t(0)
+    is64, stride = int(points.dtype == torch.float64), int(points.shape[1])
+    tail = (float(range_min), int(bool(filter_moving)), int(bool(filter_outlier)), float(min_z), float(max_z), float(pc_radius))
+    _lib.check(lib.shine_sem_frame_filter(None, n, is64, stride, None, None, *tail, None, C.byref(need), None, None, None, None, st),
+               "shine_sem_frame_filter")
+    ws = _ws(need.value, points.device)
+    kept, unknown = C.c_int64(0), C.c_int64(0)
+    _lib.check(lib.shine_sem_frame_filter(points.data_ptr(), n, is64, stride, labels.data_ptr(), lut.data_ptr(), *tail, ws.data_ptr(),
+                                          C.byref(need), out.data_ptr(), cls.data_ptr(), C.byref(kept), C.byref(unknown), st),
+               "shine_sem_frame_filter")
+    if unknown.value > 0:
+        ids = labels.to(torch.int64) & 0xFFFF
+        bad = torch.unique(ids[lut[ids] < 0]).tolist()  # (candidates: the kernel counted those among them that pass the filters)
+        raise ValueError("sem_frame_filter: %d point(s) carry a raw label id the label map does not hold (unmapped ids in this "
+                         "scan: %s)" % (unknown.value, bad))
+    return out[:kept.value], cls[:kept.value]
 
 
 class SamplerParams:
@@ -364,12 +441,13 @@ POOL_NAMES = ("coord", "sdf_label", "weight", "sample_depth", "ray_depth", "orig
 
 class LiDARDataset:
     def __init__(self, config, octree=None) -> None:
+        self.semantic = bool(getattr(config, "semantic_on", False)) and self._reads_labels(config)
         for name in UNSUPPORTED:
-            if getattr(config, name, False):
+            if getattr(config, name, False) and not (name == "semantic_on" and self.semantic):
                 raise NotImplementedError(
                     "shine_mapping_amd.dataset.LiDARDataset does not support config.%s = True%s" % (name, {
                         "behind_dropoff_on": " (the reference's own sampler raises there: it multiplies an [N,1] weight tensor by an [N] drop-off in place)",
-                        "semantic_on": " (frame-level label files and the learning map are not read; ray_sample itself takes labels)",
+                        "semantic_on": SEMANTIC_NEEDS,
                     }.get(name, "")))
         self.config = config
         self.dtype = getattr(config, "dtype", torch.float32)
@@ -423,6 +501,12 @@ class LiDARDataset:
         self.normal_label_pool = _empty((0, 3), self.dtype, self.pool_device)
         self.color_label_pool = _empty((0, 3), self.dtype, self.pool_device)
         self.sem_label_pool = _empty((0,), torch.long, self.pool_device)
+        self.label_map = None
+        if self.semantic:
+            from .semantic_kitti import LabelMap
+
+            self.label_map = LabelMap.from_config(config)
+            self._pools["sem_label"] = _Pool((), torch.int32, self.pool_device)
         self._publish()
         self._pool_version = 0
         self._sorted = None  # (SortedPool, pool version, tables epoch)
@@ -430,13 +514,19 @@ class LiDARDataset:
 
     # ---- pools --------------------------------------------------------------------------------------------------------------
     def _publish(self):
-        for n in POOL_NAMES:
+        for n in self._pools:
             setattr(self, n + "_pool", self._pools[n].view())
 
     def _kept_pools(self):
-        """the pools batch mode appends to (dataset/lidar_dataset.py:262-271)"""
-        return ("coord", "weight", "sample_depth", "ray_depth") if self.config.ray_loss else \
+        """the pools batch mode appends to (dataset/lidar_dataset.py:262-281)"""
+        names = ("coord", "weight", "sample_depth", "ray_depth") if self.config.ray_loss else \
             ("coord", "weight", "sdf_label", "origin", "time")
+        return names + ("sem_label",) if self.semantic else names
+
+    def _reads_labels(self, config):
+        """semantic_on is served only with a folder of label files (rgbd.RGBDDataset: never)"""
+        path = getattr(config, "label_path", None)
+        return isinstance(path, str) and path != ""
 
     # ---- files ----------------------------------------------------------------------------------------------------------------
     # (the two things a subclass with another kind of frame file replaces, next to frame_points: rgbd.RGBDDataset)
@@ -482,8 +572,9 @@ class LiDARDataset:
         pts = frame_filter(raw, cfg.min_z, cfg.max_z, cfg.min_range, cfg.pc_radius)
         return self._down_sample(pts, frame_id)
 
-    def _down_sample(self, pts, frame_id):
-        """stage 3: the filtered points of a frame -> the seeded random subset or the voxel means"""
+    def _down_sample(self, pts, frame_id, classes=None):
+        """stage 3: the filtered points of a frame -> the seeded random subset or the voxel means; with classes (int32 [n]) ->
+        (points, classes): the same subset of both, or the voxel means with rint(mean(class / 255) * 255) as the voxel's class"""
         cfg = self.config
         if pts.shape[0] == 0:
             raise ValueError("frame %d (%s): no point passes min_z / min_range / the crop box" % (frame_id, self.pc_filenames[frame_id]))
@@ -491,19 +582,57 @@ class LiDARDataset:
             n = int(pts.shape[0])
             keep = int(n * cfg.rand_down_r)
             if keep < n:
-                pts = pts[random_subset(n, keep, self.seed, frame_id, pts.device)]
-        else:
+                subset = random_subset(n, keep, self.seed, frame_id, pts.device)
+                pts = pts[subset]
+                classes = classes[subset] if classes is not None else None
+        elif classes is None:
             pts = ev.voxel_down_sample(pts, cfg.vox_down_m)
-        return pts
+        else:
+            pts, mean = ev.voxel_down_sample(pts, cfg.vox_down_m, attrs=classes.double() / 255.0)
+            classes = torch.round(mean * 255.0).to(torch.int32)  # (two roundings, as numpy's `colors * 255.0` then np.round)
+        return pts if classes is None else (pts, classes)
+
+    def read_semantic_point_label(self, bin_filename, label_filename):
+        """a labelled scan on the device: ([n,4] float32 points, [n] int32 holding the uint32 label words' bits)"""
+        if ".bin" not in bin_filename:
+            raise ValueError("The format of the imported point cloud is wrong (semantic_on supports only *bin): %s" % bin_filename)
+        if ".label" not in label_filename:
+            raise ValueError("The format of the imported point labels is wrong (support only *label): %s" % label_filename)
+        pts = np.fromfile(bin_filename, dtype=np.float32).reshape((-1, 4))
+        labels = np.fromfile(label_filename, dtype=np.uint32).reshape(-1)
+        if len(labels) != len(pts):
+            raise ValueError("%s holds %d labels, %s holds %d points" % (label_filename, len(labels), bin_filename, len(pts)))
+        return torch.from_numpy(pts).to(self.device), torch.from_numpy(labels.view(np.int32)).to(self.device)
+
+    def sem_frame_points(self, frame_id):
+        """frame_points with semantic_on: (points fp64 [m,3] in the SENSOR frame, classes int32 [m]) after the label filters, the
+        learning map, the crop and the down-sampling"""
+        cfg = self.config
+        name = self.pc_filenames[frame_id]
+        raw, labels = self.read_semantic_point_label(os.path.join(cfg.pc_path, name),
+                                                     os.path.join(cfg.label_path, name.replace("bin", "label")))
+        # (the reference's positional call, dataset/lidar_dataset.py:319-321: min_z lands in min_range, min_range in filter_outlier)
+        pts, classes = sem_frame_filter(raw, labels, self.label_map, cfg.min_z, getattr(cfg, "filter_moving_object", True),
+                                        bool(cfg.min_range), cfg.min_z, cfg.max_z, cfg.pc_radius)
+        return self._down_sample(pts, frame_id, classes)
 
     def process_frame(self, frame_id, incremental_on=False):
         cfg = self.config
         self.cur_pose_ref = self.poses_ref[frame_id]
-        pts = transform_points(self.frame_points(frame_id), self.cur_pose_ref)
+        classes = None
+        if self.semantic:
+            pts, classes = self.sem_frame_points(frame_id)
+            pts = transform_points(pts, self.cur_pose_ref)
+        else:
+            pts = transform_points(self.frame_points(frame_id), self.cur_pose_ref)
         frame_origin = (self.cur_pose_ref[:3, 3] * cfg.scale).astype(np.float32)
 
         # the copy merged into the map cloud
-        self.cur_frame_pc = PointCloud(ev.voxel_down_sample(pts, cfg.map_vox_down_m))
+        if classes is not None and self.label_map.colors is not None:  # (the class colours, averaged per map voxel as open3d does)
+            self.cur_frame_pc = PointCloud(*ev.voxel_down_sample(
+                pts, cfg.map_vox_down_m, attrs=self.label_map.device_colors(pts.device)[classes.long()]))
+        else:
+            self.cur_frame_pc = PointCloud(ev.voxel_down_sample(pts, cfg.map_vox_down_m))
         self.map_down_pc += self.cur_frame_pc
         lo, hi = ev.bounds(self.cur_frame_pc.points)
         self.cur_bbx = BoundingBox(lo, hi)
@@ -530,7 +659,7 @@ class LiDARDataset:
             if on_device:  # the sampler writes straight into the pools' tails
                 out = {n: pools[n].reserve(m if n == "ray_depth" else m * S) for n in self._kept_pools()}
         res = ray_sample(pts_s, frame_origin, self.sampler, seed=self.seed, stream_id=frame_id, time_value=float(frame_id), out=out,
-                         depths=bool(cfg.ray_loss), origin_time=point_mode or incremental_on)
+                         depths=bool(cfg.ray_loss), origin_time=point_mode or incremental_on, labels=classes)
 
         if self.octree is not None:
             if cfg.octree_from_surface_samples:
@@ -541,19 +670,16 @@ class LiDARDataset:
                 self.octree.update(pts_s, incremental_on)
 
         if incremental_on:
-            for n in POOL_NAMES:
+            for n in pools:
                 t = res.get(n)
                 if t is None:
-                    t = torch.empty((0,) + pools[n].tail, dtype=self.dtype, device=self.device)
+                    t = torch.empty((0,) + pools[n].tail, dtype=pools[n].dtype, device=self.device)
                 pools[n].replace(t.to(self.pool_device))
-            self.normal_label_pool = None
-            self.sem_label_pool = None
-        else:
-            if not on_device:
-                for n in self._kept_pools():
-                    pools[n].reserve(res[n].shape[0]).copy_(res[n])
-            self.normal_label_pool = None
-            self.sem_label_pool = None
+        elif not on_device:
+            for n in self._kept_pools():
+                pools[n].reserve(res[n].shape[0]).copy_(res[n])
+        self.normal_label_pool = None
+        self.sem_label_pool = None  # (with semantic_on: _publish sets the int32 view of the `sem_label` pool)
         self._publish()
         self._pool_version += 1
 
@@ -591,24 +717,32 @@ class LiDARDataset:
             weight = self.weight_pool[index].to(self.device)
             sample_depth = self.sample_depth_pool[index].to(self.device)
             ray_depth = self.ray_depth_pool[ray_index].to(self.device)
-            return coord, sample_depth, ray_depth, None, None, weight
+            sem_label = self.sem_label_pool[ray_index * R].to(self.device).long() if self.semantic else None  # (one per ray)
+            return coord, sample_depth, ray_depth, None, sem_label, weight
         if self.octree is not None and not self.to_cpu:
             sp = self.sorted_pool()
             idx = sp.draw(cfg.bs)
             coord, sdf_label, weight = sp.get_batch(idx)
             src = self._sorted_perm[idx.long()]
-            return coord, sdf_label, self.origin_pool[src], self.time_pool[src], None, None, weight
+            sem_label = self.sem_label_pool[src].long() if self.semantic else None  # (int64: what NLLLoss takes)
+            return coord, sdf_label, self.origin_pool[src], self.time_pool[src], None, sem_label, weight
         n = self.sdf_label_pool.shape[0]
         index = torch.randint(0, n, (cfg.bs,), device=self.pool_device)
+        sem_label = self.sem_label_pool[index].to(self.device).long() if self.semantic else None
         return (self.coord_pool[index, :].to(self.device), self.sdf_label_pool[index].to(self.device),
-                self.origin_pool[index].to(self.device), self.time_pool[index].to(self.device), None, None,
+                self.origin_pool[index].to(self.device), self.time_pool[index].to(self.device), None, sem_label,
                 self.weight_pool[index].to(self.device))
 
     def write_merged_pc(self, out_path):
         from .mesher import write_ply
 
         pts = transform_points(self.map_down_pc.points, np.linalg.inv(self.begin_pose_inv)).cpu().numpy()  # back to the world frame
-        write_ply(out_path, [("x", pts[:, 0], "double"), ("y", pts[:, 1], "double"), ("z", pts[:, 2], "double")])
+        props = [("x", pts[:, 0], "double"), ("y", pts[:, 1], "double"), ("z", pts[:, 2], "double")]
+        colors = self.map_down_pc.colors
+        if colors is not None:  # (a semantic map: the class colours, written as Mesher._finish writes a mesh's)
+            rgb = np.clip(np.round(colors.cpu().numpy() * 255.0), 0, 255).astype(np.uint8)
+            props += [("red", rgb[:, 0], "uchar"), ("green", rgb[:, 1], "uchar"), ("blue", rgb[:, 2], "uchar")]
+        write_ply(out_path, props)
         print("save the merged point cloud map to %s\n" % (out_path))
 
     def __len__(self) -> int:

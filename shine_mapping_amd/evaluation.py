@@ -187,37 +187,63 @@ def _check_axis_bits(lo, hi, origin, cell, what):
     return cells.astype(np.int64)
 
 
-def voxel_down_sample(points, voxel, return_keys=False):
+def voxel_down_sample(points, voxel, return_keys=False, attrs=None):
     """open3d's voxel_down_sample: one point per occupied voxel, the mean (fp64 sums) of the voxel's points.  The voxel index is
     floor((p - (min_bound - voxel/2)) / voxel) per axis with min_bound the cloud's own minimum; the output is ordered by
     ascending voxel key (ix << 42 | iy << 21 | iz) — open3d's order is that of a hash map — and is bit-identical from run to
     run.  Refuses clouds that need more than 21 bits per axis.  Returns [m,3] fp64 on the device (and the uint64 keys as int64
-    with return_keys)."""
+    with return_keys).  attrs: [n] or [n,a] (a = 1..4) fp64 values carried along, the way open3d carries colours
+    (shine_voxel_down_attr): their per-voxel means, summed in input order, are returned last ([m] or [m,a]); points and keys are
+    the same bits as without attrs."""
     torch = _torch()
     voxel = float(voxel)
     if not voxel > 0.0:
         raise ValueError("voxel_down_sample: voxel must be > 0")
     host = _host_points(points)
     n = len(host) if host is not None else int(points.shape[0])
+    att, flat = None, False
+    if attrs is not None:
+        att = attrs.detach() if isinstance(attrs, torch.Tensor) else torch.as_tensor(np.asarray(attrs, dtype=np.float64))
+        flat = att.dim() == 1
+        att = att.reshape(n, -1) if n else att.reshape(0, 1 if flat else att.shape[-1])
+        if att.shape[1] < 1 or att.shape[1] > 4:
+            raise ValueError("voxel_down_sample: attrs must be [n] or [n,a] with 1 <= a <= 4, got %s" % (tuple(attrs.shape),))
+
+    def result(out, keys, aout):
+        res = (out,) + ((keys,) if return_keys else ()) + ((aout[:, 0] if flat else aout,) if att is not None else ())
+        return res[0] if len(res) == 1 else res
+
     if n == 0:
         pts = _points(points)
-        empty = torch.empty((0, 3), dtype=torch.float64, device=pts.device)
-        return (empty, torch.empty(0, dtype=torch.int64, device=pts.device)) if return_keys else empty
+        return result(torch.empty((0, 3), dtype=torch.float64, device=pts.device), torch.empty(0, dtype=torch.int64, device=pts.device),
+                      torch.empty((0, att.shape[1]), dtype=torch.float64, device=pts.device) if att is not None else None)
     lo, hi = bounds(points)
     origin = lo - voxel * 0.5
     _check_axis_bits(lo, hi, origin, voxel, "voxel_down_sample")
     pts = _points(points)
     lib, st = _lib.lib(), _stream()
     need = C.c_size_t(0)
-    _lib.check(lib.shine_eval_voxel_down(None, n, None, voxel, None, C.byref(need), None, None, None, st), "shine_eval_voxel_down")
-    ws = _ws(need.value, pts.device)
     out = torch.empty((n, 3), dtype=torch.float64, device=pts.device)
     keys = torch.empty(n, dtype=torch.int64, device=pts.device) if return_keys else None
     m = C.c_int64(0)
-    _lib.check(lib.shine_eval_voxel_down(pts.data_ptr(), n, _d3(origin), voxel, ws.data_ptr(), C.byref(need), out.data_ptr(),
-                                         keys.data_ptr() if keys is not None else None, C.byref(m), st), "shine_eval_voxel_down")
-    out = out[:m.value].clone()
-    return (out, keys[:m.value].clone()) if return_keys else out
+    if att is None:
+        _lib.check(lib.shine_eval_voxel_down(None, n, None, voxel, None, C.byref(need), None, None, None, st), "shine_eval_voxel_down")
+        ws = _ws(need.value, pts.device)
+        _lib.check(lib.shine_eval_voxel_down(pts.data_ptr(), n, _d3(origin), voxel, ws.data_ptr(), C.byref(need), out.data_ptr(),
+                                             keys.data_ptr() if keys is not None else None, C.byref(m), st), "shine_eval_voxel_down")
+        aout = None
+    else:
+        att = att.to(device=pts.device, dtype=torch.float64).contiguous()
+        a = int(att.shape[1])
+        _lib.check(lib.shine_voxel_down_attr(None, None, a, n, None, voxel, None, C.byref(need), None, None, None, None, st),
+                   "shine_voxel_down_attr")
+        ws = _ws(need.value, pts.device)
+        aout = torch.empty((n, a), dtype=torch.float64, device=pts.device)
+        _lib.check(lib.shine_voxel_down_attr(pts.data_ptr(), att.data_ptr(), a, n, _d3(origin), voxel, ws.data_ptr(), C.byref(need),
+                                             out.data_ptr(), aout.data_ptr(), keys.data_ptr() if keys is not None else None,
+                                             C.byref(m), st), "shine_voxel_down_attr")
+        aout = aout[:m.value].clone()
+    return result(out[:m.value].clone(), keys[:m.value].clone() if keys is not None else None, aout)
 
 
 class NNGrid:

@@ -369,13 +369,25 @@ def _open3d():
         return None
 
 
-def _sem_color_map():
+def _sem_color_map(config=None):
+    """class -> (r, g, b) 0-255: the reference's table when it can be imported, else the config's own map (sem_color_map, or the
+    colours of label_map_path: semantic_kitti.LabelMap), else None"""
     try:
         from utils.semantic_kitti_utils import sem_kitti_color_map
 
         return sem_kitti_color_map
     except Exception:
-        return None
+        pass
+    cmap = getattr(config, "sem_color_map", None)
+    if cmap:
+        return cmap
+    if getattr(config, "label_map_path", None):
+        from .semantic_kitti import LabelMap
+
+        colors = LabelMap.from_yaml(config.label_map_path, int(getattr(config, "sem_class_count", 20))).colors
+        if colors is not None:
+            return {k: c * 255.0 for k, c in enumerate(colors)}
+    return None
 
 
 def _make_mesh(verts, faces, normals=None, colors=None):
@@ -518,8 +530,8 @@ class Mesher:
         return marching_cubes(sdf, mask, 0.0)
 
     def estimate_vertices_sem(self, mesh, verts, filter_free_space_vertices=True):
-        """utils/mesher.py:224-238: vertex labels (shine_sem_query_labels), colours when the reference's colour map can be
-        imported, then the free-space vertices (label <= 0) removed with their triangles."""
+        """utils/mesher.py:224-238: vertex labels (shine_sem_query_labels), colours from the reference's colour map or the
+        config's, then the free-space vertices (label <= 0) removed with their triangles."""
         dev = self.octree.hier_features[0].device
         v = torch.as_tensor(np.asarray(verts, np.float64), device=dev)
         f = torch.as_tensor(np.asarray(mesh.triangles, np.int32), device=dev)
@@ -531,10 +543,11 @@ class Mesher:
 
     def _sem_device(self, verts, faces, filter_free_space_vertices):
         labels = query_labels_device(self.octree, self.sem_decoder, (verts * self.world_scale).float())
-        cmap = _sem_color_map()
+        cmap = _sem_color_map(self.config)
         colors = None
         if cmap is not None:
-            lut = np.zeros((max(int(k) for k in cmap) + 1, 3), np.float64)
+            rows = max(max(int(k) for k in cmap), int(getattr(self.config, "sem_class_count", 0))) + 1  # (a class without a colour: black)
+            lut = np.zeros((rows, 3), np.float64)
             for k, c in cmap.items():
                 lut[int(k)] = np.asarray(c, np.float64) / 255.0
             colors = torch.as_tensor(lut, device=verts.device)[labels]

@@ -191,6 +191,9 @@ class RGBDDataset(LiDARDataset):
     depth_path, intrinsic_path (""), is_focal_file (True), pose_path, pose_kitti_format (False), max_depth_m (5.0) — the cases and
     defaults of dataset/rgbd_to_kitti_format.py:33-67,161-167."""
 
+    def _reads_labels(self, config):
+        return False  # (depth frames carry no label files: semantic_on stays refused)
+
     def _read_poses(self, config):
         self.calib = {"Tr": np.eye(4)}
         return read_poses(config.pose_path, bool(getattr(config, "pose_kitti_format", False)))

@@ -67,12 +67,14 @@ def _boxes(street_len: float, gen: torch.Generator, n=20):
     return lo, hi
 
 
-def cast_scan(origin, dirs, lo, hi, half_width=8.0, facade_h=10.0, max_range=50.0, min_range=1.5):
-    """Analytic ray cast of one scan: ground z=0, facades y=+-half_width, axis-aligned boxes. -> hit points [M,3]."""
+def cast_scan(origin, dirs, lo, hi, half_width=8.0, facade_h=10.0, max_range=50.0, min_range=1.5, kinds=False):
+    """Analytic ray cast of one scan: ground z=0, facades y=+-half_width, axis-aligned boxes. -> hit points [M,3] (with kinds
+    also what each ray met first, int64 [M] of GROUND / FACADE / BOX)."""
     o = origin
     big = torch.full((dirs.shape[0],), float("inf"), device=dirs.device)
     dz = dirs[:, 2]
     t = torch.where(dz < -1e-6, -o[2] / dz, big)
+    t_ground = t
     for sgn in (-1.0, 1.0):
         dy = dirs[:, 1]
         tf = torch.where(dy * sgn > 1e-6, (sgn * half_width - o[1]) / dy, big)
@@ -85,8 +87,12 @@ def cast_scan(origin, dirs, lo, hi, half_width=8.0, facade_h=10.0, max_range=50.
     tn = torch.minimum(t0, t1).amax(-1)
     tx = torch.maximum(t0, t1).amin(-1)
     tb = torch.where((tx >= tn) & (tn > 0), tn, torch.full_like(tn, float("inf"))).amin(-1)
+    t_flat = t
     t = torch.minimum(t, tb)
     ok = (t < max_range) & (t > min_range)
+    if kinds:
+        kind = torch.where(tb < t_flat, BOX, torch.where(t_flat < t_ground, FACADE, GROUND))
+        return o[None] + t[ok, None] * dirs[ok], kind[ok]
     return o[None] + t[ok, None] * dirs[ok]
 
 
@@ -167,8 +173,9 @@ def make_frames(cfg, frames=100, beams=64, azimuths=450, seed=42, device="cuda")
         yield sample_rays((hits - shift) * cfg.scale, (origin - shift) * cfg.scale, cfg, gen)
 
 
-def make_scans(cfg, frames=100, beams=64, azimuths=450, seed=42, device="cuda"):
-    """Yield per-frame (hit points [M,3], sensor origin [3], map centre [3]) in metres: the scans make_frames samples."""
+def make_scans(cfg, frames=100, beams=64, azimuths=450, seed=42, device="cuda", kinds=False):
+    """Yield per-frame (hit points [M,3], sensor origin [3], map centre [3]) in metres: the scans make_frames samples (with kinds
+    a fourth element: what each point lies on, cast_scan's kinds)."""
     g = torch.Generator().manual_seed(seed)
     segs = trajectory(cfg.street_len, getattr(cfg, "turns", 0))
     boxes = []
@@ -195,32 +202,68 @@ def make_scans(cfg, frames=100, beams=64, azimuths=450, seed=42, device="cuda"):
         lo, hi = boxes[k]
         local_origin = torch.tensor([s_ - acc, 0.3 * math.sin(0.2 * f), 1.8], device=device)
         hits = cast_scan(local_origin, dirs @ Rinv.T if len(segs) > 1 else dirs, lo, hi, max_range=cfg.pc_radius_m,
-                         min_range=cfg.min_range_m)
+                         min_range=cfg.min_range_m, kinds=kinds)
+        if kinds:
+            hits, kind = hits
         base = torch.tensor([x0, y0, 0.0], device=device)
         if len(segs) > 1:
             hits = hits @ R.T + base
             origin = local_origin @ R.T + base
         else:
             origin = local_origin
-        yield hits, origin, shift
+        if kinds:
+            yield hits, origin, shift, kind
+        else:
+            yield hits, origin, shift
 
 
-def write_kitti_drive(folder, cfg, frames=6, beams=64, azimuths=450, seed=42, device="cpu", yaw_per_frame=0.05):
+# the labelled drive's label definition, in SemanticKITTI's id ranges (ids >= 100 move, 1 is the outlier id): raw id -> class, and
+# class -> (r, g, b).  DRIVE_RAW_IDS: what ground, facade and boxes carry; DRIVE_UNMAPPED_ID is in neither dict.
+DRIVE_RAW_IDS = {0: 40, 1: 50, 2: 10}  # GROUND, FACADE, BOX (the kinds of cast_scan / cast_depth)
+DRIVE_LABEL_MAP = {0: 0, 1: 0, 10: 1, 40: 2, 44: 2, 50: 3, 51: 4, 252: 1, 254: 5}
+DRIVE_COLOR_MAP = {0: (255, 255, 255), 1: (100, 150, 245), 2: (255, 0, 255), 3: (255, 200, 0), 4: (255, 120, 50), 5: (255, 30, 30)}
+DRIVE_UNMAPPED_ID = 77
+
+
+def write_kitti_drive(folder, cfg, frames=6, beams=64, azimuths=450, seed=42, device="cpu", yaw_per_frame=0.05, labels=False,
+                      unmapped=0):
     """Write make_scans' drive as a KITTI-format folder — velodyne/%06d.bin (float32 x, y, z, intensity in the SENSOR frame),
     poses.txt (camera-frame poses, 12 values per line) and calib.txt (Tr: lidar -> camera) — the input LiDARDataset reads.
     The sensor yaws by `yaw_per_frame` rad per frame, so the poses carry a rotation.  Returns a SimpleNamespace with pc_path,
-    pose_path, calib_path and lidar_poses (the [4,4] float64 lidar-to-world poses the files encode: Tr^-1 . P . Tr)."""
+    pose_path, calib_path and lidar_poses (the [4,4] float64 lidar-to-world poses the files encode: Tr^-1 . P . Tr).
+    labels=True: also labels/%06d.label, one uint32 per point in SemanticKITTI's layout — the lower 16 bits the raw semantic id
+    of what the point lies on (DRIVE_RAW_IDS), the upper 16 a random instance id — with a seeded sprinkle of special ids: about
+    2 % moving (252, 254), 1 % outlier (1), 1 % unlabeled (0), 2 % a second ground id (44) and a second facade id (51), and
+    `unmapped` points per frame (default none) with DRIVE_UNMAPPED_ID, an id the map does not hold.  The result then also carries
+    label_path, label_map (raw id -> class) and color_map (class -> (r, g, b)).  The scans are the same bytes with and without
+    labels."""
     import os
 
     import numpy as np
 
     pc_path = os.path.join(folder, "velodyne")
     os.makedirs(pc_path, exist_ok=True)
+    label_path = os.path.join(folder, "labels")
+    if labels:
+        os.makedirs(label_path, exist_ok=True)
+        rng = np.random.default_rng(seed + 7)
     # KITTI's axis convention (camera x = -lidar y, y = -lidar z, z = lidar x) plus a small lever arm
     Tr = np.array([[0.0, -1.0, 0.0, 0.05], [0.0, 0.0, -1.0, -0.08], [1.0, 0.0, 0.0, -0.27], [0.0, 0.0, 0.0, 1.0]])
     Tr_inv = np.linalg.inv(Tr)
     poses, lines = [], []
-    for f, (hits, origin, shift) in enumerate(make_scans(cfg, frames, beams, azimuths, seed, device)):
+    for f, scan_f in enumerate(make_scans(cfg, frames, beams, azimuths, seed, device, kinds=labels)):
+        hits, origin, shift = scan_f[:3]
+        if labels:
+            kind = scan_f[3].cpu().numpy()
+            raw = np.select([kind == k for k in DRIVE_RAW_IDS], list(DRIVE_RAW_IDS.values())).astype(np.uint32)
+            u = rng.random(len(raw))
+            for lo_u, hi_u, ids in ((0.00, 0.02, (252, 254)), (0.02, 0.03, (1,)), (0.03, 0.04, (0,)), (0.04, 0.06, (44, 51))):
+                pick = np.flatnonzero((u >= lo_u) & (u < hi_u))
+                raw[pick] = np.asarray(ids, np.uint32)[rng.integers(0, len(ids), len(pick))]
+            if unmapped:
+                raw[rng.choice(len(raw), size=min(int(unmapped), len(raw)), replace=False)] = DRIVE_UNMAPPED_ID
+            instance = rng.integers(1, 1 << 16, len(raw)).astype(np.uint32)
+            ((instance << 16) | raw).astype(np.uint32).tofile(os.path.join(label_path, "%06d.label" % f))
         yaw = yaw_per_frame * f
         W = np.eye(4)
         W[:3, :3] = [[math.cos(yaw), -math.sin(yaw), 0.0], [math.sin(yaw), math.cos(yaw), 0.0], [0.0, 0.0, 1.0]]
@@ -239,12 +282,15 @@ def write_kitti_drive(folder, cfg, frames=6, beams=64, azimuths=450, seed=42, de
         for key in ("P0", "P1", "P2", "P3"):
             fh.write("%s: 1.0 0.0 0.0 0.0 0.0 1.0 0.0 0.0 0.0 0.0 1.0 0.0\n" % key)
         fh.write("Tr: " + " ".join(repr(float(v)) for v in Tr[:3].reshape(-1)) + "\n")
-    return SimpleNamespace(pc_path=pc_path, pose_path=pose_path, calib_path=calib_path, lidar_poses=poses, frames=frames)
+    drive = SimpleNamespace(pc_path=pc_path, pose_path=pose_path, calib_path=calib_path, lidar_poses=poses, frames=frames)
+    if labels:
+        drive.__dict__.update(label_path=label_path, label_map=dict(DRIVE_LABEL_MAP), color_map=dict(DRIVE_COLOR_MAP))
+    return drive
 
 
 def dataset_config(kind, drive, device="cuda", **over):
     """make_config(kind) plus the fields LiDARDataset reads (utils/config.py's names and defaults, the preset's crop radius and
-    minimum range), pointed at a write_kitti_drive folder"""
+    minimum range), pointed at a write_kitti_drive folder (a labelled one also sets label_path and the drive's label / colour maps)"""
     c = make_config(kind, device=device)
     c.__dict__.update(
         pc_path=drive.pc_path, pose_path=drive.pose_path, calib_path=drive.calib_path, first_frame_ref=False, begin_frame=0,
@@ -253,6 +299,9 @@ def dataset_config(kind, drive, device="cuda", **over):
         rand_down_r=1.0, map_vox_down_m=0.2, estimate_normal=False, filter_noise=False, semantic_on=False,
         behind_dropoff_on=False, octree_from_surface_samples=True, clearance_dist_m=0.3, clearance_sample_n=0,
         continual_learning_reg=False, window_replay_on=False, window_radius=50.0, ray_loss=False)
+    if getattr(drive, "label_path", None):  # a labelled drive (write_kitti_drive(labels=True)); semantic_on stays the caller's choice
+        c.__dict__.update(label_path=drive.label_path, sem_label_map=drive.label_map, sem_color_map=drive.color_map,
+                          filter_moving_object=True)
     c.__dict__.update(over)
     return c
 
