@@ -79,6 +79,24 @@ __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, con
   p -= (lr / a.bc1) * (m / denom);
 }
 
+// A workspace handed out as arrays in call order, each at a 256-byte boundary.  With base == nullptr every array is null and
+// only bytes() counts: the size query of an entry point runs the same code as the call that uses the workspace.
+class Arena {
+ public:
+  explicit Arena(void* base) : base_(static_cast<char*>(base)) {}
+  template <class T>
+  T* take(size_t count) {
+    char* p = base_ ? base_ + off_ : nullptr;
+    off_ += (count * sizeof(T) + 255) & ~(size_t)255;
+    return reinterpret_cast<T*>(p);
+  }
+  size_t bytes() const { return off_; }
+
+ private:
+  char* base_;
+  size_t off_ = 0;
+};
+
 int set_error(int code, const char* msg);
 int set_hip_error(hipError_t e, const char* what);
 

@@ -6,7 +6,8 @@
 // t = (level - v0) / (v1 - v0) in fp32, index units; an edge whose OUT end sits exactly on the level collapses onto that
 // point's "corner vertex", and a triangle that then repeats a vertex is not emitted.  Vertices are ordered by owner point
 // (corner vertex, +x, +y, +z edge), faces by cube, then by table order (csrc/shine_mc_tables.hpp).  No atomic decides where an
-// output goes: the same input gives the same bits.
+// output goes: the same input gives the same bits.  The per-point and per-cube rules themselves are in shine_mc_rules.hpp, shared
+// with shine_mc_sparse.hip; this file gives them a view of the global grid and says which cubes are processed.
 //
 // Three passes over tiles of MC_TILE = 1024 grid points (256 lanes x 4):
 //   classify  one lane per point: the owned-vertex bits (4) and the cube's non-degenerate triangle count (<= 5) packed in a
@@ -20,7 +21,7 @@
 
 namespace {
 
-#include "shine_mc_rules.hpp"  // edge_collapse, tri_degenerate, cube_tri_count, block_excl_scan
+#include "shine_mc_rules.hpp"  // FieldView, classify_bits, cube_triangles, the block reductions
 
 constexpr int MC_THREADS = 256;
 constexpr int MC_TILE = 4 * MC_THREADS;
@@ -58,55 +59,15 @@ __device__ __forceinline__ bool cube_processed(const McGrid& g, long long i, lon
   return !g.mask || g.mask[i + dx * g.Y * g.Z + dy * g.Z + dz] != 0;
 }
 
-// The cube at (x, y, z) (inside the grid): its 8 corner values and case.
-__device__ __forceinline__ int cube_case(const McGrid& g, long long i, float c[8]) {
-  const long long sx = g.Y * g.Z, sy = g.Z;
-  int cs = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    c[k] = g.v[i + (k & 1) * sx + ((k >> 1) & 1) * sy + ((k >> 2) & 1)];
-    cs |= (c[k] > g.level ? 1 : 0) << k;
-  }
-  return cs;
-}
+__device__ __forceinline__ FieldView<long long> grid_view(const McGrid& g) { return {g.v, g.Y * g.Z, g.Z, g.level}; }
 
-// Point i = (x, y, z): bits 0-3 = owns a corner vertex / a +x / +y / +z edge vertex; bits 4-7 = triangles of cube (x, y, z).
-__device__ unsigned char classify_point(const McGrid& g, long long i, long long x, long long y, long long z) {
-  const long long sx = g.Y * g.Z, sy = g.Z;
-  const long long p[3] = {x, y, z};
-  const long long dim[3] = {g.X, g.Y, g.Z};
-  const long long stride[3] = {sx, sy, 1};
-  // processed flags of the 8 cubes that contain the point: proc bit (dx | dy << 1 | dz << 2) = cube (x-1+dx, y-1+dy, z-1+dz)
+// the processed flags of the 8 cubes that contain point i = (x, y, z): bit (dx | dy << 1 | dz << 2) = cube (x-1+dx, y-1+dy, z-1+dz)
+__device__ __forceinline__ unsigned cubes_processed(const McGrid& g, long long i, long long x, long long y, long long z) {
   unsigned proc = 0;
 #pragma unroll
   for (int k = 0; k < 8; ++k)
     proc |= (cube_processed(g, i, x, y, z, (k & 1) - 1, ((k >> 1) & 1) - 1, ((k >> 2) & 1) - 1) ? 1u : 0u) << k;
-  const float v0 = g.v[i];
-  const bool in0 = v0 > g.level;
-  unsigned bits = 0;
-  bool corner = false;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    // the cubes around an axis-a edge from this point have d_a = 1, those around the edge into it d_a = 0
-    unsigned up = 0, down = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) ((k >> a) & 1 ? up : down) |= proc & (1u << k);
-    if (p[a] + 1 < dim[a] && up) {
-      const float v1 = g.v[i + stride[a]];
-      if (in0 != (v1 > g.level)) {
-        if (in0 ? v1 != g.level : v0 != g.level) bits |= 2u << a;
-        else if (!in0) corner = true;  // collapses onto this point
-      }
-    }
-    if (p[a] > 0 && down && v0 == g.level && g.v[i - stride[a]] > g.level) corner = true;
-  }
-  bits |= corner ? 1u : 0u;
-  if (proc & 0x80u) {  // cube (x, y, z) itself
-    float c[8];
-    const int cs = cube_case(g, i, c);
-    if (cs != 0 && cs != 255) bits |= (unsigned)cube_tri_count(c, g.level, cs) << 4;
-  }
-  return (unsigned char)bits;
+  return proc;
 }
 
 // The classify launch has 8 * ceil(tiles / 8) blocks; blocks that share an XCD (the same blockIdx % 8) take one contiguous eighth
@@ -121,6 +82,7 @@ __global__ __launch_bounds__(MC_THREADS) void k_mc_classify(McGrid g, long long 
   const long long tile = (long long)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
   if (tile >= tiles) return;
   const long long base = tile * MC_TILE;
+  const FieldView<long long> f = grid_view(g);
   int nv = 0, nf = 0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -130,30 +92,19 @@ __global__ __launch_bounds__(MC_THREADS) void k_mc_classify(McGrid g, long long 
     if (i < g.N) {
       long long x, y, z;
       point_xyz(g, base, o, x, y, z);
-      b = classify_point(g, i, x, y, z);
+      b = classify_bits(f, i, cubes_processed(g, i, x, y, z));
     }
     packed[i] = b;  // (the tail of the last tile is written as zeros: the emit passes read whole tiles)
     nv += __popc(b & 15u);
     nf += b >> 4;
   }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) {
-    nv += __shfl_xor(nv, o, 64);
-    nf += __shfl_xor(nf, o, 64);
-  }
-  if (lane == 0) {
-    red[0][w] = nv;
-    red[1][w] = nf;
-  }
-  __syncthreads();
+  block_sum2(nv, nf, red);
   if (threadIdx.x == 0) {
-    const int sv = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    const int sf = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    tile_v[tile] = sv;
-    tile_f[tile] = sf;
+    tile_v[tile] = nv;
+    tile_f[tile] = nf;
     // integer totals for the host's size query (order-independent: no output position depends on them)
-    if (sv) atomicAdd(totals, (unsigned long long)sv);
-    if (sf) atomicAdd(totals + 1, (unsigned long long)sf);
+    if (nv) atomicAdd(totals, (unsigned long long)nv);
+    if (nf) atomicAdd(totals + 1, (unsigned long long)nf);
   }
 }
 
@@ -209,32 +160,15 @@ __global__ __launch_bounds__(MC_THREADS) void k_mc_emit_faces(McGrid g, const un
   int total;
   long long fid = tile_fbase[blockIdx.x] + block_excl_scan((int)fcnt, total, lds4);
   if (!fcnt) return;
-  const long long sx = g.Y * g.Z, sy = g.Z;
+  const FieldView<long long> f = grid_view(g);
+  const VertexIds<long long> ids = {vbase, packed};
   for (int k = 0; k < 4; ++k) {
     if (!((w4 >> (8 * k + 4)) & 15u)) continue;
-    const long long i = i0 + k;
-    float c[8];
-    const int cs = cube_case(g, i, c);
-    const int nt = MC_NTRI[cs];
-    for (int t = 0; t < nt; ++t) {
-      const int e[3] = {MC_TRI[cs][3 * t], MC_TRI[cs][3 * t + 1], MC_TRI[cs][3 * t + 2]};
-      if (tri_degenerate(c, g.level, e[0], e[1], e[2])) continue;
+    cube_triangles(f, i0 + k, ids, [&](int, const int id[3]) {
 #pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const int col = edge_collapse(c, g.level, e[j]);
-        int id;
-        if (col >= 0) {
-          id = vbase[i + (col & 1) * sx + ((col >> 1) & 1) * sy + ((col >> 2) & 1)];  // (the corner vertex comes first)
-        } else {
-          const int c0 = MC_EDGE_BASE[e[j]], a = e[j] >> 2;
-          const long long o = i + (c0 & 1) * sx + ((c0 >> 1) & 1) * sy + ((c0 >> 2) & 1);
-          const unsigned ob = packed[o] & 15u;
-          id = vbase[o] + __popc(ob & ((2u << a) - 1u));
-        }
-        faces[3 * fid + j] = id;
-      }
+      for (int j = 0; j < 3; ++j) faces[3 * fid + j] = id[j];
       ++fid;
-    }
+    });
   }
 }
 
@@ -248,27 +182,20 @@ struct McWork {
   size_t bytes;
 };
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-McWork mc_layout(char* base, long long N, hipStream_t st) {
-  const long long tiles = (N + MC_TILE - 1) / MC_TILE;
+McWork mc_layout(void* base, long long N, hipStream_t st) {
+  const size_t tiles = (size_t)((N + MC_TILE - 1) / MC_TILE);
   McWork w = {};
-  size_t off = 0;
-  auto take = [&](size_t b) {
-    char* p = base ? base + off : nullptr;
-    off += align256(b);
-    return p;
-  };
-  w.packed = (unsigned char*)take((size_t)tiles * MC_TILE);
-  w.vbase = (int*)take((size_t)N * 4);
-  w.tile_v = (int*)take((size_t)tiles * 4);
-  w.tile_f = (int*)take((size_t)tiles * 4);
-  w.tile_vbase = (int*)take((size_t)tiles * 4);
-  w.tile_fbase = (int*)take((size_t)tiles * 4);
-  w.totals = (unsigned long long*)take(16);
-  (void)shine::prim_scan_int(nullptr, w.scan_bytes, nullptr, nullptr, (size_t)tiles, st);
-  w.scan_tmp = take(w.scan_bytes);
-  w.bytes = off;
+  shine::Arena a(base);
+  w.packed = a.take<unsigned char>(tiles * MC_TILE);
+  w.vbase = a.take<int>((size_t)N);
+  w.tile_v = a.take<int>(tiles);
+  w.tile_f = a.take<int>(tiles);
+  w.tile_vbase = a.take<int>(tiles);
+  w.tile_fbase = a.take<int>(tiles);
+  w.totals = a.take<unsigned long long>(2);
+  (void)shine::prim_scan_int(nullptr, w.scan_bytes, nullptr, nullptr, tiles, st);
+  w.scan_tmp = a.take<char>(w.scan_bytes);
+  w.bytes = a.bytes();
   return w;
 }
 
@@ -290,7 +217,7 @@ extern "C" int shine_mc_count(const float* sdf, const uint8_t* mask, int64_t nx,
     return SHINE_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
   const long long N = nx * ny * nz;
-  McWork w = mc_layout((char*)workspace, N, st);
+  McWork w = mc_layout(workspace, N, st);
   if (!workspace) {
     *workspace_bytes = w.bytes;
     return SHINE_OK;
@@ -305,18 +232,8 @@ extern "C" int shine_mc_count(const float* sdf, const uint8_t* mask, int64_t nx,
   hipLaunchKernelGGL(k_mc_classify, dim3((unsigned)(8 * ((tiles + 7) / 8))), dim3(MC_THREADS), 0, st, g, (long long)tiles, w.packed,
                      w.tile_v, w.tile_f, w.totals);
   SHINE_HIP_CHECK(hipGetLastError());
-  size_t sb = w.scan_bytes;
-  SHINE_HIP_CHECK(shine::prim_scan_int(w.scan_tmp, sb, w.tile_v, w.tile_vbase, (size_t)tiles, st));
-  sb = w.scan_bytes;
-  SHINE_HIP_CHECK(shine::prim_scan_int(w.scan_tmp, sb, w.tile_f, w.tile_fbase, (size_t)tiles, st));
-  unsigned long long tot[2] = {0, 0};
-  SHINE_HIP_CHECK(hipMemcpyAsync(tot, w.totals, 16, hipMemcpyDeviceToHost, st));
-  SHINE_HIP_CHECK(hipStreamSynchronize(st));
-  counts_out[0] = (int64_t)tot[0];
-  counts_out[1] = (int64_t)tot[1];
-  if (tot[0] >= (1ull << 31) || tot[1] >= (1ull << 31))
-    return shine::set_error(SHINE_E_INVALID, "shine_mc_count: the mesh has 2^31 or more vertices or faces (int32 ids)");
-  return SHINE_OK;
+  return scan_and_read_totals(w.tile_v, w.tile_vbase, w.tile_f, w.tile_fbase, (size_t)tiles, w.scan_tmp, w.scan_bytes, w.totals, counts_out,
+                              "shine_mc_count: the mesh has 2^31 or more vertices or faces (int32 ids)", st);
 }
 
 extern "C" int shine_mc_emit(const float* sdf, const uint8_t* mask, int64_t nx, int64_t ny, int64_t nz, float level,
@@ -326,7 +243,7 @@ extern "C" int shine_mc_emit(const float* sdf, const uint8_t* mask, int64_t nx, 
   hipStream_t st = (hipStream_t)stream;
   const long long N = nx * ny * nz;
   if (N == 0) return SHINE_OK;
-  McWork w = mc_layout((char*)workspace, N, st);
+  McWork w = mc_layout(workspace, N, st);
   if (!workspace || workspace_bytes < w.bytes) return shine::set_error(SHINE_E_INVALID, "shine_mc_emit: workspace too small");
   if (!verts_out || !faces_out) return shine::set_error(SHINE_E_INVALID, "shine_mc_emit: null output");
   const long long tiles = (N + MC_TILE - 1) / MC_TILE;

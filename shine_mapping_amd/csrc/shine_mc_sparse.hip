@@ -1,8 +1,8 @@
 // shine_mc_sparse.hip — marching cubes over a BRICK SET: n bricks of B^3 fp32 values (+ an optional B^3 mask) at B-aligned
 // origins inside a virtual grid [X, Y, Z] that is never allocated.  A grid point no brick covers has value 0 and mask 0 — the
 // zero fill of the dense grid Mesher.octree_grid_device assembles — and the result is, bit for bit, what shine_mc.hip gives on
-// that dense grid: same rules (DESIGN.md "Meshing", shine_mc_rules.hpp), same tables, same output order.  Memory is
-// proportional to the bricks and to the surface, not to X * Y * Z.
+// that dense grid: the same rules (DESIGN.md "Meshing"; shine_mc_rules.hpp, instantiated over a view of LDS), tables and order.
+// Memory is proportional to the bricks and to the surface, not to X * Y * Z.
 //
 // Every cube belongs to the brick that holds its lowest corner, so only that brick's mask decides whether it is processed; the
 // cubes on a brick's +x / +y / +z faces read values of up to 7 neighbour bricks (or zeros).  One workgroup per brick stages
@@ -70,55 +70,18 @@ __device__ __forceinline__ bool sp_processed(const SpGrid& g, long long b, long 
   return !g.mask || g.mask[b * ((long long)B * B * B) + (cx * B + cy) * B + cz] != 0;
 }
 
-__device__ __forceinline__ int sp_cube_case(const SpGrid& g, const float* sv, int a, float c[8]) {
-  const int sx = g.B1 * g.B1, sy = g.B1;
-  int cs = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    c[k] = sv[a + (k & 1) * sx + ((k >> 1) & 1) * sy + ((k >> 2) & 1)];
-    cs |= (c[k] > g.level ? 1 : 0) << k;
-  }
-  return cs;
-}
+__device__ __forceinline__ FieldView<int> brick_view(const SpGrid& g, const float* sv) { return {sv, g.B1 * g.B1, g.B1, g.level}; }
 
-// Apron point a = (lx, ly, lz): bits 0-3 = this brick's processed cubes use its corner vertex / +x / +y / +z edge vertex;
-// bits 4-7 = triangles of cube (lx, ly, lz).  shine_mc.hip's classify_point with the cubes of other bricks left out.
-__device__ unsigned char sp_classify(const SpGrid& g, const float* sv, long long b, long long ox, long long oy, long long oz, int a) {
+// the processed flags of the 8 cubes that contain apron point a = (lx, ly, lz), the cubes of other bricks left out: bit
+// (dx | dy << 1 | dz << 2) = cube (lx-1+dx, ly-1+dy, lz-1+dz).  (A processed cube of this brick has all its corners in the apron.)
+__device__ __forceinline__ unsigned sp_cubes_processed(const SpGrid& g, long long b, long long ox, long long oy, long long oz, int a) {
   const int B1 = g.B1;
   const int lz = a % B1, r = a / B1, ly = r % B1, lx = r / B1;
   unsigned proc = 0;
 #pragma unroll
   for (int k = 0; k < 8; ++k)
     proc |= (sp_processed(g, b, ox, oy, oz, lx - 1 + (k & 1), ly - 1 + ((k >> 1) & 1), lz - 1 + ((k >> 2) & 1)) ? 1u : 0u) << k;
-  if (!proc) return 0;
-  const int stride[3] = {B1 * B1, B1, 1};
-  const float v0 = sv[a];
-  const bool in0 = v0 > g.level;
-  unsigned bits = 0;
-  bool corner = false;
-#pragma unroll
-  for (int ax = 0; ax < 3; ++ax) {
-    // the cubes around the axis edge FROM this point have d = 1 on that axis, those around the edge INTO it d = 0; a processed
-    // cube of this brick on the far side implies that the far point lies in the apron and in the grid
-    unsigned up = 0, down = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) ((k >> ax) & 1 ? up : down) |= proc & (1u << k);
-    if (up) {
-      const float v1 = sv[a + stride[ax]];
-      if (in0 != (v1 > g.level)) {
-        if (in0 ? v1 != g.level : v0 != g.level) bits |= 2u << ax;
-        else if (!in0) corner = true;  // collapses onto this point
-      }
-    }
-    if (down && v0 == g.level && sv[a - stride[ax]] > g.level) corner = true;
-  }
-  bits |= corner ? 1u : 0u;
-  if (proc & 0x80u) {  // cube (lx, ly, lz) itself
-    float c[8];
-    const int cs = sp_cube_case(g, sv, a, c);
-    if (cs != 0 && cs != 255) bits |= (unsigned)cube_tri_count(c, g.level, cs) << 4;
-  }
-  return (unsigned char)bits;
+  return proc;
 }
 
 template <int CAP>
@@ -141,31 +104,21 @@ __global__ __launch_bounds__(SP_THREADS) void k_sp_classify(SpGrid g, unsigned c
     return;
   }
   const long long ox = g.org[3 * b], oy = g.org[3 * b + 1], oz = g.org[3 * b + 2];
+  const FieldView<int> f = brick_view(g, sv);
   int nv = 0, nf = 0;
   for (int a = threadIdx.x; a < n1; a += SP_THREADS) {
-    const unsigned char c = sp_classify(g, sv, b, ox, oy, oz, a);
+    const unsigned char c = classify_bits(f, a, sp_cubes_processed(g, b, ox, oy, oz, a));
     packed[b * n1 + a] = c;
     nv += __popc(c & 15u);
     nf += c >> 4;
   }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) {
-    nv += __shfl_xor(nv, o, 64);
-    nf += __shfl_xor(nf, o, 64);
-  }
-  if (lane == 0) {
-    red[0][w] = nv;
-    red[1][w] = nf;
-  }
-  __syncthreads();
+  block_sum2(nv, nf, red);
   if (threadIdx.x == 0) {
-    const int tv = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    const int tf = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    brick_v[b] = tv;
-    brick_f[b] = tf;
+    brick_v[b] = nv;
+    brick_f[b] = nf;
     // integer totals for the host's size query (order-independent: no output position depends on them)
-    if (tv) atomicAdd(totals, (u64)tv);
-    if (tf) atomicAdd(totals + 1, (u64)tf);
+    if (nv) atomicAdd(totals, (u64)nv);
+    if (nf) atomicAdd(totals + 1, (u64)nf);
   }
 }
 
@@ -220,6 +173,8 @@ __global__ __launch_bounds__(SP_THREADS) void k_sp_emit(SpGrid g, const unsigned
   }
   if (brick_f[b] == 0) return;
   __syncthreads();  // the record ids above are read back by other lanes
+  const FieldView<int> f = brick_view(g, sv);
+  const VertexIds<int> ids = {vb, pk};
   long long frun = brick_fbase[b];
   for (int a0 = 0; a0 < n1; a0 += SP_THREADS) {
     const int a = a0 + threadIdx.x;
@@ -230,29 +185,13 @@ __global__ __launch_bounds__(SP_THREADS) void k_sp_emit(SpGrid g, const unsigned
     if (!cnt) continue;
     const int lz = a % B1, r = a / B1, ly = r % B1, lx = r / B1;
     const u64 lin = (u64)(((ox + lx) * g.Y + (oy + ly)) * g.Z + (oz + lz));
-    float c[8];
-    const int cs = sp_cube_case(g, sv, a, c);
-    const int nt = MC_NTRI[cs];
-    for (int t = 0; t < nt; ++t) {
-      const int e[3] = {MC_TRI[cs][3 * t], MC_TRI[cs][3 * t + 1], MC_TRI[cs][3 * t + 2]};
-      if (tri_degenerate(c, g.level, e[0], e[1], e[2])) continue;
+    cube_triangles(f, a, ids, [&](int t, const int id[3]) {
 #pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const int col = edge_collapse(c, g.level, e[j]);
-        int id;
-        if (col >= 0) {
-          id = vb[a + (col & 1) * stride[0] + ((col >> 1) & 1) * stride[1] + ((col >> 2) & 1)];  // (the corner vertex comes first)
-        } else {
-          const int c0 = MC_EDGE_BASE[e[j]], ax = e[j] >> 2;
-          const int q = a + (c0 & 1) * stride[0] + ((c0 >> 1) & 1) * stride[1] + ((c0 >> 2) & 1);
-          id = vb[q] + __popc((pk[q] & 15u) & ((2u << ax) - 1u));
-        }
-        o.frec[3 * fid + j] = id;
-      }
+      for (int j = 0; j < 3; ++j) o.frec[3 * fid + j] = id[j];
       o.fkeys[fid] = lin * 8 + (u64)t;
       o.fvals[fid] = (u64)fid;
       ++fid;
-    }
+    });
   }
 }
 
@@ -299,8 +238,6 @@ __global__ __launch_bounds__(SP_THREADS) void k_sp_write_faces(const u64* __rest
   }
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct SpWork {  // the count call's workspace: proportional to the bricks
   long long* org;
   int* nbr;
@@ -313,27 +250,22 @@ struct SpWork {  // the count call's workspace: proportional to the bricks
   size_t bytes;
 };
 
-SpWork sp_layout(char* base, long long n, int B, hipStream_t st) {
-  const size_t n1 = (size_t)(B + 1) * (B + 1) * (B + 1);
+SpWork sp_layout(void* base, long long n_bricks, int B, hipStream_t st) {
+  const size_t n = (size_t)n_bricks, n1 = (size_t)(B + 1) * (B + 1) * (B + 1);
   SpWork w = {};
-  size_t off = 0;
-  auto take = [&](size_t b) {
-    char* p = base ? base + off : nullptr;
-    off += align256(b);
-    return p;
-  };
-  w.org = (long long*)take((size_t)n * 24);
-  w.nbr = (int*)take((size_t)n * 32);
-  w.packed = (unsigned char*)take((size_t)n * n1);
-  w.vbase = (int*)take((size_t)n * n1 * 4);
-  w.brick_v = (int*)take((size_t)n * 4);
-  w.brick_f = (int*)take((size_t)n * 4);
-  w.brick_vbase = (int*)take((size_t)n * 4);
-  w.brick_fbase = (int*)take((size_t)n * 4);
-  w.totals = (u64*)take(16);
-  (void)shine::prim_scan_int(nullptr, w.scan_bytes, nullptr, nullptr, (size_t)n, st);
-  w.scan_tmp = take(w.scan_bytes);
-  w.bytes = off;
+  shine::Arena a(base);
+  w.org = a.take<long long>(n * 3);
+  w.nbr = a.take<int>(n * 8);
+  w.packed = a.take<unsigned char>(n * n1);
+  w.vbase = a.take<int>(n * n1);
+  w.brick_v = a.take<int>(n);
+  w.brick_f = a.take<int>(n);
+  w.brick_vbase = a.take<int>(n);
+  w.brick_fbase = a.take<int>(n);
+  w.totals = a.take<u64>(2);
+  (void)shine::prim_scan_int(nullptr, w.scan_bytes, nullptr, nullptr, n, st);
+  w.scan_tmp = a.take<char>(w.scan_bytes);
+  w.bytes = a.bytes();
   return w;
 }
 
@@ -355,34 +287,30 @@ unsigned key_bits(u64 max_key) {
   return b;
 }
 
-SpScratch sp_scratch(char* base, long long C, long long F, unsigned vbits, unsigned fbits, hipStream_t st) {
+SpScratch sp_scratch(void* base, long long n_records, long long n_faces, unsigned vbits, unsigned fbits, hipStream_t st) {
+  const size_t C = (size_t)n_records, F = (size_t)n_faces;
   SpScratch s = {};
-  size_t off = 0;
-  auto take = [&](size_t b) {
-    char* p = base ? base + off : nullptr;
-    off += align256(b);
-    return p;
-  };
-  s.vkeys = (u64*)take((size_t)C * 8);
-  s.vvals = (u64*)take((size_t)C * 8);
-  s.vkeys_s = (u64*)take((size_t)C * 8);
-  s.vvals_s = (u64*)take((size_t)C * 8);
-  s.head = (unsigned char*)take((size_t)C);
-  s.excl = (int*)take((size_t)C * 4);
-  s.rank = (int*)take((size_t)C * 4);
-  s.fkeys = (u64*)take((size_t)F * 8);
-  s.fvals = (u64*)take((size_t)F * 8);
-  s.fkeys_s = (u64*)take((size_t)F * 8);
-  s.fvals_s = (u64*)take((size_t)F * 8);
-  s.frec = (int*)take((size_t)F * 12);
-  s.n_verts = (long long*)take(8);
-  size_t a = 0, b = 0, c = 0;
-  (void)shine::prim_sort_pairs_u64(nullptr, a, nullptr, nullptr, nullptr, nullptr, (size_t)C, 0u, vbits, st);
-  (void)shine::prim_sort_pairs_u64(nullptr, b, nullptr, nullptr, nullptr, nullptr, (size_t)F, 0u, fbits, st);
-  (void)shine::prim_scan_flags(nullptr, c, nullptr, nullptr, (size_t)C, st);
-  s.tmp_bytes = std::max(a, std::max(b, c));
-  s.tmp = take(s.tmp_bytes);
-  s.bytes = off;
+  shine::Arena a(base);
+  s.vkeys = a.take<u64>(C);
+  s.vvals = a.take<u64>(C);
+  s.vkeys_s = a.take<u64>(C);
+  s.vvals_s = a.take<u64>(C);
+  s.head = a.take<unsigned char>(C);
+  s.excl = a.take<int>(C);
+  s.rank = a.take<int>(C);
+  s.fkeys = a.take<u64>(F);
+  s.fvals = a.take<u64>(F);
+  s.fkeys_s = a.take<u64>(F);
+  s.fvals_s = a.take<u64>(F);
+  s.frec = a.take<int>(F * 3);
+  s.n_verts = a.take<long long>(1);
+  size_t sort_v = 0, sort_f = 0, scan = 0;
+  (void)shine::prim_sort_pairs_u64(nullptr, sort_v, nullptr, nullptr, nullptr, nullptr, C, 0u, vbits, st);
+  (void)shine::prim_sort_pairs_u64(nullptr, sort_f, nullptr, nullptr, nullptr, nullptr, F, 0u, fbits, st);
+  (void)shine::prim_scan_flags(nullptr, scan, nullptr, nullptr, C, st);
+  s.tmp_bytes = std::max(sort_v, std::max(sort_f, scan));
+  s.tmp = a.take<char>(s.tmp_bytes);
+  s.bytes = a.bytes();
   return s;
 }
 
@@ -456,7 +384,7 @@ extern "C" int shine_mc_sparse_count(const float* values, const uint8_t* mask, c
   try {
     std::vector<int> nbr;
     if (sp_brick_table(origins, n, brick, nx, ny, nz, nbr)) return SHINE_E_INVALID;
-    SpWork w = sp_layout((char*)workspace, n, brick, st);
+    SpWork w = sp_layout(workspace, n, brick, st);
     if (!workspace) {
       *workspace_bytes = w.bytes;
       return SHINE_OK;
@@ -474,18 +402,8 @@ extern "C" int shine_mc_sparse_count(const float* values, const uint8_t* mask, c
     if ((brick + 1) * (brick + 1) * (brick + 1) <= SP_CAP_SMALL) launch_classify<SP_CAP_SMALL>(g, n, w, st);
     else launch_classify<SP_CAP_LARGE>(g, n, w, st);
     SHINE_HIP_CHECK(hipGetLastError());
-    size_t sb = w.scan_bytes;
-    SHINE_HIP_CHECK(shine::prim_scan_int(w.scan_tmp, sb, w.brick_v, w.brick_vbase, (size_t)n, st));
-    sb = w.scan_bytes;
-    SHINE_HIP_CHECK(shine::prim_scan_int(w.scan_tmp, sb, w.brick_f, w.brick_fbase, (size_t)n, st));
-    u64 tot[2] = {0, 0};
-    SHINE_HIP_CHECK(hipMemcpyAsync(tot, w.totals, 16, hipMemcpyDeviceToHost, st));
-    SHINE_HIP_CHECK(hipStreamSynchronize(st));
-    counts_out[0] = (int64_t)tot[0];
-    counts_out[1] = (int64_t)tot[1];
-    if (tot[0] >= (1ull << 31) || tot[1] >= (1ull << 31))
-      return shine::set_error(SHINE_E_INVALID, "shine_mc_sparse_count: the mesh has 2^31 or more vertex records or faces (int32 ids)");
-    return SHINE_OK;
+    return scan_and_read_totals(w.brick_v, w.brick_vbase, w.brick_f, w.brick_fbase, (size_t)n, w.scan_tmp, w.scan_bytes, w.totals,
+                                counts_out, "shine_mc_sparse_count: the mesh has 2^31 or more vertex records or faces (int32 ids)", st);
   } catch (const std::bad_alloc&) {
     return shine::set_error(SHINE_E_NOMEM, "shine_mc_sparse_count: out of host memory for the brick table");
   }
@@ -503,7 +421,7 @@ extern "C" int shine_mc_sparse_emit(const float* values, const uint8_t* mask, in
   const long long C = n_records, F = n_faces;
   const u64 points = (u64)nx * (u64)ny * (u64)nz;
   const unsigned vbits = key_bits(points * 4 - 1), fbits = key_bits(points * 8 - 1);
-  SpScratch s = sp_scratch((char*)scratch, C, F, vbits, fbits, st);
+  SpScratch s = sp_scratch(scratch, C, F, vbits, fbits, st);
   if (!scratch) {
     *scratch_bytes = s.bytes;
     return SHINE_OK;
@@ -514,7 +432,7 @@ extern "C" int shine_mc_sparse_emit(const float* values, const uint8_t* mask, in
   if (C == 0) return shine::set_error(SHINE_E_INVALID, "shine_mc_sparse_emit: faces without vertex records");
   if (!verts_out || (F > 0 && !faces_out)) return shine::set_error(SHINE_E_INVALID, "shine_mc_sparse_emit: null output");
   if (*scratch_bytes < s.bytes) return shine::set_error(SHINE_E_INVALID, "shine_mc_sparse_emit: scratch too small");
-  SpWork w = sp_layout((char*)workspace, n, brick, st);
+  SpWork w = sp_layout(workspace, n, brick, st);
   if (!workspace || workspace_bytes < w.bytes) return shine::set_error(SHINE_E_INVALID, "shine_mc_sparse_emit: workspace too small");
   SpGrid g = {values, mask, w.org, w.nbr, nx, ny, nz, brick, brick + 1, level};
   SpRecords o = {s.vkeys, s.vvals, s.fkeys, s.fvals, s.frec};

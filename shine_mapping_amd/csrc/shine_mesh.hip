@@ -17,23 +17,11 @@ constexpr int T = 256;
 
 unsigned grid_of(long long n) { return (unsigned)((n + T - 1) / T); }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 unsigned bits_for(long long n) {  // bits that hold 0..n-1
   unsigned b = 1;
   while (b < 63 && (1ll << b) < n) ++b;
   return b;
 }
-
-struct Carve {
-  char* base;
-  size_t off = 0;
-  void* take(size_t b) {
-    char* p = base ? base + off : nullptr;
-    off += align256(b);
-    return p;
-  }
-};
 
 // ---------------------------------------------------------------- normals
 __global__ void k_face_normals(const double* __restrict__ v, const int* __restrict__ f, long long nf, double* __restrict__ fn,
@@ -176,21 +164,21 @@ extern "C" int shine_mesh_vertex_normals(const double* verts, int64_t n_verts, c
     return shine::set_error(SHINE_E_INVALID, "shine_mesh_vertex_normals: bad sizes (V and F must be < 2^31)");
   hipStream_t st = (hipStream_t)stream;
   const long long nk = 3 * n_faces;
-  Carve c{(char*)workspace};
-  auto* k0 = (unsigned long long*)c.take(nk * 8);
-  auto* k1 = (unsigned long long*)c.take(nk * 8);
-  auto* fn = (double*)c.take(nk * 8);
-  auto* start = (long long*)c.take(n_verts * 8);
-  auto* end = (long long*)c.take(n_verts * 8);
+  shine::Arena c(workspace);
+  auto* k0 = c.take<unsigned long long>(nk);
+  auto* k1 = c.take<unsigned long long>(nk);
+  auto* fn = c.take<double>(nk);
+  auto* start = c.take<long long>(n_verts);
+  auto* end = c.take<long long>(n_verts);
   size_t sort_bytes = 0;
   const unsigned end_bit = 32 + bits_for(n_verts);
   SHINE_HIP_CHECK(shine::prim_sort_keys_u64(nullptr, sort_bytes, nullptr, nullptr, (size_t)nk, 0u, end_bit, st));
-  void* tmp = c.take(sort_bytes);
+  void* tmp = c.take<char>(sort_bytes);
   if (!workspace) {
-    *workspace_bytes = c.off;
+    *workspace_bytes = c.bytes();
     return SHINE_OK;
   }
-  if (*workspace_bytes < c.off) return shine::set_error(SHINE_E_INVALID, "shine_mesh_vertex_normals: workspace too small");
+  if (*workspace_bytes < c.bytes()) return shine::set_error(SHINE_E_INVALID, "shine_mesh_vertex_normals: workspace too small");
   if (n_verts == 0) return SHINE_OK;
   if (!verts || !normals_out || (n_faces && !faces)) return shine::set_error(SHINE_E_INVALID, "shine_mesh_vertex_normals: null argument");
   SHINE_HIP_CHECK(hipMemsetAsync(start, 0, n_verts * 8, st));
@@ -214,28 +202,28 @@ extern "C" int shine_mesh_cluster_filter(const int32_t* faces, int64_t n_faces, 
     return shine::set_error(SHINE_E_INVALID, "shine_mesh_cluster_filter: bad size (F must be < 2^31)");
   hipStream_t st = (hipStream_t)stream;
   const long long nk = 3 * n_faces;
-  Carve c{(char*)workspace};
-  auto* k0 = (unsigned long long*)c.take(nk * 8);
-  auto* k1 = (unsigned long long*)c.take(nk * 8);
-  auto* v0 = (unsigned long long*)c.take(nk * 8);
-  auto* v1 = (unsigned long long*)c.take(nk * 8);
-  int* parent = (int*)c.take(n_faces * 4);
-  int* rank = (int*)c.take(n_faces * 4);
-  int* cluster = (int*)c.take(n_faces * 4);
-  int* counts = (int*)c.take(n_faces * 4);
-  int* pos = (int*)c.take(n_faces * 4);
-  auto* flags = (unsigned char*)c.take(n_faces);
-  int* changed = (int*)c.take(4);
+  shine::Arena c(workspace);
+  auto* k0 = c.take<unsigned long long>(nk);
+  auto* k1 = c.take<unsigned long long>(nk);
+  auto* v0 = c.take<unsigned long long>(nk);
+  auto* v1 = c.take<unsigned long long>(nk);
+  int* parent = c.take<int>(n_faces);
+  int* rank = c.take<int>(n_faces);
+  int* cluster = c.take<int>(n_faces);
+  int* counts = c.take<int>(n_faces);
+  int* pos = c.take<int>(n_faces);
+  auto* flags = c.take<unsigned char>(n_faces);
+  int* changed = c.take<int>(1);
   size_t sort_bytes = 0, scan_bytes = 0;
   SHINE_HIP_CHECK(shine::prim_sort_pairs_u64(nullptr, sort_bytes, nullptr, nullptr, nullptr, nullptr, (size_t)nk, 0u, 64u, st));
   SHINE_HIP_CHECK(shine::prim_scan_flags(nullptr, scan_bytes, nullptr, nullptr, (size_t)n_faces, st));
   const size_t tmp_bytes = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-  void* tmp = c.take(tmp_bytes);
+  void* tmp = c.take<char>(tmp_bytes);
   if (!workspace) {
-    *workspace_bytes = c.off;
+    *workspace_bytes = c.bytes();
     return SHINE_OK;
   }
-  if (*workspace_bytes < c.off) return shine::set_error(SHINE_E_INVALID, "shine_mesh_cluster_filter: workspace too small");
+  if (*workspace_bytes < c.bytes()) return shine::set_error(SHINE_E_INVALID, "shine_mesh_cluster_filter: workspace too small");
   if (!kept_out) return shine::set_error(SHINE_E_INVALID, "shine_mesh_cluster_filter: null kept_out");
   *kept_out = 0;
   if (n_faces == 0) return SHINE_OK;

@@ -432,12 +432,7 @@ class Mesher:
     def get_query_from_bbx(self, bbx, voxel_size):
         """utils/mesher.py:110-152: grid query points of a box (anything with get_min_bound()/get_max_bound(), e.g. an
         open3d AxisAlignedBoundingBox), padded, one extra layer underground; same fp32 op order, built on the device."""
-        min_bound = np.asarray(bbx.get_min_bound(), dtype=np.float64).copy()
-        max_bound = np.asarray(bbx.get_max_bound(), dtype=np.float64)
-        voxel_num_xyz = (np.ceil((max_bound - min_bound) / voxel_size) + self.config.pad_voxel * 2).astype(np.int_)
-        voxel_origin = min_bound - self.config.pad_voxel * voxel_size
-        voxel_origin[2] -= voxel_size
-        voxel_num_xyz[2] += 1
+        voxel_num_xyz, voxel_origin = self._bbx_layout(bbx, voxel_size)
         dev = self.octree.hier_features[0].device if len(self.octree.hier_features) else self.device
         x = torch.arange(int(voxel_num_xyz[0]), dtype=torch.int16, device=dev)
         y = torch.arange(int(voxel_num_xyz[1]), dtype=torch.int16, device=dev)
@@ -617,7 +612,7 @@ class Mesher:
         return min(self.octree.featured_level_num, self.config.mc_vis_level) - 1
 
     def _bbx_layout(self, bbx, voxel_size):
-        """get_query_from_bbx's grid without its points: (shape [3], voxel_origin [3] metres)"""
+        """utils/mesher.py:113-121: the box grid, padded, one extra layer underground: (shape [3], voxel_origin [3] metres)"""
         min_bound = np.asarray(bbx.get_min_bound(), dtype=np.float64).copy()
         max_bound = np.asarray(bbx.get_max_bound(), dtype=np.float64)
         shape = (np.ceil((max_bound - min_bound) / voxel_size) + self.config.pad_voxel * 2).astype(np.int_)
@@ -665,6 +660,22 @@ class Mesher:
                 mask[h:t] = m.view(-1, B, B, B)
         return values, mask, origins, tuple(int(v) for v in shape), voxel_origin
 
+    def _recon(self, sparse, fits_shape, per_point_extra, dense_fn, brick_fn, *finish):
+        """what recon_bbx_mesh and recon_octree_mesh share: the route (`sparse` None: bricks iff the dense grid of fits_shape(), a
+        shape or None for "do not ask", does not fit), the route's marching cubes — dense_fn / brick_fn return (verts, faces,
+        voxel size m, origin m) — and _finish with its remaining arguments `finish`."""
+        if getattr(self.config, "time_conditioned", False):
+            raise NotImplementedError("time-conditioned decoding is outside the SDF hot path")
+        if sparse is None:
+            shape = fits_shape()
+            if shape is not None:
+                try:
+                    ensure_grid_fits(shape, True, per_point_extra, device=self.octree.hier_features[0].device)
+                except MemoryError:
+                    sparse = True
+        verts, faces, voxel, origin = brick_fn() if sparse else dense_fn()
+        return self._finish(verts, faces, voxel, origin, *finish)
+
     def recon_bbx_mesh(self, bbx, voxel_size, mesh_path, map_path, save_map=False, estimate_sem=False, estimate_normal=True,
                        filter_isolated_mesh=True, filter_free_space_vertices=True, sparse=None):
         """utils/mesher.py:253-292 on the device: grid query -> marching cubes -> [semantics] -> [normals] -> [filter with
@@ -672,42 +683,32 @@ class Mesher:
         not fit), True = bricks (bbx_bricks_device + marching_cubes_sparse: the same mesh, memory proportional to the tiles
         near the map's nodes), None = dense when it fits, else bricks.  The brick route needs config.mc_mask_on and cannot
         save the SDF map."""
-        if getattr(self.config, "time_conditioned", False):
-            raise NotImplementedError("time-conditioned decoding is outside the SDF hot path")
-        min_bound = np.asarray(bbx.get_min_bound(), dtype=np.float64)
-        max_bound = np.asarray(bbx.get_max_bound(), dtype=np.float64)
-        shape = (np.ceil((max_bound - min_bound) / voxel_size) + self.config.pad_voxel * 2).astype(np.int_)
-        shape[2] += 1
         mask_on = bool(getattr(self.config, "mc_mask_on", True))
-        if sparse and not mask_on:
-            raise ValueError("recon_bbx_mesh: sparse=True needs config.mc_mask_on (without the mask every cube of the box is "
-                             "processed, so no tile can be left out)")
-        if sparse is None and mask_on:
-            try:
-                ensure_grid_fits(shape, mask_on, per_point_extra=12 + 6, device=self.octree.hier_features[0].device)
-            except MemoryError:
-                sparse = True
-        if sparse:
+        extra = 12 + 6  # per point, next to the grid: the query coordinates and get_query_from_bbx's int16 axes
+
+        def bricks():
+            if not mask_on:
+                raise ValueError("recon_bbx_mesh: sparse=True needs config.mc_mask_on (without the mask every cube of the box is "
+                                 "processed, so no tile can be left out)")
             if save_map:
                 raise ValueError("recon_bbx_mesh: save_map=True cannot be combined with the brick route (sparse=True, or a box "
                                  "whose dense grid does not fit): there is no sparse SDF map")
-            values, mask, origins, bshape, voxel_origin = self.bbx_bricks_device(bbx, voxel_size)
-            verts, faces = marching_cubes_sparse(values, mask, origins, bshape, 0.0)
-            del values, mask
-            return self._finish(verts, faces, voxel_size, voxel_origin, mesh_path, estimate_sem, estimate_normal,
-                                filter_isolated_mesh, filter_free_space_vertices, getattr(self.config, "min_cluster_vertices", 300))
-        ensure_grid_fits(shape, mask_on, per_point_extra=12 + 6, device=self.octree.hier_features[0].device)  # (+ the query
-        #                                                                            coordinates and get_query_from_bbx's int16 axes)
-        coord, voxel_num_xyz, voxel_origin = self.get_query_from_bbx(bbx, voxel_size)
-        sdf, mask = self._fill_grid(coord, tuple(int(v) for v in voxel_num_xyz), self._check_level(), mask_on)
-        if save_map:
-            self.generate_sdf_map(coord, sdf.reshape(-1).cpu().numpy(),
-                                  mask.reshape(-1).cpu().numpy() if mask is not None else None, map_path)
-        del coord
-        verts, faces = marching_cubes(sdf, mask, 0.0)
-        del sdf, mask
-        return self._finish(verts, faces, voxel_size, voxel_origin, mesh_path, estimate_sem, estimate_normal,
-                            filter_isolated_mesh, filter_free_space_vertices, getattr(self.config, "min_cluster_vertices", 300))
+            values, mask, origins, shape, voxel_origin = self.bbx_bricks_device(bbx, voxel_size)
+            return marching_cubes_sparse(values, mask, origins, shape, 0.0) + (voxel_size, voxel_origin)
+
+        def dense():
+            ensure_grid_fits(self._bbx_layout(bbx, voxel_size)[0], mask_on, extra, device=self.octree.hier_features[0].device)
+            coord, voxel_num_xyz, voxel_origin = self.get_query_from_bbx(bbx, voxel_size)
+            sdf, mask = self._fill_grid(coord, tuple(int(v) for v in voxel_num_xyz), self._check_level(), mask_on)
+            if save_map:
+                self.generate_sdf_map(coord, sdf.reshape(-1).cpu().numpy(),
+                                      mask.reshape(-1).cpu().numpy() if mask is not None else None, map_path)
+            del coord
+            return marching_cubes(sdf, mask, 0.0) + (voxel_size, voxel_origin)
+
+        return self._recon(sparse, lambda: self._bbx_layout(bbx, voxel_size)[0] if mask_on else None, extra, dense, bricks,
+                           mesh_path, estimate_sem, estimate_normal, filter_isolated_mesh, filter_free_space_vertices,
+                           getattr(self.config, "min_cluster_vertices", 300))
 
     def octree_grid_layout(self, query_level, mc_res_m):
         """utils/mesher.py:297-321's arithmetic (numpy, the reference's op order): (node centres [M,3] scaled, node_res_scaled,
@@ -724,73 +725,70 @@ class Mesher:
         shift = ((nodes - min_nodes) / node_res_scaled * k).astype(int)
         return nodes, node_res_scaled, k, mc_res_scaled, shape, shift
 
-    def octree_grid_device(self, query_level, mc_res_m):
-        """recon_octree_mesh's dense grid, assembled on the device: every node block of get_octree_nodes(query_level) queried at
-        once (per chunk of nodes) and scattered to its shift_coord offset, instead of one query per node (utils/mesher.py:326-337).
-        Unfilled cells stay 0 with the mask off.  The reference keeps the grid as float16 (:323); the values are rounded the same
-        way (.half().float()) so the meshes agree.  Returns (sdf [X,Y,Z] f32, mask [X,Y,Z] bool, voxel size m, origin m)."""
+    def _octree_blocks(self, query_level, mc_res_m):
+        """The node blocks of get_octree_nodes(query_level), every block queried at once per chunk of nodes instead of one query
+        per node (utils/mesher.py:326-337).  Returns (k, grid shape [3], shift_coord [M,3], voxel size m, origin m, chunks);
+        `chunks` yields (h, t, sdf, mask) for the nodes h..t-1: the blocks' (t - h) * k^3 values, block-major and (x, y, z)
+        inside a block, and their mask, None with config.mc_mask_on off.  The reference keeps its grid as float16 (:323); the
+        values are rounded the same way (.half().float()) so the meshes agree."""
         nodes, node_res_scaled, k, mc_res_scaled, shape, shift = self.octree_grid_layout(query_level, mc_res_m)
-        dev = self.octree.hier_features[0].device
-        ensure_grid_fits(shape, True, device=dev)
-        X, Y, Z = (int(v) for v in shape)
-        # the reference's node block: int16 grid coordinates, float32, times mc_res_scaled (:304-313)
-        ax = torch.arange(k, dtype=torch.int16, device=dev)
-        gx, gy, gz = torch.meshgrid(ax, ax, ax, indexing="ij")
-        block = torch.stack((gx.flatten(), gy.flatten(), gz.flatten())).transpose(0, 1).float()
-        block *= mc_res_scaled
-        block64 = block.double()
-        lin_block = ((gx.flatten().long() * Y + gy.flatten().long()) * Z + gz.flatten().long())
-        origins = torch.as_tensor(nodes - 0.5 * (node_res_scaled - mc_res_scaled), dtype=torch.float64, device=dev)
-        base = torch.as_tensor((shift[:, 0].astype(np.int64) * Y + shift[:, 1]) * Z + shift[:, 2], device=dev)
-        sdf = torch.zeros(X * Y * Z, dtype=torch.float32, device=dev)
-        mask = torch.zeros(X * Y * Z, dtype=torch.bool, device=dev)
-        mask_on = bool(getattr(self.config, "mc_mask_on", True))
-        check_level = self._check_level()
-        per = max(1, QUERY_CHUNK // (k ** 3))
-        with torch.no_grad():
+        voxel = mc_res_scaled / self.world_scale
+        origin = (np.min(nodes, 0) - 0.5 * (node_res_scaled - mc_res_scaled)) / self.world_scale
+
+        def chunks():
+            dev = self.octree.hier_features[0].device
+            # the reference's node block: int16 grid coordinates, float32, times mc_res_scaled (:304-313)
+            ax = torch.arange(k, dtype=torch.int16, device=dev)
+            gx, gy, gz = torch.meshgrid(ax, ax, ax, indexing="ij")
+            block = torch.stack((gx.flatten(), gy.flatten(), gz.flatten())).transpose(0, 1).float()
+            block *= mc_res_scaled
+            block64 = block.double()
+            origins = torch.as_tensor(nodes - 0.5 * (node_res_scaled - mc_res_scaled), dtype=torch.float64, device=dev)
+            mask_on = bool(getattr(self.config, "mc_mask_on", True))
+            check_level = self._check_level()
+            per = max(1, QUERY_CHUNK // (k ** 3))
             for h in range(0, len(nodes), per):
                 t = min(h + per, len(nodes))
                 # cur_coord += cur_origin (:329-330): a float32 tensor plus a float64 one, computed in double, stored as float32
                 coord = (block64[None] + origins[h:t, None, :]).float().reshape(-1, 3)
-                s, m = query_points_device(self.octree, self.geo_decoder, coord, check_level, True, True, mask_on)
-                idx = (base[h:t, None] + lin_block[None]).reshape(-1)
-                sdf[idx] = s.half().float()
-                if mask_on:  # (without the mask the reference assigns None, i.e. False, to its bool grid: :336)
-                    mask[idx] = m
-        voxel = mc_res_scaled / self.world_scale
-        origin = (np.min(nodes, 0) - 0.5 * (node_res_scaled - mc_res_scaled)) / self.world_scale
+                with torch.no_grad():
+                    s, m = query_points_device(self.octree, self.geo_decoder, coord, check_level, True, True, mask_on)
+                yield h, t, s.half().float(), m
+
+        return k, shape, shift, voxel, origin, chunks()
+
+    def octree_grid_device(self, query_level, mc_res_m):
+        """recon_octree_mesh's dense grid, assembled on the device: every node block (_octree_blocks) scattered to its shift_coord
+        offset.  Unfilled cells stay 0 with the mask off.  Returns (sdf [X,Y,Z] f32, mask [X,Y,Z] bool, voxel size m, origin m)."""
+        k, shape, shift, voxel, origin, chunks = self._octree_blocks(query_level, mc_res_m)
+        dev = self.octree.hier_features[0].device
+        ensure_grid_fits(shape, True, device=dev)
+        X, Y, Z = (int(v) for v in shape)
+        ax = torch.arange(k, dtype=torch.int64, device=dev)
+        lin_block = ((ax[:, None, None] * Y + ax[None, :, None]) * Z + ax[None, None, :]).reshape(-1)
+        base = torch.as_tensor((shift[:, 0].astype(np.int64) * Y + shift[:, 1]) * Z + shift[:, 2], device=dev)
+        sdf = torch.zeros(X * Y * Z, dtype=torch.float32, device=dev)
+        mask = torch.zeros(X * Y * Z, dtype=torch.bool, device=dev)
+        for h, t, s, m in chunks:
+            idx = (base[h:t, None] + lin_block[None]).reshape(-1)
+            sdf[idx] = s
+            if m is not None:  # (without the mask the reference assigns None, i.e. False, to its bool grid: :336)
+                mask[idx] = m
         return sdf.view(X, Y, Z), mask.view(X, Y, Z), voxel, origin
 
     def octree_bricks_device(self, query_level, mc_res_m):
-        """octree_grid_device's grid as bricks: every node block queried exactly as there (the same coordinates, .half().float()
-        rounding, mc_mask_on handling and chunking) and KEPT as a brick instead of being scattered into a dense grid, which is
-        never allocated.  Blocks wider than MC_SPARSE_MAX_BRICK are cut into bricks of brick_edge(k).  Returns (values
-        [n,B,B,B] f32, mask [n,B,B,B] u8, origins [n,3] int64, shape, voxel size m, origin m)."""
-        nodes, node_res_scaled, k, mc_res_scaled, shape, shift = self.octree_grid_layout(query_level, mc_res_m)
+        """octree_grid_device's grid as bricks: every node block (_octree_blocks) KEPT as a brick instead of being scattered into
+        a dense grid, which is never allocated.  Blocks wider than MC_SPARSE_MAX_BRICK are cut into bricks of brick_edge(k).
+        Returns (values [n,B,B,B] f32, mask [n,B,B,B] u8, origins [n,3] int64, shape, voxel size m, origin m)."""
+        k, shape, shift, voxel, origin, chunks = self._octree_blocks(query_level, mc_res_m)
         dev = self.octree.hier_features[0].device
         B, brick_origins = octree_brick_table(k, shift)
-        M = len(nodes)
-        ax = torch.arange(k, dtype=torch.int16, device=dev)
-        gx, gy, gz = torch.meshgrid(ax, ax, ax, indexing="ij")
-        block = torch.stack((gx.flatten(), gy.flatten(), gz.flatten())).transpose(0, 1).float()
-        block *= mc_res_scaled
-        block64 = block.double()
-        origins = torch.as_tensor(nodes - 0.5 * (node_res_scaled - mc_res_scaled), dtype=torch.float64, device=dev)
-        values = torch.empty((M, k, k, k), dtype=torch.float32, device=dev)
-        mask = torch.zeros((M, k, k, k), dtype=torch.uint8, device=dev)
-        mask_on = bool(getattr(self.config, "mc_mask_on", True))
-        check_level = self._check_level()
-        per = max(1, QUERY_CHUNK // (k ** 3))
-        with torch.no_grad():
-            for h in range(0, M, per):
-                t = min(h + per, M)
-                coord = (block64[None] + origins[h:t, None, :]).float().reshape(-1, 3)
-                s, m = query_points_device(self.octree, self.geo_decoder, coord, check_level, True, True, mask_on)
-                values[h:t] = s.half().float().view(-1, k, k, k)
-                if mask_on:
-                    mask[h:t] = m.view(-1, k, k, k)
-        voxel = mc_res_scaled / self.world_scale
-        origin = (np.min(nodes, 0) - 0.5 * (node_res_scaled - mc_res_scaled)) / self.world_scale
+        values = torch.empty((len(shift), k, k, k), dtype=torch.float32, device=dev)
+        mask = torch.zeros((len(shift), k, k, k), dtype=torch.uint8, device=dev)
+        for h, t, s, m in chunks:
+            values[h:t] = s.view(-1, k, k, k)
+            if m is not None:
+                mask[h:t] = m.view(-1, k, k, k)
         return split_blocks(values, B), split_blocks(mask, B), brick_origins, tuple(int(v) for v in shape), voxel, origin
 
     def recon_octree_mesh(self, query_level, mc_res_m, mesh_path, map_path, save_map=False, estimate_sem=False,
@@ -799,21 +797,13 @@ class Mesher:
         too; its cluster filter uses the default 300 triangles, :356).  `sparse`: False = the dense grid over the nodes'
         bounding box (MemoryError when it does not fit), True = the node blocks as bricks (octree_bricks_device +
         marching_cubes_sparse: the same mesh, memory proportional to the nodes), None = dense when it fits, else bricks."""
-        if getattr(self.config, "time_conditioned", False):
-            raise NotImplementedError("time-conditioned decoding is outside the SDF hot path")
-        if sparse is None:
-            try:
-                ensure_grid_fits(self.octree_grid_layout(query_level, mc_res_m)[4], True, device=self.octree.hier_features[0].device)
-            except MemoryError:
-                sparse = True
-        if sparse:
+        def bricks():
             values, mask, origins, shape, voxel, origin = self.octree_bricks_device(query_level, mc_res_m)
-            verts, faces = marching_cubes_sparse(values, mask, origins, shape, 0.0)
-            del values, mask
-            return self._finish(verts, faces, voxel, origin, mesh_path, estimate_sem, estimate_normal, filter_isolated_mesh,
-                                filter_free_space_vertices, 300)
-        sdf, mask, voxel, origin = self.octree_grid_device(query_level, mc_res_m)
-        verts, faces = marching_cubes(sdf, mask, 0.0)
-        del sdf, mask
-        return self._finish(verts, faces, voxel, origin, mesh_path, estimate_sem, estimate_normal, filter_isolated_mesh,
-                            filter_free_space_vertices, 300)
+            return marching_cubes_sparse(values, mask, origins, shape, 0.0) + (voxel, origin)
+
+        def dense():
+            sdf, mask, voxel, origin = self.octree_grid_device(query_level, mc_res_m)
+            return marching_cubes(sdf, mask, 0.0) + (voxel, origin)
+
+        return self._recon(sparse, lambda: self.octree_grid_layout(query_level, mc_res_m)[4], 0, dense, bricks, mesh_path,
+                           estimate_sem, estimate_normal, filter_isolated_mesh, filter_free_space_vertices, 300)

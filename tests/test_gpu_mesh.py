@@ -71,6 +71,19 @@ def test_masks_match_the_oracle():
     _same(sdf, half)
 
 
+def _tiny(shape):
+    return np.random.default_rng(0).standard_normal(shape).astype(np.float32)
+
+
+@pytest.mark.parametrize("shape,counts", [((2, 2, 2), (6, 4)), ((2, 2, 3), (12, 8)), ((1, 7, 7), (0, 0)), ((5, 1, 9), (0, 0)),
+                                          ((2, 3, 1), (0, 0))])
+def test_smallest_extents_match_the_oracle(shape, counts):
+    """one cube, two cubes, and grids too thin to hold a cube, every cube processed: each point lies on the grid's border, so the
+    only thing that keeps the classify rules from reading a neighbour outside the grid is that no processed cube lies there"""
+    v, f = _same(_tiny(shape), np.ones(shape, bool))
+    assert (len(v), len(f)) == counts
+
+
 def test_empty_surface_and_out_of_range_level():
     sdf = _smooth((20, 20, 20), 5)
     for lev in (float(sdf.max()) + 1, float(sdf.min()) - 1):

@@ -6,7 +6,7 @@ import pytest
 import torch
 
 import mc_sparse_oracle as so
-from test_gpu_mesh import _Box, _cross_zero, _mesher, _smooth, _T
+from test_gpu_mesh import _Box, _cross_zero, _mesher, _smooth, _T, _tiny
 
 pytestmark = pytest.mark.gpu
 
@@ -91,6 +91,17 @@ def test_values_on_the_level_at_brick_faces_and_corner_vertices_of_uncovered_poi
     mask = np.random.default_rng(5).random(shape) < 0.7
     values, bmask, origins = so.cut(sdf, mask, B, keep_fraction=0.6, seed=3)
     _equals_the_dense_twin(values, bmask, origins, shape)
+
+
+@pytest.mark.parametrize("B", [1, 3])
+def test_the_two_cube_grid_as_bricks(B):
+    """test_gpu_mesh's (2, 2, 3) grid with every cube processed: as twelve bricks of one point each, where every value a cube
+    reads besides its lowest corner comes from the apron, and as one brick of 3^3 that reaches beyond the grid on x and y"""
+    shape = (2, 2, 3)
+    values, bmask, origins = so.cut(_tiny(shape), np.ones(shape, bool), B)
+    assert len(origins) == (12 if B == 1 else 1)
+    v, f = _equals_the_dense_twin(values, bmask, origins, shape)
+    assert (len(v), len(f)) == (12, 8)
 
 
 def test_empty_surface_single_brick_and_no_bricks():
