@@ -60,19 +60,26 @@ typedef struct shine_next_draw {
                               shine_step_config.next_draw only */
 } shine_next_draw;
 
-/* The WHOLE next large sorted draw — and the next step's opt.zero_grad() — on the reduction launch of THIS step
- * (shine_step_config.draw_rider): a batch-mode step is then two launches, the fused kernel and this one.  The sampler's two
- * passes have a grid-wide dependency (pass 2 needs every block sum of pass 1), so they ride one step apart: step i's launch runs
- * pass 2 of draw i + 1 (whose block sums step i - 1's launch left) and pass 1 of draw i + 2.  Everything a step hands to the next
+/* The WHOLE next large sorted draw — and the next step's opt.zero_grad() — inside the two launches of THIS step
+ * (shine_step_config.draw_rider): a batch-mode step is the fused kernel and its reduction launch, nothing else.  The sampler's two
+ * passes have a grid-wide dependency (pass 2 needs every block sum of pass 1), so they ride one step apart: step i runs
+ * pass 2 of draw i + 1 (whose block sums step i - 1 left) and pass 1 of draw i + 2.  Everything a step hands to the next
  * is kept twice and addressed by the step's PARITY (steps alternate 0, 1, 0, ...):
- *   state        device uint64[2]: state[parity] = stream id of the draw THIS step used; the launch stores that + 1 into
- *                state[1 - parity] (nothing in the launch reads it)
+ *   state        device uint64[2]: state[parity] = stream id of the draw THIS step used; the step stores that + 1 into
+ *                state[1 - parity] (nothing in the step reads it)
  *   block_sum    two device double[(n + 1 + 1023) / 1024]: [1 - parity] holds pass 1 of the next draw, [parity] receives pass 1 of the
  *                draw after it
  *   surf_parts   (with surf_bits) two device int64[SHINE_SURF_PARTS]: [parity] — this step's count, consumed by its fused
- *                kernel — is cleared, [1 - parity] receives the next draw's
+ *                kernel — is cleared by the reduction launch, [1 - parity] receives the next draw's
  *   zero_ptr     the NEXT step's gradient bucket (two buckets alternate: this step's own holds its results), cleared here; or NULL
- * idx_out [n]: the next step's sorted sample indices (the fused kernel of this step has read its own by now).
+ * idx_out [n]: the next step's sorted sample indices when the call returns (the fused kernel of this step reads its own from it).
+ * idx_next [n] (scratch, not idx_out) or NULL — WHERE the rider runs:
+ *   idx_next given: as TRAILING WORKGROUPS OF THE FUSED LAUNCH.  None of the rider's work depends on the fused kernel of the same
+ *                step, and that launch ends ragged (it waits for its slowest workgroup while most CUs are idle): the trailing
+ *                workgroups are placed where step workgroups have retired.  They write the draw to idx_next — never to idx_out,
+ *                which the running kernel reads — clear zero_ptr, store state[1 - parity], fill block_sum[parity] and add to
+ *                surf_parts[1 - parity]; the reduction launch copies idx_next to idx_out and clears surf_parts[parity].
+ *   NULL:        as extra blocks of the reduction launch, behind the fused kernel (records built before the field existed).
  * The draws are bit-identical to shine_sample_sorted with the same seed / stream ids.  shine_draw_rider_prime sets the chain up:
  * draw 0 (stream id first_stream_id) into idx_out / surf_parts[0], pass 1 of draw 1 into block_sum[1], state[0], surf_parts[1] = 0;
  * the first step then has parity 0. */
@@ -87,6 +94,7 @@ typedef struct shine_draw_rider {
   int64_t* surf_parts[2];
   float* zero_ptr;
   int64_t zero_bytes;
+  int32_t* idx_next;
 } shine_draw_rider;
 int shine_draw_rider_prime(const shine_draw_rider* r, uint64_t first_stream_id, void* stream);
 
@@ -151,7 +159,7 @@ typedef struct shine_step_config {
                               them in the optimiser's launch.  loss_parts is then written by that call, and adam_state /
                               zero_f64 are served by the fused kernel itself. */
   const shine_reg_rider* reg_rider; /* host pointer or NULL: shine_forward also evaluates the regulariser (see shine_reg_rider) */
-  const shine_draw_rider* draw_rider; /* host pointer or NULL: shine_train_step's reduction launch draws the next batch and clears
+  const shine_draw_rider* draw_rider; /* host pointer or NULL: shine_train_step's two launches also draw the next batch and clear
                               the next step's gradient bucket (see shine_draw_rider).  Not with next_draw / defer_reduce. */
 } shine_step_config;
 

@@ -35,7 +35,7 @@ class DrawRider(C.Structure):
 
     _fields_ = [("pool_size", C.c_int64), ("n", C.c_int64), ("seed", C.c_uint64), ("state", C.c_void_p), ("parity", C.c_int32),
                 ("block_sum", C.c_void_p * 2), ("idx_out", C.c_void_p), ("surf_bits", C.c_void_p), ("surf_parts", C.c_void_p * 2),
-                ("zero_ptr", C.c_void_p), ("zero_bytes", C.c_int64)]
+                ("zero_ptr", C.c_void_p), ("zero_bytes", C.c_int64), ("idx_next", C.c_void_p)]
 
 
 class StepConfig(C.Structure):

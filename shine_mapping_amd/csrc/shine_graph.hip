@@ -53,6 +53,7 @@ static void graph_drop(shine_iter_graph* g) {
 static hipKernelNodeParams step_params(shine_iter_graph* g, void** kp) {
   hipKernelNodeParams p = {};
   kp[0] = &g->step.a;
+  kp[1] = &g->step.dr;  // (no trailing workgroups: the iteration graph's draw rides on the optimiser's launch)
   p.func = const_cast<void*>(g->step.fn);
   p.gridDim = g->step.grid;
   p.blockDim = g->step.block;
@@ -79,7 +80,7 @@ static hipKernelNodeParams fin_params(shine_iter_graph* g, void** kp) {
 static int graph_build(shine_iter_graph* g) {
   graph_drop(g);
   SHINE_HIP_CHECK(hipGraphCreate(&g->graph, 0));
-  void* skp[1];
+  void* skp[2];
   void* fkp[3];
   hipKernelNodeParams sp = step_params(g, skp), fp = fin_params(g, fkp);
   hipGraphNode_t prev = nullptr;
@@ -192,7 +193,7 @@ extern "C" int shine_iter_graph_commit(shine_iter_graph* g) {
     g->replayed = false;
   }
   if (g->exec && g->built_step_fn == g->step.fn && g->built_fin_fn == g->fin.fn) {
-    void* skp[1];
+    void* skp[2];
     void* fkp[3];
     hipKernelNodeParams sp = step_params(g, skp), fp = fin_params(g, fkp);
     bool ok = true;

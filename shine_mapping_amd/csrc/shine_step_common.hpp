@@ -136,21 +136,6 @@ long long v3_lds_bytes(int wg_waves);
 // measurement aid (shine_debug_set_profile_buffer): per-wave phase cycle counters or null
 extern long long* g_prof_buffer;
 
-// a fused-step launch, prepared but not launched (shine_step_v3.hip prepare_step_v3): shine_train_step_v3 launches it, the
-// iteration graph (shine_graph.hip) makes it a kernel node
-struct StepLaunch {
-  const void* fn;   // the k_step_v3 instantiation; null: empty batch, nothing to launch
-  dim3 grid, block;
-  int blocks;       // workgroups = partial vectors the launch leaves in the workspace
-  bool mark_pass;   // the touched-row flags need k_mark_touched in front (a level without a gradient table, profiling build)
-  V1Args a;
-};
-int prepare_step_v3(StepLaunch* out, const shine_tables* t, const shine_step_config* cfg, const float* coord,
-                    const float* sdf_label, const float* weight, const int32_t* perm, const int32_t* slots,
-                    const int64_t* n_surf, int64_t n, const float* const* feats, const int64_t* rows, const float* const* mlp,
-                    float* pred_out, float* grad_x_out, float* const* grad_feats, float* const* grad_mlp, double* loss_parts,
-                    unsigned char* const* touched, void* workspace, size_t workspace_bytes);
-
 // second stage of a fused step (shine_step_support.hip): add `nblocks` per-workgroup partial vectors [PART_STRIDE floats each]
 // into the gradient tensors / loss, re-zero the trash rows (set_zero, model/feature_octree.py:78-81)
 // cfg->next_draw: pass 1 of the NEXT sorted draw (two-launch form of the sampler: the block sums of its Exp(1) spacings) rides
@@ -178,10 +163,34 @@ struct DrawRiderArgs {
   long long* parts_next;   // receives the next draw's surface counts
   float4* zero_ptr;
   long long zero_n16;
+  // the rider as trailing workgroups of the FUSED launch (the record carries idx_next, shine_draw_rider.hpp): the draw goes to
+  // idx_next — the running step reads idx — and the reduction launch only copies it to idx and clears parts_this
+  int* idx_next;
+  int on_tail;    // 1: the fused launch ran the rider
+  int copy_vec;   // ... and idx / idx_next are 16-byte aligned: the copy moves 16 B per lane
 };
+
+// a fused-step launch, prepared but not launched (shine_step_v3.hip prepare_step_v3): shine_train_step_v3 launches it, the
+// iteration graph (shine_graph.hip) makes it a kernel node
+struct StepLaunch {
+  const void* fn;   // the k_step_v3 instantiation; null: empty batch, nothing to launch
+  dim3 grid, block;
+  int blocks;       // workgroups = partial vectors the launch leaves in the workspace
+  bool mark_pass;   // the touched-row flags need k_mark_touched in front (a level without a gradient table, profiling build)
+  bool tail_ok;     // fn runs the draw rider in trailing workgroups when it is given one (not the profiling builds)
+  V1Args a;
+  DrawRiderArgs dr; // the kernel's second argument; nblocks == 0 (what prepare_step_v3 leaves): no trailing workgroups
+};
+int prepare_step_v3(StepLaunch* out, const shine_tables* t, const shine_step_config* cfg, const float* coord,
+                    const float* sdf_label, const float* weight, const int32_t* perm, const int32_t* slots,
+                    const int64_t* n_surf, int64_t n, const float* const* feats, const int64_t* rows, const float* const* mlp,
+                    float* pred_out, float* grad_x_out, float* const* grad_feats, float* const* grad_mlp, double* loss_parts,
+                    unsigned char* const* touched, void* workspace, size_t workspace_bytes);
+
 __global__ void k_reduce_partials(V1Args a, int nblocks, Pass1Args p1, DrawRiderArgs dr);
 int fill_pass1_args(Pass1Args* p1, const shine_step_config* cfg);  // shine_step_support.hip
 int fill_draw_rider_args(DrawRiderArgs* dr, const shine_step_config* cfg);
+constexpr int IDX_COPY_BLOCK = 4096;  // ints one 1024-thread block of the reduction launch copies from idx_next to idx
 __global__ void k_mark_touched(V1Args a);
 int launch_operand_image(const V1Args& a, float* image, hipStream_t st);  // shine_step_support.hip (image: V3_IMAGE_FLOATS floats)
 

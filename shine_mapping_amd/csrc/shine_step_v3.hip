@@ -30,15 +30,31 @@
 // tile range holds 4-6 x the mean number of node runs (tools/run_stats.py).
 // Planned or pool batches only (the hash slots come with the batch): the Python layer plans every batch that arrives without
 // an order (shine_plan_batch), the C entry point refuses one.
+#include "shine_draw_rider.hpp"
 #include "shine_step_body.hpp"
 
 namespace shine {
 
-// one launch = one step: every workgroup runs its share of the batch (shine_step_body.hpp)
+// one launch = one step: every workgroup runs its share of the batch (shine_step_body.hpp).
+// The builds shine_train_step launches (not the profiling builds, not EXT) may be launched with MORE workgroups than the step
+// has (a.waves_total / WAVES): the trailing ones run cfg->draw_rider — the next draw and the next step's zero-fill, work that
+// depends on nothing this launch computes (shine_draw_rider.hpp) — and return.  They occupy a step workgroup's registers and LDS,
+// so they start where a step workgroup has retired: in CU time the launch's ragged end leaves idle.  A run-time branch at the
+// kernel's entry; the step's workgroups count themselves by the step's own geometry, never by gridDim.
 template <int L, int WAVES, bool EIK, bool PROF, bool EXT = false, bool MARK = false, bool FAR = false>
-__global__ __launch_bounds__(WAVES * 64, WAVES == V3_BIG ? V3_BIG / 4 : 2) void k_step_v3(V1Args a) {
+__global__ __launch_bounds__(WAVES * 64, WAVES == V3_BIG ? V3_BIG / 4 : 2) void k_step_v3(V1Args a, DrawRiderArgs dr) {
   __shared__ StepShared<WAVES, FAR> sm;
-  step_body<L, WAVES, EIK, PROF, EXT, MARK, false, FAR>(a, sm, (int)blockIdx.x, (int)gridDim.x);
+  if constexpr (!PROF && !EXT) {
+    static_assert(WAVES % 4 == 0, "a trailing workgroup is WAVES / 4 sampler blocks of 256 threads");
+    const int step_blocks = (int)(a.waves_total / WAVES);
+    if ((int)blockIdx.x >= step_blocks) {
+      draw_rider_block<WAVES / 4>(dr, (int)blockIdx.x - step_blocks, dr.idx_next, false);
+      return;
+    }
+    step_body<L, WAVES, EIK, PROF, EXT, MARK, false, FAR>(a, sm, (int)blockIdx.x, step_blocks);
+  } else {
+    step_body<L, WAVES, EIK, PROF, EXT, MARK, false, FAR>(a, sm, (int)blockIdx.x, (int)gridDim.x);
+  }
 }
 
 // x[l] + y[l ^ 32] style exchanges through v_permlane32_swap / v_permlane16_swap: pins the lane maps xsum32 / xsum16 assume
@@ -129,6 +145,8 @@ int prepare_step_v3(StepLaunch* out, const shine_tables* t, const shine_step_con
                                       "record per sample); the array form (2) is the importance sweep's");
   V1Args& a = out->a;
   a = V1Args{};
+  out->dr = DrawRiderArgs{};
+  out->tail_ok = false;
   int rc = fill_step_args(&a, t, cfg, coord, sdf_label, weight, perm, slots, n_surf, n, feats, rows, mlp, pred_out,
                           grad_x_out, grad_feats, grad_mlp, loss_parts, touched);
   if (rc != SHINE_OK) return rc;
@@ -160,6 +178,7 @@ int prepare_step_v3(StepLaunch* out, const shine_tables* t, const shine_step_con
   else
     out->fn = cfg->eikonal_on ? step_fn<true, false, false>(cfg->n_levels, g.wg_waves, prof, far)
                               : step_fn<false, false, false>(cfg->n_levels, g.wg_waves, prof, far);
+  out->tail_ok = !SHINE_V3_PROFBUILD || !prof;
   out->grid = dim3((unsigned)g.blocks);
   out->block = dim3((unsigned)(g.wg_waves * 64));
   out->blocks = (int)g.blocks;
@@ -204,18 +223,27 @@ extern "C" int shine_train_step_v3(const shine_tables* t, const shine_step_confi
     hipLaunchKernelGGL(k_mark_touched, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
     SHINE_HIP_CHECK(hipGetLastError());
   }
-  void* params[] = {&a};
+  const bool reduce = !(a.ablate & 32) && !a.defer_reduce;  // (ablate bit 32: measurement only — the dominant kernel by itself)
+  // cfg->draw_rider: the whole next draw + the next step's zero-fill.  With idx_next they are trailing workgroups of the fused
+  // launch (2 / 1 sampler blocks each) and the reduction launch copies idx_next -> idx_out; without, extra blocks of the reduction
+  // launch (4 sampler blocks each)
+  DrawRiderArgs dr = {};
+  if (reduce) rc = fill_draw_rider_args(&dr, cfg);
+  if (rc != SHINE_OK) return rc;
+  if (dr.nblocks > 0 && dr.idx_next && sl.tail_ok) {
+    dr.on_tail = 1;
+    sl.dr = dr;
+    sl.grid.x += (unsigned)draw_rider_workgroups(dr.nblocks, (int)sl.block.x / 256);
+  }
+  void* params[] = {&a, &sl.dr};
   SHINE_HIP_CHECK(hipLaunchKernel(sl.fn, sl.grid, sl.block, params, 0, st));
-  if (!(a.ablate & 32) && !a.defer_reduce) {  // (ablate bit 32: measurement only — time the dominant kernel by itself)
+  if (reduce) {
     Pass1Args p1;  // cfg->next_draw: pass 1 of the next sorted draw as extra blocks of this launch (4 sampler blocks each)
     rc = fill_pass1_args(&p1, cfg);
     if (rc != SHINE_OK) return rc;
-    DrawRiderArgs dr;  // cfg->draw_rider: the whole next draw + the next step's zero-fill (2 x 4 sampler blocks per extra block)
-    rc = fill_draw_rider_args(&dr, cfg);
-    if (rc != SHINE_OK) return rc;
-    hipLaunchKernelGGL(k_reduce_partials,
-                       dim3((unsigned)((PART_FLOATS + 63) / 64 + (p1.nblocks + 3) / 4 + 2 * ((dr.nblocks + 3) / 4))), dim3(1024), 0,
-                       st, a, sl.blocks, p1, dr);
+    const int rider_blocks = dr.on_tail ? (int)((dr.n + IDX_COPY_BLOCK - 1) / IDX_COPY_BLOCK) : draw_rider_workgroups(dr.nblocks, 4);
+    hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((PART_FLOATS + 63) / 64 + (p1.nblocks + 3) / 4 + rider_blocks)),
+                       dim3(1024), 0, st, a, sl.blocks, p1, dr);
     SHINE_HIP_CHECK(hipGetLastError());
   }
   return SHINE_OK;
@@ -262,7 +290,8 @@ extern "C" int shine_interp_sdf_backward(const shine_tables* t, const shine_step
     return set_error(SHINE_E_INVALID, "shine_interp_sdf_backward: workspace too small (shine_train_step_workspace_bytes)");
   a.partials = (float*)workspace;
   hipStream_t st = (hipStream_t)stream;
-  void* params[] = {&a};
+  DrawRiderArgs no_rider = {};
+  void* params[] = {&a, &no_rider};
   const void* fn = grad_g ? step_fn<true, true, false>(cfg->n_levels, g.wg_waves, false)
                           : step_fn<false, true, false>(cfg->n_levels, g.wg_waves, false);
   SHINE_HIP_CHECK(hipLaunchKernel(fn, dim3((unsigned)g.blocks), dim3((unsigned)(g.wg_waves * 64)), params, 0, st));

@@ -40,7 +40,7 @@ class StepOptions:
     next_draw: Optional[object] = None          # SortedPool.next_draw(...): the first pass of the NEXT large sorted draw rides on
                                                 # the step's reduction launch; complete it with pool.draw(..., pass1_done=True)
     draw_rider: Optional[object] = None         # sampler.DrawChain.rider[parity]: the WHOLE next sorted draw and the next step's
-                                                # zero-fill ride on this step's reduction launch (cfg.draw_rider)
+                                                # zero-fill ride in this step's two launches (cfg.draw_rider)
     kernel_variant: int = 0           # 0 the fused step (5 / 6: its far / near build whatever the table size); tests / tools: 1 the
                                       # lane-per-point reference kernel
                                       # (libshine_check.so)

@@ -51,8 +51,9 @@ def importance_chunks(perm, n, bs, down_rate=1):
 
 
 class DrawChain:
-    """The whole next large sorted draw — and the next step's opt.zero_grad() — riding on every step's reduction launch
-    (include/shine_hip.h shine_draw_rider): a batch-mode step is then TWO launches, the fused kernel and its reduction.
+    """The whole next large sorted draw — and the next step's opt.zero_grad() — riding in the trailing workgroups of every step's
+    fused launch (include/shine_hip.h shine_draw_rider): a batch-mode step is TWO launches, the fused kernel and its reduction,
+    and the draw runs in CU time the fused launch's ragged end leaves idle.
 
         chain = pool.draw_chain(n, idx, buckets=(flat_a, flat_b), surf=eikonal)   # idx: int32 [n], the batch every step reads
         chain.prime()                                                             # draw 0 + pass 1 of draw 1; parity 0 next
@@ -62,8 +63,8 @@ class DrawChain:
                              grad_buffers=<views of buckets[p]>)
             chain.parity ^= 1
 
-    Step k accumulates into buckets[k & 1]; its launch clears buckets[(k + 1) & 1], draws batch k + 1 into idx and runs pass 1 of
-    batch k + 2.  Capture-safe: the stream ids live in device memory; a captured graph bakes the parity of each of its steps in, so
+    Step k accumulates into buckets[k & 1]; its launches clear buckets[(k + 1) & 1], draw batch k + 1 (into idx_next beside the fused
+    kernel, copied to idx behind it) and run pass 1 of batch k + 2.  Capture-safe: the stream ids live in device memory; a captured graph bakes the parity of each of its steps in, so
     replay graphs only where the host's `parity` says the device is (an even number of steps per graph keeps it at 0)."""
 
     def __init__(self, pool, n, idx, buckets=None, surf=False):
@@ -77,6 +78,7 @@ class DrawChain:
         self.block_sum = (torch.zeros(nb, dtype=torch.float64, device=dev), torch.zeros(nb, dtype=torch.float64, device=dev))
         self.surf_parts = (pool.surf_parts_buffer(), pool.surf_parts_buffer()) if surf else (None, None)
         self.buckets = buckets
+        self.idx_next = torch.empty_like(idx)  # the rider runs beside the fused kernel, which reads idx: it draws into this shadow
         self.parity = 0
         self.rider = []
         for p in (0, 1):
@@ -85,6 +87,7 @@ class DrawChain:
             r.state, r.parity = self.state.data_ptr(), p
             r.block_sum[0], r.block_sum[1] = self.block_sum[0].data_ptr(), self.block_sum[1].data_ptr()
             r.idx_out = idx.data_ptr()
+            r.idx_next = self.idx_next.data_ptr()
             if surf:
                 r.surf_bits = pool.surf_bits().data_ptr()
                 r.surf_parts[0], r.surf_parts[1] = self.surf_parts[0].data_ptr(), self.surf_parts[1].data_ptr()
@@ -261,7 +264,7 @@ class SortedPool:
         return idx
 
     def draw_chain(self, n, idx, buckets=None, surf=False):
-        """DrawChain(self, ...): every step's reduction launch draws the next batch (and clears the next step's bucket)"""
+        """DrawChain(self, ...): every step's own two launches draw the next batch (and clear the next step's bucket)"""
         return DrawChain(self, n, idx, buckets=buckets, surf=surf)
 
     def next_draw(self, n, out=None, surf_parts=None, n_global=None):
