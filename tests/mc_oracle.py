@@ -1,7 +1,7 @@
 """Numpy marching cubes with the rules of DESIGN.md "Meshing", on the table parsed from csrc/shine_mc_tables.hpp: the oracle the
 device kernel (csrc/shine_mc.hip) is compared with, bit for bit on faces and to 1e-6 index units on vertices.  Also the small
-host oracles of the mesh post-processing (area-weighted normals, edge-connected clusters, remove_vertices_by_mask) and a PLY
-reader."""
+host oracles of the mesh post-processing (area-weighted normals in fp64 and in 80-bit long double, edge-connected clusters by
+union-find and by sort + connected components, remove_vertices_by_mask) and a PLY reader."""
 import os
 import re
 
@@ -213,6 +213,72 @@ def triangle_clusters(faces):
     roots = np.array([find(t) for t in range(F)], np.int64)
     uniq, cid = np.unique(roots, return_inverse=True)  # (roots are the smallest triangle of each cluster: sorted = open3d order)
     return cid.astype(np.int64), np.bincount(cid, minlength=len(uniq))
+
+
+def have_scipy():
+    try:
+        import scipy.sparse.csgraph  # noqa: F401
+
+        return True
+    except Exception:
+        return False
+
+
+def triangle_clusters_graph(faces):
+    """The same rule as triangle_clusters without a union-find: the 3F undirected edge keys stable-sorted with their triangle
+    ids, neighbours with equal keys linked in a sparse F x F graph, scipy's connected_components, and the components renumbered
+    by their smallest triangle (open3d: clusters appear in the order of their first triangle).  Returns (cluster id per
+    triangle, triangles per cluster)."""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    F = len(f)
+    if F == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    a, b = f.reshape(-1), f[:, [1, 2, 0]].reshape(-1)  # edge j of triangle t: (f[t, j], f[t, j + 1])
+    lo, hi = np.minimum(a, b), np.maximum(a, b)
+    tri = np.repeat(np.arange(F, dtype=np.int64), 3)
+    order = np.lexsort((hi, lo))  # (stable: by lo, then hi, then position)
+    lo, hi, tri = lo[order], hi[order], tri[order]
+    same = (lo[1:] == lo[:-1]) & (hi[1:] == hi[:-1])
+    g = coo_matrix((np.ones(int(same.sum()), np.int8), (tri[:-1][same], tri[1:][same])), shape=(F, F))
+    ncomp, lab = connected_components(g, directed=False)
+    first = np.full(ncomp, F, np.int64)
+    np.minimum.at(first, lab, np.arange(F, dtype=np.int64))
+    rank = np.empty(ncomp, np.int64)
+    rank[np.argsort(first, kind="stable")] = np.arange(ncomp, dtype=np.int64)
+    cid = rank[lab]
+    return cid, np.bincount(cid, minlength=ncomp)
+
+
+def vertex_normals_ext(verts, faces):
+    """vertex_normals' rule in np.longdouble (80-bit on x86: eps 1.08e-19), written out with products and differences: per
+    vertex the sum of its faces' (v1 - v0) x (v2 - v0) in face order, normalised, a zero sum stays zero.  Returns (normals
+    [V,3] longdouble, valence k_v [V] (a face counts once per corner it puts on the vertex), cond_v [V] float64 = sum over the
+    vertex's faces of |e1| |e2| / |sum of the face normals|, inf where that sum is zero): the edge lengths, not |fn|, in the
+    numerator, so that skinny triangles count with the rounding they cause."""
+    L = np.longdouble
+    v = np.asarray(verts, np.float64).reshape(-1, 3).astype(L)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    V = len(v)
+    p0, p1, p2 = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    e1x, e1y, e1z = p1[:, 0] - p0[:, 0], p1[:, 1] - p0[:, 1], p1[:, 2] - p0[:, 2]
+    e2x, e2y, e2z = p2[:, 0] - p0[:, 0], p2[:, 1] - p0[:, 1], p2[:, 2] - p0[:, 2]
+    fn = np.stack([e1y * e2z - e1z * e2y, e1z * e2x - e1x * e2z, e1x * e2y - e1y * e2x], 1)
+    w = np.sqrt(e1x * e1x + e1y * e1y + e1z * e1z) * np.sqrt(e2x * e2x + e2y * e2y + e2z * e2z)
+    corner = f.reshape(-1)  # face-major: ufunc.at adds in this order, so every vertex sums in face order
+    n = np.zeros((V, 3), L)
+    num = np.zeros(V, L)
+    np.add.at(n, corner, np.repeat(fn, 3, axis=0))
+    np.add.at(num, corner, np.repeat(w, 3))
+    kv = np.bincount(corner, minlength=V).astype(np.int64)
+    ln = np.sqrt(n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1] + n[:, 2] * n[:, 2])
+    nz = ln > 0
+    cond = np.full(V, np.inf)
+    cond[nz] = (num[nz] / ln[nz]).astype(np.float64)
+    n[nz] = n[nz] / ln[nz][:, None]
+    return n, kv, cond
 
 
 def remove_vertices_by_mask(verts, faces, drop, *vertex_attrs):

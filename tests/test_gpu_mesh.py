@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import mc_oracle as mo
+import mesh_post_cases as mp
 from conftest import load_golden, product_from_golden
 
 pytestmark = pytest.mark.gpu
@@ -96,12 +97,13 @@ def test_empty_surface_and_out_of_range_level():
 def _analytic(kind, n=256):
     ax = torch.arange(n, dtype=torch.float64, device="cuda")
     x, y, z = torch.meshgrid(ax, ax, ax, indexing="ij")
-    c = (127.3, 128.6, 126.9)
+    s = n / 256.0  # (the surfaces are laid out for 256^3 and shrink with a smaller grid: the same numbers at n = 256)
+    c = (127.3 * s, 128.6 * s, 126.9 * s)
     if kind == "sphere":
-        r = 100.0
+        r = 100.0 * s
         d = torch.sqrt((x - c[0]) ** 2 + (y - c[1]) ** 2 + (z - c[2]) ** 2)
         return (r - d).float(), r
-    R, r = 80.0, 30.0
+    R, r = 80.0 * s, 30.0 * s
     q = torch.sqrt((x - c[0]) ** 2 + (y - c[1]) ** 2) - R
     return (r - torch.sqrt(q ** 2 + (z - c[2]) ** 2)).float(), (R, r)
 
@@ -164,11 +166,15 @@ def test_vertex_normals_match_the_area_weighted_oracle():
 
     sdf, _ = _analytic("torus", 96)
     v, f = marching_cubes(sdf)
+    assert len(f) > 10000  # (the whole torus lies inside the grid)
     vw = v.double() * 0.1 + torch.tensor([3.0, -2.0, 1.0], dtype=torch.float64, device="cuda")
     vw = torch.cat([vw, torch.zeros(1, 3, dtype=torch.float64, device="cuda")])  # one vertex without faces: normal 0
     n = vertex_normals_device(vw, f)
-    ref = mo.vertex_normals(vw.cpu().numpy(), f.cpu().numpy())
-    assert np.abs(n.cpu().numpy() - ref).max() <= 1e-5
+    # |n - n_ref| <= 8 (k_v + 8) 2^-53 cond_v against the 80-bit oracle (mesh_post_cases.check_normals); the vertex without faces
+    # is the only one the bound does not cover, and it must be exactly zero
+    ref, kv, cond = mo.vertex_normals_ext(vw.cpu().numpy(), f.cpu().numpy())
+    ratio = mp.check_normals(n.cpu().numpy(), ref, kv, cond, cancel=(len(vw) - 1,))
+    print("torus: max |n - n_ref| / bound = %.3g" % ratio)
     assert (n[-1] == 0).all()
     assert torch.equal(n, vertex_normals_device(vw, f))
 

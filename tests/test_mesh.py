@@ -1,6 +1,7 @@
 """CPU: the marching-cubes table (csrc/shine_mc_tables.hpp) is complete, crack-free and consistently oriented; the numpy
 oracle (tests/mc_oracle.py) makes closed meshes of the right topology; the PLY writer round-trips; the mesher's host logic
-(octree grid layout, memory refusal, empty results)."""
+(octree grid layout, memory refusal, empty results); the post-processing oracles agree with each other and with the bound the
+kernels are held to, on the hand-built meshes of tests/mesh_post_cases.py; shine_mesh.hip's size checks."""
 import itertools
 import os
 import subprocess
@@ -12,6 +13,7 @@ import pytest
 import torch
 
 import mc_oracle as mo
+import mesh_post_cases as mp
 from conftest import ROOT
 
 
@@ -213,3 +215,119 @@ def test_triangle_mesh_transform_matches_open3d_convention():
     m = TriangleMesh([[1.0, 0, 0], [0, 1, 0], [0, 0, 1]], [[0, 1, 2]], vertex_normals=[[1.0, 0, 0]] * 3)
     m.transform(T)
     assert np.allclose(m.vertices, [[1, 3, 3], [0, 2, 3], [1, 2, 4]]) and np.allclose(m.vertex_normals, [[0, 1, 0]] * 3)
+
+
+# ------------------------------------------------------------------------------------- the post-processing oracles (mc_oracle.py)
+@pytest.mark.parametrize("name", mp.CLUSTER_NAMES)
+def test_cluster_oracles_agree(name):
+    """the union-find and the sort + connected_components oracle, on every cluster input of tests/test_gpu_mesh_post.py"""
+    if not mo.have_scipy():
+        pytest.skip("scipy does not import: nothing to compare the union-find with")
+    f = mp.cluster_cases()[name]
+    cid, cnt = mo.triangle_clusters(f)
+    gid, gcnt = mo.triangle_clusters_graph(f)
+    assert np.array_equal(cid, gid) and np.array_equal(cnt, gcnt)
+    assert cnt.sum() == len(f) and (cnt > 0).all()
+    first = np.full(len(cnt), len(f))
+    np.minimum.at(first, gid, np.arange(len(f)))
+    assert (np.diff(first) > 0).all(), "clusters are numbered in the order of their first triangle"
+
+
+def test_cluster_oracle_on_the_meshes_with_known_answers():
+    def graph(f):
+        return mo.triangle_clusters_graph(f) if mo.have_scipy() else mo.triangle_clusters(f)
+
+    c = mp.cluster_cases()
+    for name in ("strip-identity", "strip-reversed", "strip-random", "strip-zigzag"):
+        assert graph(c[name])[1].tolist() == [mp.STRIP_LEN]
+    f, owner = mp.many_strips()
+    cid, cnt = graph(f)
+    assert np.array_equal(cid, owner) and cnt.tolist() == list(mp.MANY_STRIPS)
+    assert 300 in cnt and 299 in cnt
+    assert graph(c["singletons"])[1].tolist() == [1] * mp.SINGLETONS
+    assert graph(c["bow-tie"])[0].tolist() == [0, 1]
+    assert graph(c["edge-opposite"])[0].tolist() == [0, 0] and graph(c["edge-same"])[0].tolist() == [0, 0]
+    for k in mp.BOOKS:
+        cid, cnt = graph(c["book-%d" % k])
+        assert sorted(cnt.tolist()) == [1, k] and cid[k // 2] == 1 and cnt[1] == 1
+    assert graph(c["duplicates"])[0].tolist() == [0, 1, 0, 0]
+    assert graph(c["degenerate"])[0].tolist() == [0, 1, 2, 1, 3]
+    assert graph(c["degenerate-attached"])[0].tolist() == [0, 1, 1]
+    assert graph(c["lone-point"])[0].tolist() == [0]
+    cnt = graph(c["sheet-10"])[1]
+    assert cnt.max() > 0.9 * len(c["sheet-10"]) and len(cnt) > 10  # one sheet and the crumbs around its holes
+    cnt = graph(c["sheet-60"])[1]
+    assert len(cnt) > 5000 and len(np.unique(cnt)) >= 20  # at 60 % it falls into many clusters of mixed size
+    for F in mp.LAUNCH_F:
+        want = [1] if F == 1 else ([F - 2, 2] if F >= 4 else [F - 1, 1])
+        assert graph(c["launch-%d-small-last" % F])[1].tolist() == want
+        if F > 1:
+            assert graph(c["launch-%d-big-last" % F])[1].tolist() == want[::-1]
+    small = graph(c["ids-2^16"])
+    assert small[0].tolist() == [0, 1, 2, 2, 3, 3] + [4] * 10
+    for name in ("ids-2^24", "ids-2^31"):
+        assert np.array_equal(graph(c[name])[0], small[0])
+    assert c["ids-2^31"].max() == 2 ** 31 - 1
+    assert graph(c["ids-top-bit"])[0].tolist() == [0, 1, 0, 2, 3, 4, 5, 6, 6]
+
+
+@pytest.mark.parametrize("name", mp.NORMALS_NAMES)
+def test_plain_fp64_normals_stay_inside_the_bound(name, capsys):
+    """an honest fp64 evaluation (numpy's, no contraction, another summation order) passes the bound the kernel is held to
+    (mesh_post_cases.check_normals), on every normals input of tests/test_gpu_mesh_post.py"""
+    v, f, cancel = mp.normals_cases()[name]
+    ref, kv, cond = mp.normals_reference(name)
+    ratio = mp.check_normals(mo.vertex_normals(v, f), ref, kv, cond, cancel)
+    fin = cond[np.isfinite(cond)]
+    with capsys.disabled():
+        print("\n  %s: numpy fp64 max |n - n_ref| / bound = %.3g, max cond_v = %.3g" % (name, ratio, fin.max() if len(fin) else 0.0))
+    assert ratio <= 1.0
+
+
+def test_extended_normals_oracle_on_known_meshes():
+    v, f, cancel = mp.normals_cases()["cancelling"]
+    n, kv, cond = mo.vertex_normals_ext(v, f)
+    assert n.dtype == np.longdouble and kv.tolist() == [2, 2, 2, 2, 1, 2, 1]
+    assert np.flatnonzero(np.isinf(cond)).tolist() == list(cancel) and (n[list(cancel)] == 0).all()
+    assert np.array_equal(n[4], [0, 0, 1]) and np.array_equal(n[6], [0, 0, -1]) and cond[4] == 1.0
+    v, f, cancel = mp.normals_cases()["star"]
+    n, kv, cond = mo.vertex_normals_ext(v, f)
+    assert kv[0] == 7 and kv[12] == 1 and kv[6] == 0 and kv[13] == 0 and np.flatnonzero(np.isinf(cond)).tolist() == [6, 13]
+    # a right triangle seen from its sharp corner: |e1| |e2| / |fn| = 1 / sin(angle at v0)
+    n, kv, cond = mo.vertex_normals_ext([[0, 0, 0], [1, 0, 0], [1, 1e-3, 0]], [[0, 1, 2]])
+    assert np.allclose(cond, np.sqrt(1 + 1e-6) / 1e-3) and np.array_equal(n, [[0, 0, 1]] * 3)
+    v, f, _ = mp.normals_cases()["fan"]
+    assert mo.vertex_normals_ext(v, f)[1][0] == mp.FAN
+
+
+def test_mesh_post_entry_points_reject_bad_sizes_without_a_gpu():
+    import ctypes as C
+
+    from shine_mapping_amd import _lib
+
+    lib = _lib.lib()
+    INVALID = -1
+    host = (C.c_char * 4096)()  # stands in for device memory: every call below returns before anything would touch it
+    p = C.cast(host, C.c_void_p)
+    need, kept = C.c_size_t(0), C.c_int64(-7)
+
+    def normals(nv, nf, ws=None, wb=need):
+        return lib.shine_mesh_vertex_normals(p, nv, p, nf, ws, C.byref(wb) if wb is not None else None, p, None)
+
+    def clusters(nf, ws=None, wb=need, out=kept):
+        return lib.shine_mesh_cluster_filter(p, nf, 300, ws, C.byref(wb) if wb is not None else None, None, p,
+                                             C.byref(out) if out is not None else None, None)
+
+    for ws in (None, p):  # the size query and the call itself
+        assert normals(1 << 31, 10, ws) == INVALID and normals(10, 1 << 31, ws) == INVALID
+        assert b"shine_mesh_vertex_normals" in lib.shine_error_string(INVALID) and b"2^31" in lib.shine_error_string(INVALID)
+        assert normals(-1, 10, ws) == INVALID and normals(10, -1, ws) == INVALID and normals(10, 10, ws, None) == INVALID
+        assert clusters(1 << 31, ws) == INVALID and clusters(1 << 40, ws) == INVALID
+        assert b"shine_mesh_cluster_filter" in lib.shine_error_string(INVALID) and b"2^31" in lib.shine_error_string(INVALID)
+        assert clusters(-1, ws) == INVALID and clusters(10, ws, None) == INVALID
+    assert kept.value == -7
+    # One below the limit is not refused for its size.  The size query itself asks rocPRIM for its scratch, which asks for the
+    # device's architecture: 0 and a size with a GPU, a HIP error (not INVALID) without one, so the sizes, the too-small workspace
+    # and the null kept_out, which the library checks after the query, are tested on the device (tests/test_gpu_mesh_post.py).
+    for rc in (normals((1 << 31) - 1, 256), clusters(256)):
+        assert rc != INVALID and (rc != 0 or need.value >= 256 * 8)
