@@ -1,10 +1,14 @@
 """GPU: the sdf_l1 / sdf_l2 and ray-rendering (dr, dr_neus) objectives on HIP (csrc/shine_loss_modes.hip) against the reference's
 recorded values (tests/golden/loss_modes.pt), against torch composites at scale, and in the drivers' Tier A loop together with
-the fused optimiser's learnable sigma_size group."""
+the fused optimiser's learnable sigma_size group; then the sweeps on the CPU-generated inputs of tests/test_loss_modes.py: every
+sample count 1..32 in both modes with tied depths and saturated rows, every launch shape of the two kernels, and the workspace
+and ticket counter they share."""
 import pytest
 import torch
 
-from test_loss_modes import FIXTURE, composite_diff, composite_ray, grad_close, load_fixture
+from test_loss_modes import (DIFF_SCALES, DIFF_SIZES, FIXTURE, LAUNCH_RAYS, LAUNCH_SAMPLES, SWEEP_RAYS, composite_diff,
+                             composite_ray, diff_inputs, fp64_rows, grad_close, load_fixture, ray_distance, ray_inputs,
+                             ray_reference, ray_sweep_case, saturated_rows)
 
 pytestmark = pytest.mark.gpu
 
@@ -342,3 +346,145 @@ def test_fixture_is_present():
     import os
 
     assert os.path.isfile(FIXTURE)
+
+
+# ---- sweeps: the inputs come from tests/test_loss_modes.py's CPU generators (their conditions are asserted there)
+
+BOUND_FACTOR = 4.0  # x e_ref (test_gpu_dataset.py): two correct fp32 evaluations in different operation orders each sit within
+# ~e_ref of exact; e_ref = the float32 composite's own distance to its float64 evaluation over the same rows
+
+
+def _ray(fn, x, y, d, neus):
+    """(loss, d loss / d y) of one call, on the host"""
+    yy = y.detach().clone().cuda().requires_grad_(True)
+    loss = fn(x.cuda(), yy, d.cuda(), neus)
+    loss.backward()
+    return loss.detach().cpu(), yy.grad.cpu()
+
+
+def _assert_ray_matches_a(what, loss, g, loss_a, ga):
+    """the fixture tests' bounds against the float32 composite: loss 1e-5 relative, grad_close(. R, . R, 1e-4), finite"""
+    R = g.shape[0]
+    ok, worst = grad_close(g * R, ga * R, 1e-4)
+    rel = abs(float(loss) - float(loss_a)) / abs(float(loss_a))
+    print("%s  vs float32 composite: loss rel %.2e  grad distance %.2e" % (what, rel, worst))
+    assert torch.isfinite(g).all(), what
+    assert rel <= 1e-5, (what, float(loss), float(loss_a))
+    assert ok, (what, worst)
+
+
+@pytest.mark.parametrize("neus", [False, True])
+@pytest.mark.parametrize("S", range(1, 33))
+def test_every_sample_count_matches_the_float32_and_float64_composites(S, neus):
+    x, y, d = ray_sweep_case(S, neus)
+    loss_a, ga = ray_reference(x, y, d, neus, torch.float32)  # A: what the fixture pins to the reference; every row
+    _, gb = ray_reference(x, y, d, neus, torch.float64)  # B: the rows an fp64 evaluation can judge
+    rows = fp64_rows(y, S >= 2)
+    e_ref = ray_distance(ga, gb, rows)
+    if S >= 2:  # another order of row 0's probabilities: its depths are all equal, so the column order alone decides
+        yp = y.clone()
+        yp[0] = y[0].flip(0)
+        loss_ap, gap = ray_reference(x, yp, d, neus, torch.float32)
+    # (row 5, all zeros, is what pins the backward loop's `k < A` guard with dr_neus at every S below the network's width: the
+    # last sample's quotient against the padding column behind it is 0 / 1, inside the clamp, and would put -gd x into its column)
+    for name, ray, _ in _paths():
+        what = "S=%d neus=%d R=%d %s" % (S, neus, SWEEP_RAYS, name)
+        loss, g = _ray(ray, x, y, d, neus)
+        assert g.shape == (SWEEP_RAYS, S)
+        dist = ray_distance(g, gb, rows)
+        print("%s  vs float64 composite over %d unsaturated rows: kernel %.3e  e_ref %.3e  bound %.3e"
+              % (what, int(rows.sum()), dist, e_ref, BOUND_FACTOR * e_ref))
+        _assert_ray_matches_a(what, loss, g, loss_a, ga)
+        assert dist <= BOUND_FACTOR * e_ref, (what, dist, e_ref)
+        if S == 1 and neus:  # no alpha at all
+            assert float(g.abs().max()) == 0.0, what
+        if S >= 2:
+            loss_p, gp = _ray(ray, x, yp, d, neus)
+            _assert_ray_matches_a(what + " row 0 flipped", loss_p, gp, loss_ap, gap)
+            assert torch.equal(gp[1:], g[1:]), what  # (nothing else moves)
+
+
+@pytest.mark.parametrize("S", LAUNCH_SAMPLES)
+@pytest.mark.parametrize("R", LAUNCH_RAYS)
+def test_ray_loss_at_every_launch_shape(R, S):
+    x, y, d = ray_inputs(R, S, 2000 + S)
+    assert not saturated_rows(y).any()
+    for neus in (False, True):
+        loss_a, ga = ray_reference(x, y, d, neus, torch.float32)
+        for name, ray, _ in _paths():
+            loss, g = _ray(ray, x, y, d, neus)
+            _assert_ray_matches_a("R=%d S=%d neus=%d %s" % (R, S, neus, name), loss, g, loss_a, ga)
+
+
+def _raw_diff_loss(p, l, w, scale, l2):
+    """shine_sdf_diff_loss through ctypes without the gradient output: the loss alone"""
+    from shine_mapping_amd import _lib, losses
+
+    out = torch.empty(1, dtype=torch.float32, device="cuda")
+    _lib.check(_lib.lib().shine_sdf_diff_loss(p.data_ptr(), l.data_ptr(), w.data_ptr(), p.shape[0], float(scale), 1 if l2 else 0,
+                                              out.data_ptr(), None, losses.loss_workspace(p.device).data_ptr(),
+                                              _lib.current_stream_handle()), "shine_sdf_diff_loss")
+    return out[0]
+
+
+@pytest.mark.parametrize("n", DIFF_SIZES)
+def test_diff_loss_at_every_launch_shape(n):
+    pred, label, weight = diff_inputs(n, 3000 + n)
+    pc, lc, wc = pred.cuda(), label.cuda(), weight.cuda()
+    for l2 in (False, True):
+        for scale in DIFF_SCALES:
+            pb = pred.double().requires_grad_(True)
+            lb = composite_diff(pb, label.double(), weight.double(), scale, l2)
+            lb.backward()
+            for name, _, diff in _paths():
+                what = "n=%d l2=%d scale=%g %s" % (n, l2, scale, name)
+                pa = pc.clone().requires_grad_(True)
+                la = diff(pa, lc, wc, scale, l2)
+                la.backward()
+                rel = abs(float(la) - float(lb)) / abs(float(lb))
+                err = rel_err(pa.grad, pb.grad)
+                print("%s  loss rel %.2e  grad rel_err %.2e" % (what, rel, err))
+                assert rel <= 1e-5, (what, float(la), float(lb))
+                assert err <= 1e-5, (what, err)
+                # a label equal to the prediction: sgn(0) = 0 (l1), 2 * 0 (l2); a zero weight: no gradient either
+                assert not bool(pa.grad[1::5].any()) and not bool(pa.grad[1::7].any()), what
+                assert bool((pa.grad[::35] != 0).all()), what  # (a difference and a weight: a gradient, at n = 1 too)
+                assert torch.equal(_raw_diff_loss(pc, lc, wc, scale, l2), la.detach()), what
+
+
+def test_ray_and_point_losses_share_one_workspace():
+    """the two kernels share loss_workspace(device) and its ticket counter: a sequence of launches of both, with one and with
+    1024 workgroups, gives on the shared workspace what each call gives on a freshly zeroed one"""
+    from shine_mapping_amd import losses
+
+    big_r, big_n = LAUNCH_RAYS[6], DIFF_SIZES[8]
+    rays = {R: tuple(t.cuda() for t in ray_inputs(R, S, 2000 + S)) for R, S in ((big_r, 17), (1, 8))}
+    pts = {n: tuple(t.cuda() for t in diff_inputs(n, 3000 + n)) for n in (1, big_n)}
+    sequence = [("ray", big_r, True), ("diff", 1, False), ("ray", 1, False), ("diff", big_n, True), ("ray", big_r, True)]
+
+    def call(kind, size, flag, ray, diff):
+        if kind == "ray":
+            x, y, d = rays[size]
+            yy = y.clone().requires_grad_(True)
+            loss = ray(x, yy, d, flag)
+            loss.backward()
+            return loss.detach().clone(), yy.grad.clone()
+        p, l, w = pts[size]
+        pp = p.clone().requires_grad_(True)
+        loss = diff(pp, l, w, DIFF_SCALES[0], flag)
+        loss.backward()
+        return loss.detach().clone(), pp.grad.clone()
+
+    def fresh_ray(x, y, d, neus):
+        return losses._RayRender.apply(x, y, d, neus, torch.zeros(losses.LOSS_WORKSPACE_BYTES // 8, dtype=torch.float64, device="cuda"))
+
+    def fresh_diff(p, l, w, scale, l2):
+        return losses._SdfDiff.apply(p, l, w, scale, l2, torch.zeros(losses.LOSS_WORKSPACE_BYTES // 8, dtype=torch.float64,
+                                                                   device="cuda"))
+
+    want = [call(kind, size, flag, fresh_ray, fresh_diff) for kind, size, flag in sequence]
+    for name, ray, diff in _paths():
+        got = [call(kind, size, flag, ray, diff) for kind, size, flag in sequence]
+        for step, (a, b) in enumerate(zip(got, want)):
+            assert torch.isfinite(a[0]) and torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), (name, step, sequence[step])
+    assert not bool(losses.loss_workspace(torch.device("cuda"))[1024:].view(torch.int64).any())  # (the counter is back at zero)

@@ -28,10 +28,13 @@ def composite_diff(pred, label, weight, scale, l2_loss):
     return (weight * per).sum() / pred.shape[0]
 
 
-def composite_ray(x, y, d_meas, neus_on):
+def rendered_depth(x, y, neus_on, stable=False):
     """per ray: samples in depth order; alphas = the probabilities (dr) or clamp((y[i+1] - y[i]) / (1 - y[i] + 1e-10), 0, 1)
-    (dr_neus); o = (1 - a) + 1e-10; w = cumprod(o) / o * a; the mean over rays of |sum w x - d_meas|"""
-    depth, order = x.sort(dim=1)
+    (dr_neus); o = (1 - a) + 1e-10; w = cumprod(o) / o * a; sum w x.  stable: the order the kernel documents and no torch
+    version or machine changes — equal depths keep their column order (torch.sort promises nothing about them without it) and
+    the samples are added front to back (torch.sum's order over a short row depends on the vector width: the last bit of the
+    depth, and with it sgn(d - d_meas) of a ray rendered exactly onto its measurement)"""
+    depth, order = x.sort(dim=1, stable=True) if stable else x.sort(dim=1)
     prob = y.gather(1, order)
     if neus_on:
         lo, hi = prob[:, :-1], prob[:, 1:]
@@ -40,8 +43,18 @@ def composite_ray(x, y, d_meas, neus_on):
         a = prob
     o = torch.ones_like(a) - a + 1e-10
     w = o.cumprod(dim=1) / o * a
-    d = (w * depth[:, :a.shape[1]]).sum(dim=1)
-    return (d - d_meas).abs().mean()
+    t = w * depth[:, :a.shape[1]]
+    if not stable:
+        return t.sum(dim=1)
+    d = t[:, :0].sum(dim=1)
+    for k in range(t.shape[1]):
+        d = d + t[:, k]
+    return d
+
+
+def composite_ray(x, y, d_meas, neus_on, stable=False):
+    """the mean over rays of |rendered_depth - d_meas|"""
+    return (rendered_depth(x, y, neus_on, stable) - d_meas).abs().mean()
 
 
 def grad_close(got, ref, tol):
@@ -50,6 +63,131 @@ def grad_close(got, ref, tol):
     scale = ref.abs().amax(dim=1, keepdim=True).clamp_min(1.0)
     worst = float(((got - ref).abs() / scale).max())
     return worst <= tol, worst
+
+
+# ---- the sweep over every sample count and launch shape: CPU generators, so the conditions on the inputs can be checked here and
+# are the same on every machine; tests/test_gpu_loss_modes.py runs the kernels on exactly these inputs
+
+SWEEP_RAYS = 300  # three 128-ray chunks, the last ragged
+ZERO_GRAD_ROW = 6  # d_meas is the row's own rendered depth
+
+
+def ray_inputs(R, S, seed):
+    """x = 20 rand + 0.5, y = sigmoid(1.5 randn), d_meas = 20 rand + 0.5"""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.rand(R, S, generator=g) * 20.0 + 0.5
+    y = torch.sigmoid(torch.randn(R, S, generator=g) * 1.5)
+    d = torch.rand(R, generator=g) * 20.0 + 0.5
+    return x, y, d
+
+
+def ray_sweep_case(S, neus):
+    """ray_inputs with the edge rows (S >= 2): 0 all depths equal, 1 one pair of equal depths, 2 a leading 0, 3 a trailing 1,
+    4 all ones, 5 all zeros (with dr_neus the last sample's quotient against the padding column behind it is 0 / 1, inside the
+    clamp: the row that pins the backward loop's `k < A` guard at every S below its network's width), 6 the measurement equal
+    to the rendered depth of the float32 composite (sgn(0) = 0)"""
+    x, y, d = ray_inputs(SWEEP_RAYS, S, 1000 + 2 * S + int(neus))
+    if S >= 2:
+        x[0, :] = x[0, 0]
+        x[1, 1] = x[1, 0]
+        y[2, 0] = 0.0
+        y[3, S - 1] = 1.0
+        y[4, :] = 1.0
+        y[5, :] = 0.0
+        d[ZERO_GRAD_ROW] = rendered_depth(x, y, neus, stable=True)[ZERO_GRAD_ROW]
+    return x, y, d
+
+
+def saturated_rows(y):
+    """rays with a probability of exactly 0 or 1: the gradient's autograd form is a difference of ~1e10-sized terms there, and
+    only the float32 composite's own roundings specify it"""
+    return ((y == 0) | (y == 1)).any(dim=1)
+
+
+def fp64_rows(y, with_edges):
+    """the rays an fp64 evaluation can judge: unsaturated ones, without the row whose measurement IS the float32 rendered
+    depth — its gradient is sgn(d - d_meas) at the jump: 0 in float32, +-1 times the weights as soon as d is rounded otherwise"""
+    rows = ~saturated_rows(y)
+    if with_edges:
+        rows[ZERO_GRAD_ROW] = False
+    return rows
+
+
+def ray_reference(x, y, d_meas, neus, dtype):
+    """(loss, d loss / d y) of the stable composite evaluated in `dtype` on the inputs' device"""
+    yy = y.detach().clone().to(dtype).requires_grad_(True)
+    loss = composite_ray(x.to(dtype), yy, d_meas.to(dtype), neus, stable=True)
+    (g,) = torch.autograd.grad(loss, yy)
+    return loss.detach(), g
+
+
+def ray_distance(got, ref, rows):
+    """grad_close's unit over `rows`: the per-ray error of the per-ray gradient (x R) over max(1, largest |ref| in the ray)"""
+    R = got.shape[0]
+    return grad_close(got[rows].cpu() * R, ref[rows].cpu() * R, 0.0)[1]
+
+
+@pytest.mark.parametrize("neus", [False, True])
+def test_ray_sweep_recipe_holds_its_conditions(neus):
+    for S in range(1, 33):
+        x, y, d = ray_sweep_case(S, neus)
+        loss_a, ga = ray_reference(x, y, d, neus, torch.float32)
+        loss_b, gb = ray_reference(x, y, d, neus, torch.float64)
+        assert ga.dtype == torch.float32 and gb.dtype == torch.float64 and ga.shape == gb.shape == (SWEEP_RAYS, S)
+        assert torch.isfinite(ga).all() and torch.isfinite(loss_a), (S, neus)
+        sat = saturated_rows(y)
+        rows = fp64_rows(y, S >= 2)
+        e_ref = ray_distance(ga, gb, rows)
+        print("S=%2d neus=%d  e_ref = %.3e over %d rows, |loss A - loss B| / loss B = %.3e"
+              % (S, neus, e_ref, int(rows.sum()), abs(float(loss_a) - float(loss_b)) / float(loss_b)))
+        assert e_ref < 1e-4, (S, neus, e_ref)
+        if S == 1:
+            assert not sat.any()
+            if neus:  # no alpha at all: every ray renders 0
+                assert torch.equal(loss_a, d.abs().mean()) and float(ga.abs().max()) == 0.0
+            continue
+        assert bool((x[0] == x[0, 0]).all()) and float(x[1, 1]) == float(x[1, 0])
+        assert sat[2:6].all() and not sat[:2].any() and not sat[ZERO_GRAD_ROW] and int(sat.sum()) == 4, (S, neus)
+        assert float(y[2, 0]) == 0.0 and float(y[3, S - 1]) == 1.0 and bool((y[4] == 1).all()) and bool((y[5] == 0).all())
+        assert float(ga[ZERO_GRAD_ROW].abs().max()) == 0.0, (S, neus)  # d == d_meas: sgn(0) = 0
+        assert int(rows.sum()) == SWEEP_RAYS - 5
+        # a permutation of row 0's probabilities is another ray (the stable order of equal depths is the column order)
+        if S >= 3 or float(y[0, 0]) != float(y[0, 1]):
+            yp = y.clone()
+            yp[0] = y[0].flip(0)
+            assert not torch.equal(ray_reference(x, yp, d, neus, torch.float32)[1][0], ga[0].flip(0)), (S, neus)
+
+
+LAUNCH_RAYS = (1, 127, 128, 129, 256, 131072, 131073, 131072 + 128 * 5 + 3)  # one workgroup (the gridDim == 1 branch), two,
+# exactly 1024 chunks, the chunk-stride pass (one more chunk, five more and a ragged one)
+LAUNCH_SAMPLES = (1, 8, 17, 32)
+DIFF_SIZES = (1, 255, 256, 257, 1023, 1024, 1025, 1 << 20, (1 << 20) + 1, (1 << 20) + 1025)  # 1024 points per workgroup, 1024
+# workgroups at most
+DIFF_SCALES = (0.0390625, -0.1)
+
+
+def diff_inputs(n, seed):
+    """pred, label, weight: every fifth label equal to the prediction, every seventh weight zero, both from index 1 on (the
+    point of n = 1 carries a difference and a weight)"""
+    g = torch.Generator().manual_seed(seed)
+    pred, label, weight = torch.randn(n, generator=g), torch.randn(n, generator=g), torch.rand(n, generator=g)
+    label[1::5] = pred[1::5]
+    weight[1::7] = 0.0
+    return pred, label, weight
+
+
+def test_launch_shape_recipes_hold_their_conditions():
+    for S in LAUNCH_SAMPLES:
+        for R in LAUNCH_RAYS[:5]:
+            x, y, d = ray_inputs(R, S, 2000 + S)
+            assert not saturated_rows(y).any() and x.shape == y.shape == (R, S) and d.shape == (R,)
+    chunks = [(R + 127) // 128 for R in LAUNCH_RAYS]
+    assert chunks == [1, 1, 1, 2, 2, 1024, 1025, 1030]
+    for n in DIFF_SIZES:
+        pred, label, weight = diff_inputs(n, 3000 + n)
+        assert torch.equal(pred[1::5], label[1::5]) and bool((weight[1::7] == 0).all())
+        assert bool((pred[::5] != label[::5]).all()) and bool((weight[::7] > 0).all())  # (index 0 among them: n = 1 is no zero)
+    assert [(n + 1023) // 1024 for n in DIFF_SIZES] == [1, 1, 1, 1, 1, 1, 2, 1024, 1025, 1026]
 
 
 def test_composites_reproduce_the_reference_fixture():

@@ -43,6 +43,116 @@ def ulp_close(a, b, ulps=8):
     return bool(((a - b).abs() <= tol + 1e-12).all()), float((a - b).abs().max())
 
 
+# ---- the sweeps over every class count and launch shape: CPU generators, so the conditions on the inputs can be checked here and
+# are the same on every machine; tests/test_gpu_semantic.py runs the kernels on exactly these inputs
+
+SWEEP_N = 321  # five 64-point tiles and one ragged lane, in two backward workgroups
+TICKET_CLASSES = (1, 20, 32)
+# backward workgroups (256 points each, 256 at most, ticket runs of 16): 1 .. 256 one; 257 two; 4096 a full run; 4097 a second run
+# of one; 65281 / 65536 all 256 with a ragged / full last tile; 65537 / 69700 the grid-stride pass on one wave / on 17 workgroups
+TICKET_SIZES = (1, 63, 64, 65, 256, 257, 4096, 4097, 65281, 65536, 65537, 69700)
+FWD_STRIDE_N = 2048 * 256 + 257  # the forward's 2048 workgroups and a second pass on two of them
+
+
+def sweep_params(C, seed=None):
+    """W1, b1, W2, b2, Wc [C, 32], bc [C] drawn as nn.Linear draws them (uniform in +-1 / sqrt(fan_in))"""
+    g = torch.Generator().manual_seed(100 + C if seed is None else seed)
+    out = []
+    for rows, cols in ((32, 8), (32, 32), (C, 32)):
+        bound = cols ** -0.5
+        out.append((torch.rand(rows, cols, generator=g) * 2 - 1) * bound)
+        out.append((torch.rand(rows, generator=g) * 2 - 1) * bound)
+    return out
+
+
+def sweep_inputs(C, n=SWEEP_N, seed=None):
+    """feat = 0.3 randn [n, 8], d loss / d logp = randn / n [n, C]"""
+    g = torch.Generator().manual_seed(C if seed is None else seed)
+    return torch.randn(n, 8, generator=g) * 0.3, torch.randn(n, C, generator=g) / n
+
+
+def decoder_from_params(params, device="cpu"):
+    """the project's Decoder(is_geo_encoder=False) holding the six tensors"""
+    from shine_mapping_amd import Decoder
+
+    dec = Decoder(sem_config(device, params[5].numel() - 1), is_geo_encoder=False)
+    named = dict(dec.named_parameters())
+    with torch.no_grad():
+        for k, p in zip(SEM_NAMES, params):
+            named[k].copy_(p)
+    return dec
+
+
+def kink_rows(params, f, eps=1e-5):
+    """rows with a hidden pre-activation within eps of 0 (in fp64): float32 rounding may put them on either side of ReLU's kink,
+    and the gradient jumps there"""
+    ps = [p.detach().double() for p in params]
+    z1 = f.double() @ ps[0].T + ps[1]
+    z2 = torch.relu(z1) @ ps[2].T + ps[3]
+    return (z1.abs() < eps).any(dim=1) | (z2.abs() < eps).any(dim=1)
+
+
+def fp64_logits(params, f):
+    ps = [p.detach().double() for p in params]
+    h = torch.relu(torch.relu(f.double() @ ps[0].T + ps[1]) @ ps[2].T + ps[3])
+    return h, h @ ps[4].T + ps[5]
+
+
+def tie_pairs(C):
+    """(i, j): row j of Wc and bc copied onto row i"""
+    return [(0, C - 1)] + ([(2, 3)] if C >= 4 else [])
+
+
+def value_case(kind, C):
+    """the six tensors for the value tests: "ties" one pair (C >= 4: two pairs) of classes with bit-identical logits on every
+    row, "large" logits of several hundred, "dead" no second-layer unit alive on any row"""
+    p = [t.clone() for t in sweep_params(C, 300 + C)]
+    if kind == "ties":
+        p[0] *= 10.0  # (spread the logits: an untrained head labels every row alike)
+        for i, j in tie_pairs(C):
+            p[4][i], p[5][i] = p[4][j], p[5][j]
+    elif kind == "large":
+        p[0] *= 30.0
+        p[4] *= 300.0
+    elif kind == "dead":
+        p[3].fill_(-10.0)
+    else:
+        raise ValueError(kind)
+    return p
+
+
+def test_sweep_inputs_stay_off_the_relu_kinks():
+    """the fp64 composite is a reference only off the kinks: at most max(2, n // 100) rows within 1e-5 of one"""
+    for C in range(1, 33):
+        f, dlogp = sweep_inputs(C)
+        assert f.shape == (SWEEP_N, 8) and dlogp.shape == (SWEEP_N, C)
+        k = int(kink_rows(sweep_params(C), f).sum())
+        assert k <= max(2, SWEEP_N // 100), (C, k)
+    for C in TICKET_CLASSES:
+        p = sweep_params(C)
+        for n in TICKET_SIZES + (FWD_STRIDE_N,):
+            k = int(kink_rows(p, sweep_inputs(C, n, 1000 + n)[0]).sum())
+            assert k <= max(2, n // 100), (C, n, k)
+    assert [min(256, (n + 255) // 256) for n in TICKET_SIZES] == [1, 1, 1, 1, 1, 2, 16, 17, 256, 256, 256, 256]
+
+
+def test_value_cases_hold_their_conditions():
+    for C in (2, 7, 32):
+        f, _ = sweep_inputs(C)
+        h, z = fp64_logits(value_case("ties", C), f)
+        for i, j in tie_pairs(C):
+            assert torch.equal(z[:, i], z[:, j])
+            assert int((z.argmax(dim=1) == min(i, j)).sum()) > 0, (C, i, j)  # (the pair is the argmax on some rows)
+        h, z = fp64_logits(value_case("large", C), f)
+        assert float(z.abs().max()) > 200.0, (C, float(z.abs().max()))
+        if C > 1:
+            assert float((z.max(dim=1).values - z.min(dim=1).values).max()) > 88.0  # exp() of a raw difference underflows
+        h, z = fp64_logits(value_case("dead", C), f)
+        assert float(h.max()) == 0.0, C
+        assert int(kink_rows(value_case("ties", C), f).sum()) <= max(2, SWEEP_N // 100)
+        assert not bool(kink_rows(sweep_params(C), torch.zeros(1, 8)).any()), C  # (zero features are off the kinks too)
+
+
 def test_fixture_is_consistent_with_the_composite():
     torch.set_num_threads(1)
     fx = load_fixture()
