@@ -277,6 +277,29 @@ int shine_sem_query_labels(const shine_tables* t, const shine_step_config* cfg, 
                            const float* const* feats, const int64_t* rows, const float* const* mlp, int32_t n_class,
                            int64_t* label_out, void* stream);
 
+/* ---- Tier B with semantic_on: the semantic term of one training iteration (shine_batch.py:132-133,200-204,
+ *      shine_incre.py:128-129,173-177) in ONE launch, beside shine_train_step on the same batch:
+ *        feature = query_feature(coord) (the interpolation of shine_query_points: the hash tables are probed from the coordinates),
+ *        logp = sem_label_prob(feature) (shine_sem_forward's head), sem_loss = NLLLoss('mean')(logp[::decimation],
+ *        label[::decimation]), and weight_s * d sem_loss / d {feature tables, W1, b1, W2, b2, Wc, bc}.
+ *      Only the ceil(n / decimation) rows i with i % decimation == 0 are computed.
+ *      coord: rows of coord_stride floats whose first three are x, y, z — 3: a plain [n,3] array; 8: the 32-byte records of a
+ *      node-ordered pool (either record layout; the slot words are not read).  idx: NULL, or int32 [n] — batch position i reads
+ *      row idx[i] of coord AND of labels (without idx: row i).  labels: int32, 0 <= label < n_class (the caller's precondition:
+ *      a label outside contributes a loss of 0 and the softmax part of the gradient only).
+ *      feats / rows / grad_feats as for shine_interp_backward: grad_feats[s] [rows_s+1,8] is ACCUMULATED INTO with fp32 atomics,
+ *      trash row included (NULL array / NULL entries: no gradient for that level).  mlp / n_class as for shine_sem_forward.
+ *      grad_mlp: NULL (a frozen head: only feature grads are written) or 6 tensors shaped like mlp that the sums are ADDED to by
+ *      the workgroup that finishes them; those sums and *sem_loss_out (float, the UNWEIGHTED mean) are bit-identical from call to
+ *      call.  workspace: SHINE_SEM_WORKSPACE_BYTES as for shine_sem_backward (always needed: the loss is summed there), zero when
+ *      first used, left zero: the launch can be captured into a HIP graph.  n == 0 launches nothing and writes a loss of 0.
+ *      SHINE_E_INVALID before anything touches the device: a null table handle, coord_stride other than 3 or 8, decimation < 1,
+ *      n_class outside 1..SHINE_SEM_MAX_CLASSES, null arguments, more than 4 featured levels. */
+int shine_sem_train_step(const shine_tables* t, const shine_step_config* cfg, const float* coord, int32_t coord_stride,
+                         const int32_t* idx, const int32_t* labels, int64_t n, int32_t decimation, float weight_s,
+                         const float* const* feats, const int64_t* rows, float* const* grad_feats, const float* const* mlp,
+                         int32_t n_class, float* const* grad_mlp, float* sem_loss_out, void* workspace, void* stream);
+
 /* ---- Tier A (strict drop-in): the backward of FeatureOctree.query_feature as autograd derives it from
  *      model/feature_octree.py:222-234, and its own backward (needed by get_gradient(create_graph=True),
  *      utils/tools.py:175-185, when the eikonal term is differentiated, shine_batch.py:182-185).

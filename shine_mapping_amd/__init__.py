@@ -7,6 +7,7 @@ Public surface mirrors the reference's modules for this path:
     sdf_diff_loss, batch_ray_rendering_loss   utils/loss.py (main_loss_type sdf_l1 / sdf_l2, dr / dr_neus)
     train_step / StepOptions            the fused Tier-B step (one HIP pass) as a torch.autograd.Function
     fused_train_step                    the same launch in raw form (grads written straight into .grad)
+    fused_sem_step                      semantic_on: the NLL term of the same batch, one more launch in raw form
     eval_mesh                           eval/eval_utils.py (mesh metrics against a ground-truth cloud; evaluation.py)
 All compute goes through libshine_hip.so (include/shine_hip.h); there is no CPU fallback.
 """
@@ -14,7 +15,7 @@ from .decoder import Decoder
 from .evaluation import eval_mesh
 from .feature_octree import FeatureOctree
 from .losses import batch_ray_rendering_loss, get_gradient, sdf_bce_loss, sdf_diff_loss
-from .ops import StepOptions, forward_sdf, fused_train_step, octree_interp, train_step
+from .ops import StepOptions, forward_sdf, fused_sem_step, fused_train_step, octree_interp, train_step
 
-__all__ = ["Decoder", "FeatureOctree", "StepOptions", "forward_sdf", "fused_train_step", "train_step", "octree_interp",
+__all__ = ["Decoder", "FeatureOctree", "StepOptions", "forward_sdf", "fused_train_step", "fused_sem_step", "train_step", "octree_interp",
            "sdf_bce_loss", "get_gradient", "sdf_diff_loss", "batch_ray_rendering_loss", "eval_mesh"]

@@ -1,0 +1,417 @@
+// shine_sem_step.hip — the semantic term of a training iteration in ONE launch (shine_batch.py:132-133,200-204,
+// shine_incre.py:128-129,173-177):
+//
+//   feature  = query_feature(coord)                 the interpolation of shine_query_points, hash tables probed from the coordinates
+//   logp     = sem_label_prob(feature)              the head of shine_semantic.hip (shine_sem_head.hpp), bit for bit its forward
+//   sem_loss = mean over rows i % d == 0 of -logp[i, label[i]]
+//   grads   += weight_s * d sem_loss / d {feature tables, W1, b1, W2, b2, Wc, bc}
+//
+// Only the m = ceil(n / d) decimated rows are computed.  One wave = one tile of 64 computed rows at a time, lane = row, exactly
+// k_sem_bwd's staging ([64][ST] floats of LDS per wave): forward through the head, dz = weight_s / m * (softmax - onehot), the
+// three weight-grad contractions, d feature, then the feature-grad scatter of shine_interp.hip's backward with the lanes
+// transposed to (row, feature) — one fp32 atomic instruction covers 8 rows x the 8 features of one corner each; the misses of a
+// wave reach the trash row as one atomic per feature.
+//
+// The six weight grads and the loss are summed as in k_sem_bwd (fixed order inside a wave and a workgroup, two ticket levels
+// across workgroups), so they are bit-identical from call to call; the workgroup that finishes the sum ADDS them to grad_mlp and
+// writes the loss.  What bounds the launch at the reference's batch (4096 rows = 64 tiles) is the latency of ONE tile through
+// the head and back — the rolled weight-row loops are chains of scalar loads and FMAs — not throughput: 64 waves on 16 CUs.
+#include "shine_sem_head.hpp"
+
+namespace shine {
+using namespace sem;
+namespace {
+
+constexpr int PS = P_N + 4;  // partial stride in floats: the six weight grads, then [P_N] the tile losses
+static_assert(kCounterBytes + (size_t)(kMaxBlocks + kGroups) * PS * sizeof(float) <= SHINE_SEM_WORKSPACE_BYTES, "workspace");
+
+constexpr int kWaves = kThreads / 64;  // waves of a workgroup, a tile each
+
+struct SemStepArgs {
+  LevelSet ls;
+  const float* coord;   // rows of `stride` floats, x y z first
+  const int* idx;       // [n] gather or null
+  const int* labels;    // indexed like coord
+  long long n, m;       // batch rows, computed rows ceil(n / d)
+  long long d;
+  int stride;
+  int C;
+  float gscale;         // weight_s / m
+  float inv_m;
+  SemArgsPtrs p;
+  SemGradPtrs gp;
+  int want_wgrad;
+  float* loss_out;
+  unsigned char* ws;
+};
+
+template <int L, bool POLY>
+__global__ __launch_bounds__(kThreads) void k_sem_step(const SemStepArgs a) {
+  __shared__ float s_stage[4 * 64 * ST];
+  __shared__ unsigned s_flag;
+  const SemW w = sem_weights(a.p.mlp);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  float* st = s_stage + wv * 64 * ST;
+  float* row = st + lane * ST;  // [0,32) left operands, [32,64) right operands
+  const int jj = lane & 31, hi = lane >> 5;
+  const int sub = lane >> 3, fi = lane & 7;
+  const bool wgrad = a.want_wgrad != 0;
+  const int rows = opaque(H);
+  const int nc = opaque(a.C);
+
+  float accWc[16], accW2[16], accW1[4];
+  float accbc = 0.f, accb2 = 0.f, accb1 = 0.f, accloss = 0.f;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) accWc[q] = 0.f, accW2[q] = 0.f;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) accW1[q] = 0.f;
+
+  const long long tiles = (a.m + 63) >> 6;
+  for (long long t = (long long)blockIdx.x * kWaves + wv; t < tiles; t += (long long)gridDim.x * kWaves) {
+    const long long r = t * 64 + lane;  // computed row; batch position r * d
+    const bool valid = r < a.m;
+    float x0 = 0.f, x1 = 0.f, x2 = 0.f;
+    int label = 0;
+    if (valid) {
+      const long long i = r * a.d;
+      const long long j = a.idx ? (long long)a.idx[i] : i;
+      const float* c = a.coord + j * a.stride;
+      x0 = c[0], x1 = c[1], x2 = c[2];
+      label = a.labels[j];
+    }
+    // ---- query_feature (k_sem_query's interpolation); a padding lane misses everywhere
+    float f[F];
+#pragma unroll
+    for (int k = 0; k < F; ++k) f[k] = 0.f;
+    int slot[L];
+#pragma unroll
+    for (int s = 0; s < L; ++s) slot[s] = valid ? level_slot(a.ls.lv[s], x0, x1, x2) : -1;
+#pragma unroll
+    for (int s = 0; s < L; ++s) {
+      const bool hit = slot[s] >= 0;
+      const LevelDev& Lv = a.ls.lv[s];
+      int ids[8];
+      corner_ids(Lv.vals, hit ? (unsigned int)slot[s] : 0u, ids);
+      const Axis X = axis_weight<POLY>(x0, Lv.res, Lv.dres), Y = axis_weight<POLY>(x1, Lv.res, Lv.dres),
+                 Z = axis_weight<POLY>(x2, Lv.res, Lv.dres);
+      float wc[8];
+      corner_weights(X.t, Y.t, Z.t, wc);
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const unsigned int off = (hit ? (unsigned int)ids[c] : 0u) * (unsigned int)F;
+        const float4 fa = *reinterpret_cast<const float4*>(Lv.feat + off);
+        const float4 fb = *reinterpret_cast<const float4*>(Lv.feat + off + 4u);
+        const float wz = hit ? wc[c] : 0.f;
+        f[0] += wz * fa.x, f[1] += wz * fa.y, f[2] += wz * fa.z, f[3] += wz * fa.w;
+        f[4] += wz * fb.x, f[5] += wz * fb.y, f[6] += wz * fb.z, f[7] += wz * fb.w;
+      }
+    }
+    // ---- the head forward: h2 kept in registers, logp left at row[0..C)
+    float h1[H];
+    unsigned m1, m2;
+    sem_hidden(w, f, row, h1, m1, m2);
+    float h2[H];
+#pragma unroll
+    for (int k = 0; k < H; ++k) h2[k] = row[k];
+    wave_lds_fence();
+    sem_head(w, row, a.C);
+    wave_lds_fence();
+    // NLLLoss('mean') on the m computed rows: d loss / d logp = -gscale at the label; dz = dlogp - exp(logp) sum_k dlogp_k
+    // (in place: every lane rewrites its own row, padding lanes / classes get 0)
+    float lp_label = 0.f;
+#pragma unroll
+    for (int c = 0; c < CM; ++c) {
+      float dz = 0.f;
+      if (valid && c < nc) {
+        const float lp = row[c];
+        if (c == label) lp_label = lp;
+        dz = (c == label ? -a.gscale : 0.f) + expf(lp) * a.gscale;
+      }
+      row[c] = dz;
+    }
+    accloss -= lp_label;
+#pragma unroll
+    for (int k = 0; k < H; ++k) row[32 + k] = h2[k];
+    wave_lds_fence();
+    if (wgrad) {  // dWc += dz (x) h2, dbc += dz
+      contract64r<16>(st, jj, 32 + hi * 16, accWc, accbc, true);
+      wave_lds_fence();
+    }
+    // dh2 = Wc^T dz; d2 = m2 .* dh2
+    float dd[H];
+#pragma unroll
+    for (int k = 0; k < H; ++k) dd[k] = 0.f;
+SEM_ROW_LOOP(2)
+    for (int c = 0; c < nc; ++c) {
+      const float dz = row[c];
+#pragma unroll
+      for (int k = 0; k < H; ++k) dd[k] = fmaf(w.WC[c * H + k], dz, dd[k]);
+    }
+    wave_lds_fence();
+#pragma unroll
+    for (int k = 0; k < H; ++k) row[k] = ((m2 >> k) & 1u) ? dd[k] : 0.f;
+#pragma unroll
+    for (int k = 0; k < H; ++k) row[32 + k] = h1[k];
+    wave_lds_fence();
+    if (wgrad) {  // dW2 += d2 (x) h1, db2 += d2
+      contract64r<16>(st, jj, 32 + hi * 16, accW2, accb2, true);
+      wave_lds_fence();
+    }
+    // dh1 = W2^T d2; d1 = m1 .* dh1
+#pragma unroll
+    for (int k = 0; k < H; ++k) dd[k] = 0.f;
+SEM_ROW_LOOP(2)
+    for (int j = 0; j < rows; ++j) {
+      const float d2 = row[j];
+#pragma unroll
+      for (int k = 0; k < H; ++k) dd[k] = fmaf(w.W2[j * H + k], d2, dd[k]);
+    }
+    wave_lds_fence();
+#pragma unroll
+    for (int k = 0; k < H; ++k) row[k] = ((m1 >> k) & 1u) ? dd[k] : 0.f;
+#pragma unroll
+    for (int q = 0; q < F; ++q) row[32 + q] = f[q];
+    wave_lds_fence();
+    // df = W1^T d1
+    float df[F];
+#pragma unroll
+    for (int q = 0; q < F; ++q) df[q] = 0.f;
+SEM_ROW_LOOP(8)
+    for (int k = 0; k < rows; ++k) {
+      const float dk = row[k];
+#pragma unroll
+      for (int q = 0; q < F; ++q) df[q] = fmaf(w.W1[k * F + q], dk, df[q]);
+    }
+    if (wgrad) {  // dW1 += d1 (x) f, db1 += d1
+      contract64r<4>(st, jj, 32 + hi * 4, accW1, accb1, true);
+    }
+    wave_lds_fence();
+    // ---- feature grads: df through LDS once ([row][feature] -> lane (row & 7 group, feature)), ids and weights by shuffle
+#pragma unroll
+    for (int q = 0; q < F; ++q) st[lane * F + q] = df[q];
+    wave_lds_fence();
+    float gval[8];
+#pragma unroll
+    for (int G = 0; G < 8; ++G) gval[G] = st[G * 64 + lane];
+    wave_lds_fence();
+#pragma unroll
+    for (int s = 0; s < L; ++s) {
+      const LevelDev& Lv = a.ls.lv[s];
+      if (!Lv.grad) continue;  // (wave-uniform)
+      const bool hit = slot[s] >= 0;
+      int ids[8];
+      corner_ids(Lv.vals, hit ? (unsigned int)slot[s] : 0u, ids);
+      const Axis X = axis_weight<POLY>(x0, Lv.res, Lv.dres), Y = axis_weight<POLY>(x1, Lv.res, Lv.dres),
+                 Z = axis_weight<POLY>(x2, Lv.res, Lv.dres);
+      float wc[8];
+      corner_weights(X.t, Y.t, Z.t, wc);
+      float csum = 0.f;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        csum += wc[c];
+        const int sid = hit ? ids[c] : -1;
+#pragma unroll
+        for (int G = 0; G < 8; ++G) {
+          const int id = __shfl(sid, G * 8 + sub, 64);
+          const float cf = __shfl(wc[c], G * 8 + sub, 64);
+          if (id >= 0) atomic_add_f32(Lv.grad + (long long)id * F + fi, cf * gval[G]);
+        }
+      }
+      // a miss: all eight corners address the trash row, which receives sum_c w_c * df — one atomic per wave and feature
+      if (__any(valid && !hit)) {
+        const float cm = (valid && !hit) ? csum : 0.f;
+#pragma unroll
+        for (int q = 0; q < F; ++q) {
+          const float tsum = wave_sum(cm * df[q]);
+          if (lane == 0 && tsum != 0.f) atomic_add_f32(Lv.grad + Lv.rows * F + q, tsum);
+        }
+      }
+    }
+  }
+
+  // ---- the workgroup's partial: its waves summed in index order through LDS
+  accloss = wave_sum(accloss);
+  __syncthreads();
+  constexpr int NV = 40;
+  float vals[NV];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) vals[q] = accWc[q], vals[16 + q] = accW2[q];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) vals[32 + q] = accW1[q];
+  vals[36] = accbc, vals[37] = accb2, vals[38] = accb1, vals[39] = accloss;
+#pragma unroll
+  for (int v = 0; v < NV; ++v) s_stage[(wv * NV + v) * 64 + lane] = vals[v];
+  __syncthreads();
+  float* part = reinterpret_cast<float*>(a.ws + kCounterBytes);
+  float* mine = part + (size_t)blockIdx.x * PS;
+  if (wv == 0) {
+#pragma unroll
+    for (int ww = 1; ww < kWaves; ++ww) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) vals[v] += s_stage[(ww * NV + v) * 64 + lane];
+    }
+    if (wgrad) {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        mine[P_WC + jj * H + hi * 16 + q] = vals[q];
+        mine[P_W2 + jj * H + hi * 16 + q] = vals[16 + q];
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) mine[P_W1 + jj * F + hi * 4 + q] = vals[32 + q];
+      if (hi == 0) {
+        mine[P_BC + jj] = vals[36];
+        mine[P_B2 + jj] = vals[37];
+        mine[P_B1 + jj] = vals[38];
+      }
+    }
+    if (lane == 0) mine[P_N] = vals[39];
+  }
+  unsigned* cnt = reinterpret_cast<unsigned*>(a.ws);
+  float* runsum = part + (size_t)kMaxBlocks * PS;  // [kGroups][PS]
+  const unsigned G = gridDim.x;
+  const unsigned grp = blockIdx.x / kGroup;
+  const unsigned g0 = grp * kGroup;
+  const unsigned gsz = (G - g0) < (unsigned)kGroup ? (G - g0) : (unsigned)kGroup;
+  const unsigned ngrp = (G + kGroup - 1) / kGroup;
+  // the sums below walk the partial vectors four floats at a time (PS, every tensor's offset and the loss's slot P_N are
+  // multiples of four; the three floats behind the loss are summed along and never used)
+  static_assert(PS % 4 == 0 && P_N % 4 == 0 && P_B1 % 4 == 0 && P_BC % 4 == 0, "float4 walk");
+  const int c0 = wgrad ? 0 : P_N / 4;  // a frozen head: only the loss is summed
+
+  // level 1: the last workgroup of this run to arrive sums the run's partials in index order
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned tk = __hip_atomic_fetch_add(cnt + 1 + grp, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    s_flag = (tk == gsz - 1) ? 1u : 0u;
+  }
+  __syncthreads();
+  if (s_flag == 0u) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  for (int c = c0 + threadIdx.x; c <= P_N / 4; c += (int)blockDim.x) {
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (unsigned b = 0; b < gsz; ++b) {
+      const float4 v = *reinterpret_cast<const float4*>(part + (size_t)(g0 + b) * PS + 4 * c);
+      s.x += v.x, s.y += v.y, s.z += v.z, s.w += v.w;
+    }
+    *reinterpret_cast<float4*>(runsum + (size_t)grp * PS + 4 * c) = s;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __hip_atomic_store(cnt + 1 + grp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next call
+    const unsigned tk = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    s_flag = (tk == ngrp - 1) ? 2u : 0u;
+  }
+  __syncthreads();
+  if (s_flag != 2u) return;
+  // level 2: the last run to finish sums the run sums in index order, ADDS the six gradients and writes the loss
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  for (int c = c0 + threadIdx.x; c <= P_N / 4; c += (int)blockDim.x) {
+    float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (unsigned q = 0; q < ngrp; ++q) {
+      const float4 v = *reinterpret_cast<const float4*>(runsum + (size_t)q * PS + 4 * c);
+      s4.x += v.x, s4.y += v.y, s4.z += v.z, s4.w += v.w;
+    }
+    const float sv[4] = {s4.x, s4.y, s4.z, s4.w};
+    if (4 * c == P_N) {
+      a.loss_out[0] = sv[0] * a.inv_m;
+      continue;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int k = 4 * c + e;
+      const float s = sv[e];
+      if (k < P_B1) a.gp.g[0][k - P_W1] += s;
+      else if (k < P_W2) a.gp.g[1][k - P_B1] += s;
+      else if (k < P_B2) a.gp.g[2][k - P_W2] += s;
+      else if (k < P_WC) a.gp.g[3][k - P_B2] += s;
+      else if (k < P_BC) {
+        if (k - P_WC < a.C * H) a.gp.g[4][k - P_WC] += s;
+      } else if (k - P_BC < a.C) {
+        a.gp.g[5][k - P_BC] += s;
+      }
+    }
+  }
+  if (threadIdx.x == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Launch shape: four waves per workgroup, a tile each, at most kMaxBlocks workgroups with a grid stride past 64 K rows; it
+// depends on m alone, so equal batches sum in equal order.  (One wave per workgroup — a tile per CU up to 16 K rows — was
+// measured at N = 4096: 8 us less with the head frozen, 13 us MORE with it training, where 64 partial vectors instead of 16
+// meet in the ticket sums; not kept.  DESIGN.md 3.15.)
+template <int L, bool POLY>
+void launch_sem_step_p(const SemStepArgs& a, hipStream_t st) {
+  const long long tiles = (a.m + 63) / 64;
+  const long long b = (tiles + kWaves - 1) / kWaves;
+  hipLaunchKernelGGL((k_sem_step<L, POLY>), dim3((unsigned)(b > kMaxBlocks ? kMaxBlocks : b)), dim3(kThreads), 0, st, a);
+}
+
+template <int L>
+void launch_sem_step(const SemStepArgs& a, bool poly, hipStream_t st) {
+  if (poly) launch_sem_step_p<L, true>(a, st);
+  else launch_sem_step_p<L, false>(a, st);
+}
+
+}  // namespace
+}  // namespace shine
+
+using namespace shine;
+
+extern "C" int shine_sem_train_step(const shine_tables* t, const shine_step_config* cfg, const float* coord, int32_t coord_stride,
+                                    const int32_t* idx, const int32_t* labels, int64_t n, int32_t decimation, float weight_s,
+                                    const float* const* feats, const int64_t* rows, float* const* grad_feats,
+                                    const float* const* mlp, int32_t n_class, float* const* grad_mlp, float* sem_loss_out,
+                                    void* workspace, void* stream) {
+  if (!t) return set_error(SHINE_E_INVALID, "shine_sem_train_step: null table handle");
+  if (coord_stride != 3 && coord_stride != 8)
+    return set_error(SHINE_E_INVALID, "shine_sem_train_step: coord_stride is 3 ([n,3] array) or 8 (32-byte pool records)");
+  if (decimation < 1) return set_error(SHINE_E_INVALID, "shine_sem_train_step: decimation < 1");
+  SemStepArgs a = {};
+  int rc = fill_mlp(&a.p, mlp, n_class, "shine_sem_train_step: decoder parameters / n_class (1..32)");
+  if (rc != SHINE_OK) return rc;
+  if (n < 0 || !feats || !rows || !sem_loss_out || (n > 0 && (!coord || !labels)))
+    return set_error(SHINE_E_INVALID, "shine_sem_train_step: null argument");
+  if (!workspace || ((size_t)workspace & 255)) return set_error(SHINE_E_INVALID, "shine_sem_train_step: workspace");
+  if (grad_mlp)
+    for (int k = 0; k < 6; ++k) {
+      if (!grad_mlp[k]) return set_error(SHINE_E_INVALID, "shine_sem_train_step: null weight-grad tensor");
+      a.gp.g[k] = grad_mlp[k];
+    }
+  rc = make_level_set(t, cfg, feats, rows, grad_feats, &a.ls);
+  if (rc != SHINE_OK) return rc;
+  const int L = cfg->n_levels;
+  if (L > 4) return set_error(SHINE_E_INVALID, "shine_sem_train_step: more than 4 featured levels");
+  for (int s = 0; s < L; ++s) {
+    if (!feats[s]) return set_error(SHINE_E_INVALID, "shine_sem_train_step: null feature level");
+    if (rows[s] >= (1ll << 29)) return set_error(SHINE_E_INVALID, "shine_sem_train_step: level exceeds 2^29 rows");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0) {
+    SHINE_HIP_CHECK(hipMemsetAsync(sem_loss_out, 0, sizeof(float), st));
+    return SHINE_OK;
+  }
+  const long long m = (n + decimation - 1) / decimation;
+  a.coord = coord;
+  a.idx = idx;
+  a.labels = labels;
+  a.n = n;
+  a.m = m;
+  a.d = decimation;
+  a.stride = coord_stride;
+  a.C = n_class;
+  a.gscale = weight_s / (float)m;
+  a.inv_m = 1.0f / (float)m;
+  a.want_wgrad = grad_mlp ? 1 : 0;
+  a.loss_out = sem_loss_out;
+  a.ws = (unsigned char*)workspace;
+  const bool poly = cfg->poly_int_on != 0;
+  switch (L) {
+    case 1: launch_sem_step<1>(a, poly, st); break;
+    case 2: launch_sem_step<2>(a, poly, st); break;
+    case 3: launch_sem_step<3>(a, poly, st); break;
+    default: launch_sem_step<4>(a, poly, st); break;
+  }
+  SHINE_HIP_CHECK(hipGetLastError());
+  return SHINE_OK;
+}

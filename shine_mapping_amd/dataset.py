@@ -695,11 +695,13 @@ class LiDARDataset:
             raise ValueError("LiDARDataset.sorted_pool serves the point-sample pools on the device (not ray_loss, not the CPU pool)")
         key = (self._pool_version, self.octree._tables_epoch)
         if self._sorted is None or self._sorted[1] != key:
+            # (semantic_on: the labels travel with the pool, checked against the head's class count)
+            sem = dict(sem_label=self.sem_label_pool, n_class=int(self.config.sem_class_count) + 1) if self.semantic else {}
             if self._sorted is None:
-                sp = SortedPool(self.octree, self.coord_pool, self.sdf_label_pool, self.weight_pool, seed=self.seed)
+                sp = SortedPool(self.octree, self.coord_pool, self.sdf_label_pool, self.weight_pool, seed=self.seed, **sem)
             else:
                 sp = self._sorted[0]
-                sp.rebuild(self.coord_pool, self.sdf_label_pool, self.weight_pool)
+                sp.rebuild(self.coord_pool, self.sdf_label_pool, self.weight_pool, **sem)
             self._sorted = (sp, key)
             self._sorted_perm = sp.perm.long()
         return self._sorted[0]

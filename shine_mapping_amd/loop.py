@@ -15,14 +15,30 @@ device memory and are advanced by the kernels themselves (shine_sample_sorted_de
 replay draws a fresh batch and applies the right bias correction.  Learning-rate decay stays outside the graph
 (`opt.sync_lr()` after changing `param_groups`).  Re-create after `octree.update()` (parameters are re-allocated, like
 the optimiser itself, shine_incre.py:108-109).
+
+With `sem=SemTerm(...)` (semantic_on) the iteration is {fused step, semantic step, tail} on the same batch: the semantic step
+(ops.fused_sem_step, one launch) adds weight_s * d NLL / d {features, head} to the grads the tail's Adam consumes, and while the
+head trains its six tensors get one more graph-safe Adam launch of their own (the tail keeps its feature-table + decoder set).
 """
 import ctypes as C
+from dataclasses import dataclass
 
 import torch
 
 from . import _lib
 from .autograd_ops import bump_param_epoch
-from .ops import StepOptions, fused_regularization, fused_train_step, touched_flags
+from .autograd_ops import SEM_WORKSPACE_BYTES
+from .ops import StepOptions, fused_regularization, fused_sem_step, fused_train_step, touched_flags
+
+
+@dataclass
+class SemTerm:
+    """The semantic term of GraphedIteration(sem=...): the semantic decoder (Decoder(config, is_geo_encoder=False)), the
+    reference's config.weight_s and config.sem_label_decimation (shine_batch.py:132-133,200-204)."""
+
+    decoder: object
+    weight_s: float = 1.0
+    decimation: int = 1
 
 
 _CAPTURE_STREAM = {}
@@ -124,7 +140,8 @@ class GraphedIteration:
     object every frame: the eager iteration costs ~0.1 ms of launches that a replay does in a third of the time)."""
 
     def __init__(self, octree, decoder, pool, opt, opts: StepOptions, n: int, lambda_forget: float = 0.0, unroll: int = 1,
-                 fold: bool = True, eager_first: bool = True, active_rows: bool = True, native: bool = True, graph_slot: int = 0):
+                 fold: bool = True, eager_first: bool = True, active_rows: bool = True, native: bool = True, graph_slot: int = 0,
+                 sem: SemTerm = None):
         self.octree, self.decoder, self.pool, self.opt, self.opts, self.n = octree, decoder, pool, opt, opts, int(n)
         self.lambda_forget = float(lambda_forget)
         self.graph_slot = int(graph_slot)
@@ -155,11 +172,21 @@ class GraphedIteration:
         # the constructor runs no iteration whatever `eager_first` says.  Needs the two-launch iteration (fold, the next draw
         # inside the tail: n < 16 K).
         self.native = bool(native and can_fold and self.n + 1 <= 16 * 1024)
+        self.sem = sem
+        self.sem_loss = None
+        if sem is not None:
+            self._init_sem(can_fold)
         self.ran_eager = (not self.native) and (bool(eager_first) or dev_key not in _WARMED or not can_fold)
         if can_fold:
             # the optimiser's device-side step state up front: the eager warm-up iteration then runs the SAME two launches the
             # graph replays (with active rows it has to: its rows must end up flagged "touched earlier")
-            self.opt.prepare_graph_safe()
+            if sem is None:
+                self.opt.prepare_graph_safe()
+            else:  # (the head's lout never receives a gradient, model/decoder.py:89-101: it stays out of the stepped set)
+                skip = list(sem.decoder.lout.parameters())
+                if hasattr(decoder, "nclass_out"):  # (nor does the geometry decoder's class layer)
+                    skip += list(decoder.nclass_out.parameters())
+                self.opt.prepare_graph_safe(skip=skip)
         if self.ran_eager:
             # eager warm-up: allocates workspaces and optimiser state and loads the kernels outside the capture
             self.loss, self.reg = self._body()
@@ -180,6 +207,26 @@ class GraphedIteration:
         self.graph = self.graph_k = None
         self._out_1 = self._out_k = None
         self._native = {}  # unroll -> (IterationGraph, outputs, keep-alive) bound to this object's buffers
+
+    def _init_sem(self, can_fold):
+        """the semantic term's buffers, all made here: a captured graph bakes their addresses in"""
+        sem = self.sem
+        if not can_fold:
+            raise ValueError("GraphedIteration(sem=...) needs the folded iteration (fold=True, a FusedAdam optimiser)")
+        if getattr(self.pool, "sem_label", None) is None:
+            raise ValueError("GraphedIteration(sem=...) needs a SortedPool built with sem_label=")
+        if int(sem.decimation) < 1:
+            raise ValueError("sem_label_decimation must be >= 1")
+        self.native = False  # (the library-built graph holds the two-launch iteration)
+        dev = self.pool.coord.device
+        self._sem_params = list(sem.decoder.sem_params())
+        train = [p.requires_grad for p in self._sem_params]
+        if any(train) != all(train):
+            raise ValueError("the semantic head's six tensors must all train or all be frozen")
+        self._sem_train = all(train)
+        self._sem_ws = torch.zeros(SEM_WORKSPACE_BYTES // 8, dtype=torch.float64, device=dev)
+        self._sem_out = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.sem_loss = self._sem_out[0]
 
     def _graph_1(self):
         if self.graph is None:
@@ -236,6 +283,8 @@ class GraphedIteration:
                                       idx=idx, touched=self.touched, pending=pending, graph=graph)
         if keep is not None:
             keep["pending"] = pending  # (every device buffer the nodes name stays alive with this object)
+        if self.sem is not None:
+            return self._sem_tail(idx, fold, pending, loss)
         if fold:
             self.opt.finish_iteration(pending, dict(lambda_forget=self.lambda_forget, touched=self.touched,
                                                     out=self._reg_out) if self.regularize else None,
@@ -247,6 +296,23 @@ class GraphedIteration:
             reg = fused_regularization(self.octree, self.lambda_forget, self.touched, out=self._reg_out, out_zeroed=hooked)
         self.opt.step(zero_grad=True, graph_safe=True, advanced=hooked)
         return loss, reg
+
+    def _sem_tail(self, idx, fold, pending, loss):
+        """semantic_on: the semantic step on the batch the fused step just read (its touched flags cover the same rows), the
+        tail on the feature tables + decoder, and — while the head trains — the head's own Adam launch"""
+        if not fold:
+            raise RuntimeError("GraphedIteration(sem=...): the optimiser has no device-side step state")
+        sem = self.sem
+        fused_sem_step(self.octree, sem.decoder, None, None, float(sem.weight_s), int(sem.decimation), pool=self.pool, idx=idx,
+                       out=self._sem_out, workspace=self._sem_ws)
+        head = self._sem_params if self._sem_train else []
+        self.opt.finish_iteration(pending, dict(lambda_forget=self.lambda_forget, touched=self.touched,
+                                                out=self._reg_out) if self.regularize else None,
+                                  next_draw=self.pool.next_draw(self.n, self._idx, self._surf) if self._ahead else None,
+                                  active_flags=self.touched if self.active_rows else None, others=head)
+        if head:
+            self.opt.step_tensors_dev(head)
+        return loss, (self._reg_out[0] if self.regularize else None)
 
     def __call__(self):
         """Run one iteration; returns the loss of the fused terms as a 0-dim device tensor (no host sync)."""

@@ -280,6 +280,86 @@ def _fused_launch(octree, decoder, coord, sdf_label, weight, opts: StepOptions, 
     return loss_parts[3], pred, gx  # 0-dim float64 view: BCE (+ weight_e * eikonal), no extra launch
 
 
+def fused_sem_step(octree, sem_decoder, coord, sem_label, weight_s, decimation=1, pool=None, idx=None, grad_buffers=None,
+                   out=None, workspace=None):
+    """The semantic term of one training iteration (shine_batch.py:132-133,200-204) in ONE launch (shine_sem_train_step):
+
+        sem_loss = NLLLoss('mean')(sem_decoder.sem_label_prob(octree.query_feature(coord))[::decimation], sem_label[::decimation])
+        (weight_s * sem_loss).backward()
+
+    coord [N,3] float32, sem_label [N] int32 with 0 <= label < the head's class count (the caller's precondition: SortedPool checks
+    its labels at rebuild), or pool = a SortedPool built with sem_label= and idx = pool.draw(n): the batch is read straight out of
+    the pool's records (coord / sem_label are ignored).  Returns the UNWEIGHTED sem_loss as a 0-dim float32 device tensor (no host
+    sync, no grad_fn — the gradients are already in place; `out`: a float32 tensor of one element to write it to).
+    Accumulates into ``.grad`` of octree.hier_features[*] and of the head's six tensors exactly as fused_train_step does (dense,
+    trash row included), or into `grad_buffers` = (L feature-grad tensors, 6 head-grad tensors | None) instead.  A head whose
+    parameters do not require grad (freeze_model) gets no gradient: only the feature grads are written.
+    `workspace`: SHINE_SEM_WORKSPACE_BYTES of zeroed device memory the caller owns (default: the current stream's,
+    autograd_ops.sem_workspace)."""
+    t = octree._require_tables()  # (the kernel probes the hash tables from the coordinates)
+    mlp = sem_decoder.sem_params()
+    n_class = int(mlp[4].shape[0])
+    decimation = int(decimation)
+    if decimation < 1:
+        raise ValueError("decimation must be >= 1")
+    if pool is not None:
+        if idx is None or not (idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous()):
+            raise ValueError("pool mode needs idx = SortedPool.draw(n) (CUDA int32)")
+        if pool.tables_epoch != octree._tables_epoch:
+            raise RuntimeError("the octree grew since the pool was planned: call SortedPool.rebuild()")
+        labels = getattr(pool, "sem_label", None)
+        if labels is None:
+            raise ValueError("pool mode needs a SortedPool built with sem_label=")
+        if getattr(pool, "rec", None) is not None:
+            src, stride = pool.rec, 8
+        else:
+            src, stride = pool.soa()[0], 3
+        n = int(idx.numel())
+    else:
+        src, stride = octree._check_coord(coord.detach()), 3
+        labels = sem_label
+        n = int(src.shape[0])
+        if idx is not None:
+            if not (idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous()):
+                raise ValueError("idx must be a contiguous CUDA int32 tensor")
+            n = int(idx.numel())
+        elif labels.numel() != n:
+            raise ValueError("sem_label must hold one label per coordinate")
+    if not (labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous()):
+        raise ValueError("sem_label must be a contiguous CUDA int32 tensor")
+    dev = src.device
+    if not sem_decoder._params_on(dev, mlp):
+        raise ValueError("the semantic decoder's parameters must be CUDA float32 contiguous on the batch's device")
+    gfeat, gmlp = grad_buffers if grad_buffers is not None else (None, None)
+    if gfeat is None:
+        gfeat = [_dense_grad(p) if p.requires_grad else None for p in octree.feature_list()]
+    if grad_buffers is None:
+        train = [p.requires_grad for p in mlp]
+        if any(train) != all(train):
+            raise ValueError("the semantic head's six tensors must all require grad or all be frozen")
+        gmlp = [_dense_grad(p) for p in mlp] if all(train) else None
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.numel() == 1):
+        raise ValueError("out must be a CUDA float32 tensor of one element")
+    ws = workspace if workspace is not None else autograd_ops.sem_workspace(dev)
+    cfg = octree.step_config()
+    _lib.check(
+        _lib.lib().shine_sem_train_step(
+            t.handle, C.byref(cfg), src.data_ptr(), stride, idx.data_ptr() if idx is not None else None, labels.data_ptr(), n,
+            decimation, float(weight_s), octree.feature_ptrs(), octree.row_counts(),
+            _lib.ptr_array([g.data_ptr() if g is not None else None for g in gfeat]),
+            _lib.ptr_array([p.data_ptr() for p in mlp]), n_class,
+            _lib.ptr_array([g.data_ptr() for g in gmlp]) if gmlp is not None else None,
+            out.data_ptr(), ws.data_ptr(), _stream(),
+        ),
+        "shine_sem_train_step",
+    )
+    if not torch.cuda.is_current_stream_capturing():
+        octree._tables_read_done()
+    return out.view(())
+
+
 def octree_interp(octree, coord):
     """FeatureOctree.query_feature (model/feature_octree.py:237-244) -> [N,8]; also fills hierarchical_indices."""
     needs_grad = torch.is_grad_enabled() and (

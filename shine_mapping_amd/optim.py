@@ -338,14 +338,18 @@ def setup_optimizer(config, octree_feat, mlp_geo_param, mlp_sem_param=None, sigm
     return FusedAdam(groups, betas=(0.9, 0.99), eps=getattr(config, "adam_eps", 1e-15))
 
 
-def _prepare_graph_safe(self):
+def _prepare_graph_safe(self, skip=()):
     """Create the device-side step state (what the first step(graph_safe=True) does) without taking a step, so that an
-    iteration can be captured into a HIP graph without an eager one in front of it."""
+    iteration can be captured into a HIP graph without an eager one in front of it.
+    `skip`: parameters that never receive a gradient (the semantic decoder's lout): they get no zero gradient here, so they stay
+    out of the stepped set as torch.optim.Adam keeps them out — with weight decay a zero gradient would still move them."""
+    skip = {id(p) for p in skip}
     # the dense gradient tensors the fused step would create on its first launch and the optimiser's exp_avg / exp_avg_sq, for
     # every parameter that has neither yet: views of ONE zero-filled buffer (incremental mapping builds a new optimiser every
     # frame, shine_incre.py:107-109: 27 small fills per frame otherwise)
     fresh = [p for g in self.param_groups for p in g["params"]
-             if p.requires_grad and p.grad is None and p not in self.state and p.is_cuda and p.dtype == torch.float32]
+             if p.requires_grad and p.grad is None and p not in self.state and p.is_cuda and p.dtype == torch.float32
+             and id(p) not in skip]
     if fresh:
         sizes = [(p.numel() + 3) // 4 * 4 for p in fresh]  # (16-byte aligned views)
         total = sum(sizes)
@@ -361,7 +365,7 @@ def _prepare_graph_safe(self):
             self.state[p] = (m.view(p.shape), v.view(p.shape))
     for g in self.param_groups:
         for p in g["params"]:
-            if p.requires_grad and p.grad is None:
+            if p.requires_grad and p.grad is None and id(p) not in skip:
                 p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
     ts = self._tensors()
     if not ts:
@@ -378,7 +382,7 @@ def _prepare_graph_safe(self):
     return self._dev[0]
 
 
-def _finish_iteration(self, pending, regulariser=None, next_draw=None, active_flags=None, graph=None):
+def _finish_iteration(self, pending, regulariser=None, next_draw=None, active_flags=None, graph=None, others=()):
     """The tail of an iteration in ONE launch (shine_finish_iteration): `pending` is the dict a
     fused_train_step(..., pending=...) filled — its partial sums are added up where they are consumed, the regulariser
     (regulariser = dict(lambda_forget, touched, out) as for ops.fused_regularization) is evaluated on the touched rows, Adam
@@ -388,7 +392,9 @@ def _finish_iteration(self, pending, regulariser=None, next_draw=None, active_fl
     active_flags (the per-level uint8 flags the step was given as `touched`): EXACT active-row Adam — the flags are kept sticky
     and rows whose flag is 0 (no gradient since this optimiser and the flags were created: m = v = g = 0, which torch's Adam
     leaves bit for bit unchanged) are not read.  The caller zeroes the flags whenever it creates the optimiser.
-    graph (loop.IterationGraph): nothing is launched — the launch becomes the tail node of the library-built iteration graph."""
+    graph (loop.IterationGraph): nothing is launched — the launch becomes the tail node of the library-built iteration graph.
+    others: tensors of this optimiser that a launch of their own steps (step_tensors_dev: the semantic head) — the tail selects
+    the feature tables and the decoder and leaves these alone."""
     if self._dev is None:
         raise RuntimeError("finish_iteration needs the device-side step state: run one step(graph_safe=True) first")
     bump_param_epoch()
@@ -396,7 +402,9 @@ def _finish_iteration(self, pending, regulariser=None, next_draw=None, active_fl
     ts = self._tensors()
     by_param = {id(t[0]): (i, t) for i, t in enumerate(ts)}
     order = list(octree.hier_features) + (list(decoder.fused_params()) if pending["dec_grad"] else [])
-    if len(order) != len(ts) or any(id(p) not in by_param for p in order):
+    other_ids = {id(p) for p in others}
+    if (len(order) + len(other_ids) != len(ts) or any(id(p) not in by_param for p in order)
+            or any(i not in by_param for i in other_ids) or any(id(p) in other_ids for p in order)):
         raise NotImplementedError("finish_iteration: the optimiser must hold exactly the feature tables and the decoder tensors "
                                   "that receive grads")
     if self._dev[1].numel() != len(ts):
@@ -442,5 +450,39 @@ def _finish_iteration(self, pending, regulariser=None, next_draw=None, active_fl
         "shine_finish_iteration")
 
 
+@torch.no_grad()
+def _step_tensors_dev(self, params):
+    """One graph-replayable Adam launch (shine_adam_step_dev) on `params` alone — a run of consecutive tensors of the
+    device-state set, e.g. the semantic head's six — with the step state another launch of the iteration already advanced
+    (the fused step, StepOptions.adam_state) and the grads cleared in the same pass: zero_grad bits 1 | 2.  The learning rates
+    are read from the device copy sync_lr() maintains."""
+    if self._dev is None:
+        raise RuntimeError("step_tensors_dev needs the device-side step state: call prepare_graph_safe() first")
+    ts = self._tensors()
+    if self._dev[1].numel() != len(ts):
+        raise RuntimeError("step_tensors_dev: the set of tensors changed since the device state was made")
+    by_param = {id(t[0]): i for i, t in enumerate(ts)}
+    pos = [by_param.get(id(p)) for p in params]
+    if not pos or any(i is None for i in pos) or pos != list(range(pos[0], pos[0] + len(pos))):
+        raise NotImplementedError("step_tensors_dev: the tensors must be consecutive members of the optimiser's stepped set")
+    sel = [ts[i] for i in pos]
+    for p, m, v, _, _ in sel:
+        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad.is_contiguous()):
+            raise ValueError("FusedAdam needs contiguous CUDA float32 parameters and grads")
+    n = len(sel)
+    bump_param_epoch()
+    _lib.check(
+        _lib.lib().shine_adam_step_dev(
+            n, _lib.ptr_array([t[0].data_ptr() for t in sel]), _lib.ptr_array([t[0].grad.data_ptr() for t in sel]),
+            _lib.ptr_array([t[1].data_ptr() for t in sel]), _lib.ptr_array([t[2].data_ptr() for t in sel]),
+            _lib.i64_array([t[0].numel() for t in sel]), self._dev[1].data_ptr() + 4 * pos[0],
+            (C.c_float * n)(*[t[4] for t in sel]), float(self.betas[0]), float(self.betas[1]), float(self.eps),
+            self._dev[0].data_ptr(), 1 | 2, None, _lib.current_stream_handle(),
+        ),
+        "shine_adam_step_dev",
+    )
+
+
 FusedAdam.finish_iteration = _finish_iteration
+FusedAdam.step_tensors_dev = _step_tensors_dev
 FusedAdam.prepare_graph_safe = _prepare_graph_safe

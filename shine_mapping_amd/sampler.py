@@ -114,12 +114,15 @@ class DrawChain:
 
 
 class SortedPool:
-    def __init__(self, octree, coord, sdf_label, weight, seed=42, canonical=False):
+    def __init__(self, octree, coord, sdf_label, weight, seed=42, canonical=False, sem_label=None, n_class=None):
         """`canonical`: order the samples of one node by their original pool index.  The plan's counting sort places the
         samples of a node in whatever order its atomics retire, so two processes (or two runs) hold the same pool in
         different within-node orders: still a valid pool — draws stay i.i.d. uniform — but not the SAME draw.  Data-parallel
         ranks that want literally one global batch (and anyone who wants run-to-run reproducible draws) pass True; it costs
-        one device sort of the pool per rebuild."""
+        one device sort of the pool per rebuild.
+        `sem_label` (semantic_on): the samples' labels; kept in pool order as `self.sem_label` (int32) for
+        ops.fused_sem_step(pool=...).  `n_class` (the semantic head's class count): every rebuild checks 0 <= label < n_class
+        and raises ValueError otherwise (one min / max, outside the iteration)."""
         self.octree = octree
         self.canonical = bool(canonical)
         self.seed = int(seed)
@@ -127,9 +130,19 @@ class SortedPool:
         self._ws = {}  # per batch size, never replaced: captured HIP graphs bake the address in
         self._stream_state = None  # device uint64[4] for graph-replayable draws (loop.GraphedIteration)
         self._rider_for = None     # size of the draw whose first pass the last fused step carried (StepOptions.next_draw)
-        self.rebuild(coord, sdf_label, weight)
+        self.n_class = None if n_class is None else int(n_class)
+        self.rebuild(coord, sdf_label, weight, sem_label=sem_label)
 
-    def rebuild(self, coord, sdf_label, weight):
+    def rebuild(self, coord, sdf_label, weight, sem_label=None, n_class=None):
+        if n_class is not None:
+            self.n_class = int(n_class)
+        if sem_label is not None:
+            if sem_label.shape[0] != coord.shape[0] or sem_label.dim() != 1:
+                raise ValueError("sem_label must hold one label per pool sample")
+            if self.n_class is not None and sem_label.numel():
+                lo, hi = int(sem_label.min()), int(sem_label.max())
+                if lo < 0 or hi >= self.n_class:
+                    raise ValueError("sem_label out of range: [%d, %d] with %d classes" % (lo, hi, self.n_class))
         perm, slots = plan_batch(self.octree, coord, sort=True)  # (node order whatever the pool's size: it is drawn from many times)
         if self.canonical and perm.numel() > 1:
             order = canonical_order(perm, slots)
@@ -170,6 +183,10 @@ class SortedPool:
             self.sdf_label = sdf_label[p].contiguous()
             self.weight = weight[p].contiguous()
             self.slots = slots  # already in pool (= visiting) order
+        if sem_label is not None:
+            self.sem_label = sem_label[p].to(torch.int32).contiguous()
+        elif hasattr(self, "sem_label"):
+            del self.sem_label  # (a rebuild without labels: nothing stale is kept)
         self.tables_epoch = self.octree._tables_epoch
         # sampler scratch of other pool sizes is dead weight (a graph captured for the old pool is invalid anyway: the
         # tables epoch moved); without this an object rebuilt every frame pins one buffer per distinct frame size
