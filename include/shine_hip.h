@@ -715,6 +715,34 @@ int shine_pool_window_filter(const float* coord, int64_t n, const float* origin,
                              const void* const* src, void* const* dst, const int32_t* words, void* workspace,
                              size_t* workspace_bytes, int64_t* n_out, void* stream);
 
+/* ---- neighbourhood searches over a frame's OWN cloud (csrc/shine_frame_nn.hip): LiDARDataset's filter_noise
+ *      (open3d remove_statistical_outlier) and estimate_normal (open3d estimate_normals with KDTreeSearchParamHybrid).  fp64.
+ *      The cloud is searched through the grid shine_eval_grid_count / shine_eval_grid_emit built over it: grid, n (= the cloud's
+ *      point count), n_fine, n_coarse, origin (HOST double[3]), cell and cells_per_axis (HOST int64[3]) are shine_eval_nn_search's.
+ *      Results are in the caller's point order.  workspace == NULL returns the bytes needed in *workspace_bytes.  Squared
+ *      distances are (dx*dx + dy*dy) + dz*dz of the fp64 differences, no fused multiply-add.
+ *      _knn_search: for every point its k (1..32) nearest points of the cloud, itself included at distance 0, limited to squared
+ *        distance <= radius * radius if radius >= 0 (radius < 0: unbounded).  Ascending squared distance, equal distances by
+ *        ascending index.  idx_out [n][k] (-1 where there is no neighbour), d2_out [n][k] (+inf there), count_out [n].
+ *      _sor_mean_dist: the unbounded search, reduced in the kernel: mean_dist_out [n] = mean of sqrt(d2) over the min(k, n)
+ *        neighbours found (the point's own 0 included, as open3d's SearchKNN includes it); stats_out (DEVICE double[2]) = {mean
+ *        of mean_dist_out, sum of squared deviations from that mean}, added in a fixed order: the same bits on every run.
+ *      Unbounded searches are exact: a first pass searches one coarse cell edge around every point, the points whose list did not
+ *      fill are searched again with twice the radius, and so on until none is left or the radius covers the grid; the count of
+ *      unfinished points is read back once per round (synchronises).  *rounds_out (HOST, may be NULL) = search launches made.
+ *      _frame_normals: the search with radius (finite, >= 0) and max_nn (1..32); normals_out [n][3] = the unit eigenvector of the
+ *        smallest eigenvalue of the neighbours' covariance about their own mean (cyclic Jacobi), (0, 0, 1) where fewer than 3
+ *        neighbours are found or all of them coincide, negated where n . (viewpoint - p) < 0 (viewpoint HOST double[3]). -------- */
+int shine_knn_search(const void* grid, int64_t n, int64_t n_fine, int64_t n_coarse, const double* origin, double cell,
+                     const int64_t* cells_per_axis, int32_t k, double radius, void* workspace, size_t* workspace_bytes,
+                     int32_t* idx_out, double* d2_out, int32_t* count_out, int32_t* rounds_out, void* stream);
+int shine_sor_mean_dist(const void* grid, int64_t n, int64_t n_fine, int64_t n_coarse, const double* origin, double cell,
+                        const int64_t* cells_per_axis, int32_t k, void* workspace, size_t* workspace_bytes, double* mean_dist_out,
+                        double* stats_out, int32_t* rounds_out, void* stream);
+int shine_frame_normals(const void* grid, int64_t n, int64_t n_fine, int64_t n_coarse, const double* origin, double cell,
+                        const int64_t* cells_per_axis, double radius, int32_t max_nn, const double* viewpoint, void* workspace,
+                        size_t* workspace_bytes, double* normals_out, void* stream);
+
 /* ---- graph-replayable forms of the two calls whose per-iteration scalars are otherwise baked into a captured HIP
  *      graph: the scalars live in device memory and the kernels advance them, so ONE captured iteration
  *      {draw, shine_train_step, [shine_regularize], Adam} can be replayed for every iteration of a frame.

@@ -70,6 +70,8 @@ class StepConfig(C.Structure):
 
 
 _P = C.c_void_p
+# a search grid as shine_eval_nn_search and the frame searches take it: grid, n, n_fine, n_coarse, origin, cell, cells_per_axis
+_GRID = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int64)]
 _SIGNATURES = {
     # name: (restype, argtypes)
     "shine_version": (C.c_int, []),
@@ -227,6 +229,10 @@ _SIGNATURES = {
     "shine_pool_window_filter": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_float), C.c_float, C.c_int32, C.POINTER(_P),
                                            C.POINTER(_P), C.POINTER(C.c_int32), _P, C.POINTER(C.c_size_t),
                                            C.POINTER(C.c_int64), _P]),
+    # neighbourhood searches over a frame's own cloud (csrc/shine_frame_nn.hip); the first seven arguments are the grid's
+    "shine_knn_search": (C.c_int, _GRID + [C.c_int32, C.c_double, _P, C.POINTER(C.c_size_t), _P, _P, _P, C.POINTER(C.c_int32), _P]),
+    "shine_sor_mean_dist": (C.c_int, _GRID + [C.c_int32, _P, C.POINTER(C.c_size_t), _P, _P, C.POINTER(C.c_int32), _P]),
+    "shine_frame_normals": (C.c_int, _GRID + [C.c_double, C.c_int32, C.POINTER(C.c_double), _P, C.POINTER(C.c_size_t), _P, _P]),
     "shine_iter_graph_create": (C.c_int, [C.c_int32, C.POINTER(_P)]),
     "shine_iter_graph_destroy": (C.c_int, [_P]),
     "shine_iter_graph_commit": (C.c_int, [_P]),

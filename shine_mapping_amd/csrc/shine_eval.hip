@@ -21,42 +21,16 @@
 //                       original fp64 coordinates.
 //   metrics             one launch: the sums, sums of squares and below-threshold counts of the two distance arrays (fixed
 //                       partition into blocks, the last block to finish adds the partials in block order).
-#include "shine_internal.hpp"
+#include "shine_eval_grid.hpp"
 
 namespace {
 
+using namespace shine::grid;  // the grid's constants, layout and cell arithmetic (shared with shine_frame_nn.hip)
+
 constexpr int T = 256;
-constexpr int FINE_BITS = 2;                     // fine cells per coarse cell edge = 1 << FINE_BITS
-constexpr int FINE_PER_COARSE = 1 << FINE_BITS;
-constexpr int LOCAL_BITS = 3 * FINE_BITS;        // low bits of a sort key: the fine cell inside its coarse cell
-constexpr int AXIS_BITS = 21;                    // fine cell index bits per axis
-constexpr int COARSE_BITS = AXIS_BITS - FINE_BITS;
-constexpr long long AXIS_MAX = (1ll << AXIS_BITS) - 1;
-constexpr double MARGIN = 1.0 / (1 << 20);       // cell units: slack of every box bound (cell assignment rounds at ~2^-32)
-constexpr unsigned long long EMPTY = ~0ull;
 constexpr int RED_BLOCKS = 256;                  // blocks of the bounds / metrics reductions
 
 unsigned grid_of(long long n) { return (unsigned)((n + T - 1) / T); }
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct Carve {
-  char* base;
-  size_t off = 0;
-  void* take(size_t b) {
-    char* p = base ? base + off : nullptr;
-    off += align256(b);
-    return p;
-  }
-};
-
-struct Vec3 {
-  double x, y, z;
-};
-
-struct Cell {  // a fine-cell entry, or a slot of the coarse table
-  unsigned long long key;
-  int first, end;
-};
 
 __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -272,21 +246,6 @@ __global__ void k_voxel_mean_attr(const double* __restrict__ p, const double* __
 }
 
 // ---------------------------------------------------------------- nearest neighbour: the grid
-// sort key of a fine cell (ix, iy, iz): the coarse cell (ix >> 2, ...) in bits 6.., the fine cell inside it in bits 0..5
-__device__ __forceinline__ unsigned long long grid_key(unsigned long long ix, unsigned long long iy, unsigned long long iz) {
-  const unsigned long long m = FINE_PER_COARSE - 1;
-  const unsigned long long local = ((ix & m) << (2 * FINE_BITS)) | ((iy & m) << FINE_BITS) | (iz & m);
-  return (((ix >> FINE_BITS) << (2 * COARSE_BITS)) | ((iy >> FINE_BITS) << COARSE_BITS) | (iz >> FINE_BITS)) << LOCAL_BITS | local;
-}
-
-__device__ __forceinline__ unsigned long long coarse_key(long long cx, long long cy, long long cz) {
-  return ((unsigned long long)cx << (2 * COARSE_BITS)) | ((unsigned long long)cy << COARSE_BITS) | (unsigned long long)cz;
-}
-
-__device__ __forceinline__ unsigned int coarse_slot(unsigned long long key, unsigned int shift) {
-  return (unsigned int)((key * 0x9E3779B97F4A7C15ull) >> shift);
-}
-
 __global__ void k_grid_keys(const double* __restrict__ p, long long n, Vec3 o, double cell, unsigned long long* __restrict__ keys,
                             unsigned long long* __restrict__ vals) {
   const long long i = (long long)blockIdx.x * T + threadIdx.x;
@@ -340,30 +299,12 @@ __global__ void k_coarse_insert(const Cell* __restrict__ coarse, long long n_coa
   }
 }
 
-struct GridDev {
-  const double* pts;   // [n][3] reference points, sorted by cell
-  const int* sidx;     // [n] their indices in the caller's array
-  const Cell* fine;    // [n_fine]
-  const Cell* table;   // [mask + 1] coarse cells, open addressing
-  unsigned int shift, mask;
-  Vec3 o;
-  double cell;
-  long long cmax[3];   // largest coarse cell index per axis
-};
-
 __global__ void k_query_keys(const double* __restrict__ q, long long n, Vec3 o, double cell, unsigned long long* __restrict__ keys,
                              unsigned long long* __restrict__ vals) {
   const long long i = (long long)blockIdx.x * T + threadIdx.x;
   if (i >= n) return;
   keys[i] = grid_key(cell_of(q[3 * i], o.x, cell), cell_of(q[3 * i + 1], o.y, cell), cell_of(q[3 * i + 2], o.z, cell));
   vals[i] = (unsigned long long)i;
-}
-
-// squared distance from t (cell units) to the box [lo, lo + w] widened by MARGIN, along one axis
-__device__ __forceinline__ double axis_gap(double t, double lo, double w) {
-  const double below = (lo - MARGIN) - t, above = t - (lo + w + MARGIN);
-  const double g = fmax(fmax(below, above), 0.0);
-  return g;
 }
 
 __global__ __launch_bounds__(T) void k_nn_search(GridDev g, const double* __restrict__ q, const unsigned long long* __restrict__ order,
@@ -519,39 +460,6 @@ __global__ __launch_bounds__(T) void k_metrics(const double* __restrict__ dp, lo
   }
   if (threadIdx.x == 6) out[6] = (double)np;
   if (threadIdx.x == 7) out[7] = (double)nr;
-}
-
-bool bad_count(int64_t n) { return n < 0 || n >= (1ll << 31); }
-
-struct GridLayout {
-  double* pts;
-  int* sidx;
-  Cell* fine;
-  Cell* coarse;
-  Cell* table;
-  long long cap;
-  size_t bytes;
-};
-
-GridLayout grid_layout(void* buf, long long n, long long n_fine, long long n_coarse) {
-  Carve c{(char*)buf};
-  GridLayout L;
-  L.pts = (double*)c.take((size_t)n * 24);
-  L.sidx = (int*)c.take((size_t)n * 4);
-  L.fine = (Cell*)c.take((size_t)n_fine * sizeof(Cell));
-  L.coarse = (Cell*)c.take((size_t)n_coarse * sizeof(Cell));
-  long long cap = 16;
-  while (cap < 2 * n_coarse) cap <<= 1;
-  L.cap = cap;
-  L.table = (Cell*)c.take((size_t)cap * sizeof(Cell));
-  L.bytes = c.off;
-  return L;
-}
-
-unsigned int log2_of(long long pow2) {
-  unsigned int b = 0;
-  while ((1ll << b) < pow2) ++b;
-  return b;
 }
 
 // the workspace of shine_eval_grid_count, read again by shine_eval_grid_emit
@@ -806,21 +714,9 @@ extern "C" int shine_eval_nn_search(const void* grid, int64_t n_ref, int64_t n_f
   if (nq == 0) return SHINE_OK;
   if (!grid || !origin || !cells_per_axis || !query || !index_out || !dist_out || !keep_out || !(cell > 0.0) || !(truncation >= 0.0))
     return shine::set_error(SHINE_E_INVALID, "shine_eval_nn_search: null argument, cell <= 0 or truncation < 0");
-  const GridLayout L = grid_layout(const_cast<void*>(grid), n_ref, n_fine, n_coarse);
   GridDev g;
-  g.pts = L.pts;
-  g.sidx = L.sidx;
-  g.fine = L.fine;
-  g.table = L.table;
-  g.mask = (unsigned int)(L.cap - 1);
-  g.shift = 64u - log2_of(L.cap);
-  g.o = Vec3{origin[0], origin[1], origin[2]};
-  g.cell = cell;
-  for (int a = 0; a < 3; ++a) {
-    if (cells_per_axis[a] < 1 || cells_per_axis[a] > AXIS_MAX + 1)
-      return shine::set_error(SHINE_E_INVALID, "shine_eval_nn_search: cells_per_axis out of range (1 .. 2^21)");
-    g.cmax[a] = (cells_per_axis[a] - 1) >> FINE_BITS;
-  }
+  if (!grid_dev(grid, n_ref, n_fine, n_coarse, origin, cell, cells_per_axis, &g))
+    return shine::set_error(SHINE_E_INVALID, "shine_eval_nn_search: cells_per_axis out of range (1 .. 2^21)");
   LAUNCH(k_query_keys, nq, query, nq, g.o, cell, k0, v0);
   SHINE_HIP_CHECK(shine::prim_sort_pairs_u64(tmp, sort_bytes, k0, k1, v0, v1, (size_t)nq, 0u, 63u, st));
   if (stats_out) SHINE_HIP_CHECK(hipMemsetAsync(stats_out, 0, 8, st));
