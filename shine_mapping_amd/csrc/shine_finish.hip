@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) void k_finish(const FinArgs a, int fb, int db)
       // launch are already counting the next batch's surface samples into a.n_surf
       const long long ns = a.n_surf ? (long long)reinterpret_cast<const double*>(a.partials + PART_LOSS)[3] : 0;
       const double bce = a.reduction_sum ? ls : ls * (double)a.inv_n;
-      const double eik = ns > 0 ? es * (double)(1.0f / (float)ns) : 0.0;
+      const double eik = ns > 0 ? es / (double)ns : 0.0;  // (as k_reduce_partials: the mean, not a rounded 1 / n)
       a.loss_parts[0] = bce;
       a.loss_parts[1] = eik;
       a.loss_parts[2] = cs;

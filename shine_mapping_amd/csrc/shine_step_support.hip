@@ -193,7 +193,7 @@ __global__ __launch_bounds__(1024) void k_reduce_partials(V1Args a, int nblocks,
     }
     const long long ns = s_ns;
     const double bce = a.reduction_sum ? ls : ls * (double)a.inv_n;
-    const double eik = ns > 0 ? es * (double)(1.0f / (float)ns) : 0.0;
+    const double eik = ns > 0 ? es / (double)ns : 0.0;  // the mean as the reference takes it: n equal terms give that term
     a.loss_parts[0] = bce;
     a.loss_parts[1] = eik;
     a.loss_parts[2] = cs;

@@ -393,15 +393,23 @@ __global__ __launch_bounds__(256) void k_step_v0(StepArgs a) {
       }
     }
     double ls = wave_sum_d(loss_acc), es = wave_sum_d(eik_acc), cs = wave_sum_d(cnt_acc);
-    if (lane == 0 && a.loss_parts) {
+    if (lane == 0 && a.loss_parts) {  // (the eikonal SUM: k_v0_loss_parts divides it by the surface count and adds the total)
       const double bce = a.reduction_sum ? ls : ls * (double)a.inv_n;
-      const double eik = EIK ? es * (double)inv_nsurf : 0.0;
       atomicAdd(a.loss_parts + 0, bce);
-      if (EIK) atomicAdd(a.loss_parts + 1, eik);
+      if (EIK) atomicAdd(a.loss_parts + 1, es);
       atomicAdd(a.loss_parts + 2, cs);
-      atomicAdd(a.loss_parts + 3, bce + (double)a.weight_e * eik);
     }
   }
+}
+
+// after the step: loss_parts[1] = the eikonal mean (sum / surface count, as the reference takes it: n equal terms give that term),
+// loss_parts[3] = the total of the fused terms
+__global__ void k_v0_loss_parts(double* parts, const long long* n_surf, float weight_e) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const long long ns = n_surf ? *n_surf : 0;
+  const double eik = ns > 0 ? parts[1] / (double)ns : 0.0;
+  parts[1] = eik;
+  parts[3] = parts[0] + (double)weight_e * eik;
 }
 
 static unsigned grid_for(long long n) {
@@ -474,6 +482,9 @@ extern "C" int shine_train_step_v0(const shine_tables* t, const shine_step_confi
     launch_v0<true, true>(a, cfg->poly_int_on != 0, (hipStream_t)stream);
   else
     launch_v0<false, true>(a, cfg->poly_int_on != 0, (hipStream_t)stream);
+  if (loss_parts)
+    hipLaunchKernelGGL(k_v0_loss_parts, dim3(1), dim3(64), 0, (hipStream_t)stream, loss_parts,
+                       cfg->eikonal_on ? a.n_surf : nullptr, a.weight_e);
   SHINE_HIP_CHECK(hipGetLastError());
   return SHINE_OK;
 }
