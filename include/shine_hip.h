@@ -602,6 +602,32 @@ int shine_mc_sparse_emit(const float* values, const uint8_t* mask, int64_t n, in
                          float level, void* workspace, size_t workspace_bytes, int64_t n_records, int64_t n_faces, void* scratch,
                          size_t* scratch_bytes, float* verts_out, int32_t* faces_out, int64_t* n_verts_out, void* stream);
 
+/* ---- the block cache of incremental meshing (csrc/shine_mesh_cache.hip; Mesher.update_octree_mesh).  All
+ *      pointer ARRAYS are host arrays of device pointers, all count arrays host int64; levels are featured slots, top-down.
+ *      _rows_diff: ONE launch over n_levels feature tables.  rows[s] = rows of table s INCLUDING its last, "trash" row, which is
+ *        never compared; snap_rows[s] = rows snapshot s holds (it has room for rows[s] - 1).  flags[s][i] (u8, i < rows[s] - 1) =
+ *        1 iff i >= snap_rows[s] or the 32 bytes of row i differ BITWISE from the snapshot's (-0.0 differs from 0.0, an
+ *        identical NaN does not); the snapshot row is overwritten exactly where the flag is 1.  changed (DEVICE int64[n_levels])
+ *        is ADDED to: the flagged rows per level (an integer atomic per workgroup).  Tables and snapshots 16-byte aligned.
+ *      _mesh_mark_dirty: which nodes of slot sq can have changed.  Per slot: node_keys [n_nodes[s]] (Morton, insertion order),
+ *        node_ids [n_nodes[s], 8] int32 corner rows, prev_nodes[s] = the node count at the previous call, row_flags[s]
+ *        [flag_rows[s]] from _rows_diff.  For the slots s <= sq also sorted_keys[s] (ascending) and sorted_perm[s] (int64: sorted
+ *        position -> insertion index).  A node j of slot s is dirty iff j >= prev_nodes[s] or one of its 8 rows is flagged;
+ *        dirty_out [n_nodes[sq]] u8 = 1 iff the node is dirty itself, or a dirty node of a finer slot has key >> 3 (s - sq) equal
+ *        to its key, or the node of a coarser slot with its key >> 3 (sq - s) exists and is dirty; else 0.  counts_out (DEVICE
+ *        int64[2]) = {dirty among the first prev_nodes[sq] nodes, dirty in all}.  Two launches (scatter, then gather + count).
+ *      _blocks_scatter: values [capacity, block_points] f32 and masks (same shape, u8) receive n queried blocks: block b of sdf
+ *        [n, block_points] goes to block index[b] (DEVICE int64 [n]; an index outside [0, capacity) is skipped); masks gets
+ *        mask[b] != 0, or 0 with mask == NULL. -------- */
+int shine_rows_diff(int32_t n_levels, const float* const* feats, float* const* snaps, const int64_t* rows, const int64_t* snap_rows,
+                    uint8_t* const* flags, int64_t* changed, void* stream);
+int shine_mesh_mark_dirty(int32_t n_levels, int32_t sq, const int64_t* const* node_keys, const int32_t* const* node_ids,
+                          const int64_t* n_nodes, const int64_t* prev_nodes, const uint8_t* const* row_flags, const int64_t* flag_rows,
+                          const int64_t* const* sorted_keys, const int64_t* const* sorted_perm, uint8_t* dirty_out,
+                          int64_t* counts_out, void* stream);
+int shine_blocks_scatter(const float* sdf, const uint8_t* mask, const int64_t* index, int64_t n, int64_t block_points,
+                         int64_t capacity, float* values, uint8_t* masks, void* stream);
+
 /* ---- mesh evaluation: eval/eval_utils.py (eval_mesh, nn_correspondance, crop_intersection) on the device
  *      (csrc/shine_eval.hip; layout and rules in DESIGN.md 3.10).  All geometry is fp64; counts are int64 and < 2^31.
  *      Workspaces follow rocPRIM's convention: workspace == NULL returns the bytes needed in *workspace_bytes.

@@ -197,6 +197,13 @@ _SIGNATURES = {
                                         C.c_float, _P, C.POINTER(C.c_size_t), C.POINTER(C.c_int64), _P]),
     "shine_mc_sparse_emit": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_float, _P, C.c_size_t,
                                        C.c_int64, C.c_int64, _P, C.POINTER(C.c_size_t), _P, _P, C.POINTER(C.c_int64), _P]),
+    # the block cache of incremental meshing (csrc/shine_mesh_cache.hip)
+    "shine_rows_diff": (C.c_int, [C.c_int32, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                  C.POINTER(_P), _P, _P]),
+    "shine_mesh_mark_dirty": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P),
+                                        _P, _P, _P]),
+    "shine_blocks_scatter": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
     # mesh evaluation (csrc/shine_eval.hip)
     "shine_eval_fine_per_coarse": (C.c_int, []),
     "shine_eval_bounds": (C.c_int, [_P, C.c_int64, _P, C.POINTER(C.c_size_t), _P, _P]),

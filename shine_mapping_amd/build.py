@@ -2,7 +2,8 @@
 
     python -m shine_mapping_amd.build [--force]
 
-  lib/libshine_hip.so    the PRODUCT: csrc/*.hip — the fused step (shine_step_v3.hip) and everything around it
+  lib/libshine_hip.so    the PRODUCT: csrc/*.hip — the fused step (shine_step_v3.hip) and everything around it (every .hip file
+                         of csrc/ is a translation unit of it, shine_mesh_cache.hip included: see sources())
   lib/libshine_check.so  the product's objects + shine_step_v0.hip (the lane-per-point reference step): the on-device
                          cross-check of the GPU tests.  Only tests / tools load it (StepOptions.kernel_variant 1).
   lib/_shine_ext.so      csrc/shine_torch_ext.cpp: Tier A's autograd nodes as a torch C++ extension over the C ABI (host code

@@ -213,6 +213,96 @@ def split_blocks(t, B):
     return t.view(M, q, B, q, B, q, B).permute(0, 1, 3, 5, 2, 4, 6).reshape(M * q ** 3, B, B, B)
 
 
+# ------------------------------------------------------------------------------------- the block cache
+def mesh_cache_key(query_level, k, mc_res_scaled, mask_on, check_level, world_scale):
+    """What a cached block's values depend on besides the map: a cache built under another key is dropped."""
+    return (int(query_level), int(k), float(mc_res_scaled), bool(mask_on), int(check_level), float(world_scale))
+
+
+def keys_are_prefix(cached_keys, keys):
+    """True iff the node keys seen at the previous call are the first len(cached_keys) of the current ones (the tables are
+    append-only in insertion order, so anything else means they were replaced)"""
+    n = len(cached_keys)
+    return n <= len(keys) and bool(np.array_equal(np.asarray(keys[:n]), np.asarray(cached_keys)))
+
+
+def mesh_cache_rebuild_reason(cached, key, decoder_same, node_keys, node_ids, rows):
+    """Why update_octree_mesh must rebuild its cache from nothing, or None.  `cached`: None, or an object with `key`, and per
+    featured level `node_keys`, `node_ids` (the host tables seen at the previous call) and `snap_rows` (rows without the trash
+    row); `node_keys` / `node_ids` / `rows` are the current ones; `decoder_same()` is asked only when the key matches.  Every
+    level's tables must be a prefix, not the query level's alone: the cache holds device copies of all of them, appended by count."""
+    if cached is None:
+        return "first"
+    if cached.key != key:
+        return "key"
+    if not decoder_same():
+        return "decoder"
+    if (any(int(r) < int(c) for r, c in zip(rows, cached.snap_rows))
+            or not all(keys_are_prefix(c, k) for c, k in zip(cached.node_keys, node_keys))
+            or not all(keys_are_prefix(c, i) for c, i in zip(cached.node_ids, node_ids))):
+        return "octree"
+    return None
+
+
+def grown_capacity(have, need):
+    """rows to allocate for a buffer that holds `have` and must hold `need`: geometric, so appending does not copy per frame"""
+    return int(have) if need <= have else max(int(need), 2 * int(have), 16)
+
+
+class _MeshCache:
+    """The state update_octree_mesh keeps between calls."""
+
+    def __init__(self, key, decoder_bits, levels):
+        self.key = key
+        self.decoder_bits = decoder_bits  # the geo decoder's parameters, one int32 view
+        self.values = self.masks = None  # [capacity, k, k, k] f32 (half-rounded) / u8
+        self.node_keys = [np.zeros(0, np.int64) for _ in range(levels)]  # the host tables of the previous call (the octree
+        self.node_ids = [np.zeros((0, 8), np.int32) for _ in range(levels)]  # replaces these arrays, it never writes into them)
+        self.snaps = [None] * levels  # hier_features[s] without its trash row, [capacity, 8]
+        self.snap_rows = [0] * levels
+        self.dev_keys = [None] * levels  # the octree's node keys / corner ids on the device, appended per call
+        self.dev_ids = [None] * levels
+        self.dev_nodes = [0] * levels
+        self.sorted = [None] * levels  # (node count, sorted keys, permutation) of the slots <= sq
+
+
+def _grow_rows(buf, used, need, tail, dtype, device):
+    cap = grown_capacity(0 if buf is None else buf.shape[0], need)
+    if buf is not None and cap == buf.shape[0]:
+        return buf
+    new = torch.empty((cap,) + tuple(tail), dtype=dtype, device=device)
+    if used:
+        new[:used] = buf[:used]
+    return new
+
+
+def rows_diff_device(feats, snaps, snap_rows, flags, changed):
+    """shine_rows_diff (csrc/shine_mesh_cache.hip): feats[s] [rows, 8] f32 with the trash row last, snaps[s] with room for rows - 1,
+    flags[s] u8 [rows - 1], changed int64 [levels] (added to); one launch."""
+    _lib.check(_lib.lib().shine_rows_diff(
+        len(feats), _lib.ptr_array([f.data_ptr() for f in feats]), _lib.ptr_array([s.data_ptr() for s in snaps]),
+        _lib.i64_array([f.shape[0] for f in feats]), _lib.i64_array(snap_rows), _lib.ptr_array([f.data_ptr() for f in flags]),
+        changed.data_ptr(), _stream()), "shine_rows_diff")
+
+
+def mark_dirty_device(sq, node_keys, node_ids, n_nodes, prev_nodes, flags, sorted_keys, sorted_perm, dirty, counts):
+    """shine_mesh_mark_dirty: per slot device node keys / [n, 8] int32 corner ids / row flags, host counts; sorted keys and
+    permutation (or None) per slot; dirty u8 [n_nodes[sq]] and counts int64 [2] are outputs."""
+    ptr = lambda ts: _lib.ptr_array([t.data_ptr() if t is not None else None for t in ts])
+    _lib.check(_lib.lib().shine_mesh_mark_dirty(
+        len(node_keys), int(sq), ptr(node_keys), ptr(node_ids), _lib.i64_array(n_nodes), _lib.i64_array(prev_nodes), ptr(flags),
+        _lib.i64_array([f.shape[0] for f in flags]), ptr(sorted_keys), ptr(sorted_perm), dirty.data_ptr(), counts.data_ptr(),
+        _stream()), "shine_mesh_mark_dirty")
+
+
+def blocks_scatter_device(sdf, mask, index, values, masks):
+    """shine_blocks_scatter: block b of `sdf` / `mask` ([n * k^3], mask bool / u8 or None) -> block index[b] of values / masks"""
+    n, k3 = int(index.shape[0]), int(values[0].numel())
+    _lib.check(_lib.lib().shine_blocks_scatter(sdf.data_ptr(), mask.data_ptr() if mask is not None else None, index.data_ptr(), n,
+                                               k3, int(values.shape[0]), values.data_ptr(), masks.data_ptr(), _stream()),
+               "shine_blocks_scatter")
+
+
 def box_candidate_tiles(nodes, node_res_scaled, world_scale, voxel_origin, voxel_size, shape, B=BOX_BRICK):
     """Tiles (B^3 points, tile coordinates [T,3] int64, sorted) of a box grid — point (i, j, l) at voxel_origin + (i, j, l) *
     voxel_size metres — that may hold a point inside one of `nodes` (centres [M,3] in scaled coordinates, edge
@@ -428,6 +518,8 @@ class Mesher:
         self.ts = 0
         self.global_transform = np.eye(4)
         self.last_mesh_device = None  # (verts f64, faces int32) of the last mesh _finish made, on the device
+        self._mesh_cache = None  # update_octree_mesh's blocks, snapshots and node tables (reset_mesh_cache drops them)
+        self.last_update_stats = None
 
     def get_query_from_bbx(self, bbx, voxel_size):
         """utils/mesher.py:110-152: grid query points of a box (anything with get_min_bound()/get_max_bound(), e.g. an
@@ -585,8 +677,9 @@ class Mesher:
         if cn is not None:
             rgb = np.clip(np.round(cn * 255.0), 0, 255).astype(np.uint8)
             props += [("red", rgb[:, 0], "uchar"), ("green", rgb[:, 1], "uchar"), ("blue", rgb[:, 2], "uchar")]
-        write_ply(mesh_path, props, fn)
-        print("save the mesh to %s\n" % (mesh_path))
+        if mesh_path is not None:  # (update_octree_mesh may be asked for the arrays only)
+            write_ply(mesh_path, props, fn)
+            print("save the mesh to %s\n" % (mesh_path))
         mesh = _make_mesh(vn, fn, nn, cn)
         if isinstance(mesh, TriangleMesh) and labels is not None:
             mesh.vertex_labels = labels.cpu().numpy()
@@ -731,31 +824,38 @@ class Mesher:
         `chunks` yields (h, t, sdf, mask) for the nodes h..t-1: the blocks' (t - h) * k^3 values, block-major and (x, y, z)
         inside a block, and their mask, None with config.mc_mask_on off.  The reference keeps its grid as float16 (:323); the
         values are rounded the same way (.half().float()) so the meshes agree."""
+        nodes, node_res_scaled, k, mc_res_scaled, shape, shift, voxel, origin = self._block_layout(query_level, mc_res_m)
+        return k, shape, shift, voxel, origin, self._query_blocks(nodes, node_res_scaled, k, mc_res_scaled)
+
+    def _block_layout(self, query_level, mc_res_m):
+        """octree_grid_layout plus the grid's (voxel size m, origin m)"""
         nodes, node_res_scaled, k, mc_res_scaled, shape, shift = self.octree_grid_layout(query_level, mc_res_m)
         voxel = mc_res_scaled / self.world_scale
         origin = (np.min(nodes, 0) - 0.5 * (node_res_scaled - mc_res_scaled)) / self.world_scale
+        return nodes, node_res_scaled, k, mc_res_scaled, shape, shift, voxel, origin
 
-        def chunks():
-            dev = self.octree.hier_features[0].device
-            # the reference's node block: int16 grid coordinates, float32, times mc_res_scaled (:304-313)
-            ax = torch.arange(k, dtype=torch.int16, device=dev)
-            gx, gy, gz = torch.meshgrid(ax, ax, ax, indexing="ij")
-            block = torch.stack((gx.flatten(), gy.flatten(), gz.flatten())).transpose(0, 1).float()
-            block *= mc_res_scaled
-            block64 = block.double()
-            origins = torch.as_tensor(nodes - 0.5 * (node_res_scaled - mc_res_scaled), dtype=torch.float64, device=dev)
-            mask_on = bool(getattr(self.config, "mc_mask_on", True))
-            check_level = self._check_level()
-            per = max(1, QUERY_CHUNK // (k ** 3))
-            for h in range(0, len(nodes), per):
-                t = min(h + per, len(nodes))
-                # cur_coord += cur_origin (:329-330): a float32 tensor plus a float64 one, computed in double, stored as float32
-                coord = (block64[None] + origins[h:t, None, :]).float().reshape(-1, 3)
-                with torch.no_grad():
-                    s, m = query_points_device(self.octree, self.geo_decoder, coord, check_level, True, True, mask_on)
-                yield h, t, s.half().float(), m
-
-        return k, shape, shift, voxel, origin, chunks()
+    def _query_blocks(self, nodes, node_res_scaled, k, mc_res_scaled):
+        """The k^3 blocks of the nodes with centres `nodes [m,3]` (scaled), queried QUERY_CHUNK points at a time: yields (h, t, sdf,
+        mask) as _octree_blocks documents.  A block's values depend on its own node only: on no other row of `nodes`, and not on
+        the grid's origin."""
+        dev = self.octree.hier_features[0].device
+        # the reference's node block: int16 grid coordinates, float32, times mc_res_scaled (:304-313)
+        ax = torch.arange(k, dtype=torch.int16, device=dev)
+        gx, gy, gz = torch.meshgrid(ax, ax, ax, indexing="ij")
+        block = torch.stack((gx.flatten(), gy.flatten(), gz.flatten())).transpose(0, 1).float()
+        block *= mc_res_scaled
+        block64 = block.double()
+        origins = torch.as_tensor(nodes - 0.5 * (node_res_scaled - mc_res_scaled), dtype=torch.float64, device=dev)
+        mask_on = bool(getattr(self.config, "mc_mask_on", True))
+        check_level = self._check_level()
+        per = max(1, QUERY_CHUNK // (k ** 3))
+        for h in range(0, len(nodes), per):
+            t = min(h + per, len(nodes))
+            # cur_coord += cur_origin (:329-330): a float32 tensor plus a float64 one, computed in double, stored as float32
+            coord = (block64[None] + origins[h:t, None, :]).float().reshape(-1, 3)
+            with torch.no_grad():
+                s, m = query_points_device(self.octree, self.geo_decoder, coord, check_level, True, True, mask_on)
+            yield h, t, s.half().float(), m
 
     def octree_grid_device(self, query_level, mc_res_m):
         """recon_octree_mesh's dense grid, assembled on the device: every node block (_octree_blocks) scattered to its shift_coord
@@ -782,14 +882,107 @@ class Mesher:
         Returns (values [n,B,B,B] f32, mask [n,B,B,B] u8, origins [n,3] int64, shape, voxel size m, origin m)."""
         k, shape, shift, voxel, origin, chunks = self._octree_blocks(query_level, mc_res_m)
         dev = self.octree.hier_features[0].device
-        B, brick_origins = octree_brick_table(k, shift)
         values = torch.empty((len(shift), k, k, k), dtype=torch.float32, device=dev)
         mask = torch.zeros((len(shift), k, k, k), dtype=torch.uint8, device=dev)
         for h, t, s, m in chunks:
             values[h:t] = s.view(-1, k, k, k)
             if m is not None:
                 mask[h:t] = m.view(-1, k, k, k)
-        return split_blocks(values, B), split_blocks(mask, B), brick_origins, tuple(int(v) for v in shape), voxel, origin
+        return self._blocks_as_bricks(values, mask, shape, shift) + (voxel, origin)
+
+    @staticmethod
+    def _blocks_as_bricks(values, mask, shape, shift):
+        """node blocks [M, k, k, k] at grid offsets `shift` as marching_cubes_sparse's (values, mask, origins, shape)"""
+        B, brick_origins = octree_brick_table(values.shape[1], shift)
+        return split_blocks(values, B), split_blocks(mask, B), brick_origins, tuple(int(v) for v in shape)
+
+    def reset_mesh_cache(self):
+        """Drop update_octree_mesh's cache: its next call queries every block again (reason "first")."""
+        self._mesh_cache = None
+
+    def update_octree_mesh(self, query_level, mc_res_m, mesh_path=None, estimate_sem=False, estimate_normal=True,
+                           filter_isolated_mesh=True, filter_free_space_vertices=True):
+        """recon_octree_mesh(..., sparse=True) on the octree's current state — the same vertices, faces, order, normals, colours
+        and PLY bytes — from a block cache that persists between calls: only the node blocks whose values can have changed since the
+        previous call are queried again (changed feature rows -> dirty nodes -> dirty query-level nodes, all on
+        the device).  Marching cubes and the mesh's tail still run over everything.  mesh_path None writes no file; the mesh is
+        left in last_mesh_device either way, and last_update_stats says what was queried: nodes, new_nodes, dirty_nodes,
+        requeried_nodes, requeried_points, full, reason ("first" / "key" / "decoder" / "octree" when the cache was rebuilt from
+        nothing, else None), and changed_rows per level, the count shine_rows_diff leaves next to them.  The cache costs the size of the feature tables plus 5 bytes per grid point."""
+        if getattr(self.config, "time_conditioned", False):
+            raise NotImplementedError("time-conditioned decoding is outside the SDF hot path")
+        try:
+            return self._update_octree_mesh(query_level, mc_res_m, mesh_path, estimate_sem, estimate_normal, filter_isolated_mesh,
+                                            filter_free_space_vertices)
+        except BaseException:
+            self._mesh_cache = None  # (a call that stopped half-way leaves snapshots ahead of the blocks)
+            raise
+
+    def _update_octree_mesh(self, query_level, mc_res_m, *finish):
+        octree = self.octree
+        nodes, node_res_scaled, k, mc_res_scaled, shape, shift, voxel, origin = self._block_layout(query_level, mc_res_m)
+        dev = octree.hier_features[0].device
+        L, sq = octree.featured_level_num, query_level - octree.free_level_num
+        feats = [p.detach() for p in octree.feature_list()]
+        if not all(f.is_cuda and f.dtype == torch.float32 and f.is_contiguous() for f in feats):
+            raise ValueError("update_octree_mesh: the feature tables must be CUDA float32 contiguous")
+        rows = [int(f.shape[0]) - 1 for f in feats]  # without the trash row
+        # (octree_grid_layout's get_octree_nodes merged the device's growth into the host tables)
+        node_keys, node_ids = list(octree._node_keys), list(octree._node_ids)
+        counts = [len(a) for a in node_keys]
+        M = counts[sq]
+        key = mesh_cache_key(query_level, k, mc_res_scaled, bool(getattr(self.config, "mc_mask_on", True)), self._check_level(),
+                             self.world_scale)
+        decoder_bits = torch.cat([p.detach().reshape(-1) for p in self.geo_decoder.fused_params()]).view(torch.int32)
+        c = self._mesh_cache
+        reason = mesh_cache_rebuild_reason(c, key, lambda: torch.equal(c.decoder_bits, decoder_bits), node_keys, node_ids, rows)
+        if reason is not None:  # from nothing: an empty snapshot and no node seen make every row changed and every node new
+            c = self._mesh_cache = _MeshCache(key, decoder_bits, L)
+        prev = [len(a) for a in c.node_keys]
+
+        # the feature rows that changed since the previous call (and the snapshot brought up to date)
+        flags = [torch.empty(r, dtype=torch.uint8, device=dev) for r in rows]
+        counters = torch.zeros(L + 2, dtype=torch.int64, device=dev)  # changed rows per level, then mark_dirty's two counts
+        for s in range(L):
+            c.snaps[s] = _grow_rows(c.snaps[s], c.snap_rows[s], rows[s], (_lib.FEATURE_DIM,), torch.float32, dev)
+        rows_diff_device(feats, c.snaps, c.snap_rows, flags, counters[:L])
+        c.snap_rows = rows
+
+        # the node tables on the device (appended), the sorted keys of the slots the search runs in, the dirty query nodes
+        for s in range(L):
+            n0, n1 = c.dev_nodes[s], counts[s]
+            c.dev_keys[s] = _grow_rows(c.dev_keys[s], n0, n1, (), torch.int64, dev)
+            c.dev_ids[s] = _grow_rows(c.dev_ids[s], n0, n1, (8,), torch.int32, dev)
+            if n1 > n0:
+                c.dev_keys[s][n0:n1] = torch.from_numpy(node_keys[s][n0:n1]).to(dev)
+                c.dev_ids[s][n0:n1] = torch.from_numpy(np.ascontiguousarray(node_ids[s][n0:n1], np.int32)).to(dev)
+            c.dev_nodes[s] = n1
+            if s <= sq and (c.sorted[s] is None or c.sorted[s][0] != n1):
+                c.sorted[s] = (n1,) + tuple(torch.sort(c.dev_keys[s][:n1]))
+        dirty = torch.empty(M, dtype=torch.uint8, device=dev)
+        mark_dirty_device(sq, c.dev_keys, c.dev_ids, counts, prev, flags, [e[1] if e else None for e in c.sorted],
+                          [e[2] if e else None for e in c.sorted], dirty, counters[L:])
+        index = torch.nonzero(dirty).reshape(-1)
+        index_host = index.cpu().numpy()
+        counted = [int(v) for v in counters.tolist()]
+        changed_rows, old_dirty, all_dirty = counted[:L], counted[L], counted[L + 1]
+        if all_dirty != len(index_host) or all_dirty != (M - prev[sq]) + old_dirty or (reason is not None and all_dirty != M):
+            raise RuntimeError("update_octree_mesh: %d flagged blocks, %d counted (%d of them old), %d nodes, %d seen before "
+                               "(rebuilt: %s)" % (len(index_host), all_dirty, old_dirty, M, prev[sq], reason))
+
+        # the dirty and the new blocks, queried as _octree_blocks queries them, written into the cache
+        chunks = self._query_blocks(nodes[index_host], node_res_scaled, k, mc_res_scaled)
+        c.values = _grow_rows(c.values, prev[sq], M, (k, k, k), torch.float32, dev)
+        c.masks = _grow_rows(c.masks, prev[sq], M, (k, k, k), torch.uint8, dev)
+        for h, t, s, m in chunks:
+            blocks_scatter_device(s, m, index[h:t], c.values, c.masks)
+        c.node_keys, c.node_ids = node_keys, node_ids
+        self.last_update_stats = {
+            "nodes": M, "new_nodes": M - prev[sq], "dirty_nodes": old_dirty, "requeried_nodes": all_dirty,
+            "requeried_points": all_dirty * k ** 3, "full": reason is not None, "reason": reason, "changed_rows": changed_rows,
+        }
+        verts, faces = marching_cubes_sparse(*self._blocks_as_bricks(c.values[:M], c.masks[:M], shape, shift), 0.0)
+        return self._finish(verts, faces, voxel, origin, *finish, 300)
 
     def recon_octree_mesh(self, query_level, mc_res_m, mesh_path, map_path, save_map=False, estimate_sem=False,
                           estimate_normal=True, filter_isolated_mesh=True, filter_free_space_vertices=True, sparse=None):
