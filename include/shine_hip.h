@@ -20,6 +20,20 @@
  *    "trash bin" that index -1 addresses (model/feature_octree.py:76-81,205);
  *  - F (feature_dim) = 8 and H (hidden) = 32, 2 hidden layers: the only decoder shape any
  *    shipped config uses (config/ all yamls: feature_dim 8, mlp_hidden_dim 32, mlp_level 2).
+ *
+ * The workspace convention (rocPRIM's), for every entry point that takes `void* workspace, size_t* workspace_bytes`:
+ *  - workspace == NULL is the size query: *workspace_bytes = the device bytes this call needs for exactly these arguments,
+ *    and SHINE_OK.  Pass the arguments of the real call: the query checks their sizes, reads no device memory, writes no
+ *    output and launches nothing; a NULL workspace_bytes is SHINE_E_INVALID;
+ *  - otherwise *workspace_bytes is the size of `workspace`; one that is short is refused with SHINE_E_INVALID and the
+ *    message "<entry point>: workspace too small", before anything is launched or any output is written;
+ *  - the contents need no initialisation and mean nothing afterwards, unless the entry point says otherwise; arrays inside
+ *    start at 256-byte boundaries, so `workspace` itself should be 256-byte aligned (any hipMalloc / torch allocation is);
+ *  - an entry point that takes `size_t workspace_bytes` BY VALUE cannot be queried: it re-uses the workspace of the call its
+ *    comment names (or is sized by a function of its own) and refuses a missing or short one the same way, unless its
+ *    comment says otherwise; a second buffer sized by the same kind of query (a scratch, a result grid) is refused in words
+ *    that name it.
+ * Below, "workspace: see the convention" refers to this block.
  */
 #ifndef SHINE_HIP_H_
 #define SHINE_HIP_H_
@@ -391,7 +405,7 @@ int shine_mark_touched(const shine_tables* t, const shine_step_config* cfg, cons
 
 /* ---- Morton ordering of a batch: the new step right after LiDARDataset.get_batch
  *      (dataset/lidar_dataset.py:430-450).  perm_out[N] int32 = argsort of the leaf-level node keys, to be
- *      passed as `perm` to shine_train_step.  Call with workspace == NULL to get the required bytes. --- */
+ *      passed as `perm` to shine_train_step.  workspace: see the convention. --- */
 int shine_morton_sort(const shine_step_config* cfg, const float* coord, int64_t n, int32_t* perm_out,
                       void* workspace, size_t* workspace_bytes, void* stream);
 
@@ -434,7 +448,7 @@ int shine_append_rows(int32_t n_levels, const float* const* old_feat, const floa
  *      down_rate], :27-31) for a node-ordered pool: perm[j] = ORIGINAL pool index of the sample at sorted position j.  Writes
  *      idx_out (device int32, >= number of kept samples, <= n): the sorted positions of the chunks' members, chunk after chunk,
  *      ascending inside a chunk, and chunk_begin (HOST int64[n_chunks + 1], n_chunks = ceil(n / (bs * down_rate))): what
- *      shine_importance_sweep takes.  workspace == NULL: *workspace_bytes = the size needed. */
+ *      shine_importance_sweep takes.  workspace: see the convention. */
 int shine_importance_chunks(const int32_t* perm, int64_t n, int64_t bs, int32_t down_rate, int32_t* idx_out,
                             int64_t* chunk_begin, int32_t n_chunks, void* workspace, size_t* workspace_bytes, void* stream);
 int shine_importance_sweep_sizes(int32_t n_levels, const int64_t* rows, int32_t n_chunks, int64_t max_chunk,
@@ -465,8 +479,8 @@ int shine_adam_step(int32_t n_tensors, float* const* params, float* const* grads
  *      after the tree grew, the leaf level (slot L-1) last.  keys/ranks: device arrays of n entries.
  *      shine_plan_batch: perm_out [N] int32 (visiting order) and slots_out [N,L] int32 (in visiting order) to pass
  *      to shine_train_step.  zero_ptr/zero_bytes (16-B aligned, may be NULL/0): a buffer cleared in the same pass —
- *      the flat gradient bucket, i.e. opt.zero_grad() for the fused step.  workspace == NULL returns the required
- *      bytes.  Replaces shine_morton_sort on the training path: ~3 small launches, and the fused kernel no longer
+ *      the flat gradient bucket, i.e. opt.zero_grad() for the fused step.  workspace: see the
+ *      convention.  Replaces shine_morton_sort on the training path: ~3 small launches, and the fused kernel no longer
  *      hashes or probes.  Batches of <= 16384 points (the reference's batch size is 4096) are NOT reordered — perm_out is the
  *      identity, one launch: the fused step does not see the order at that size — unless cfg->kernel_variant has bit 0x800 set
  *      (a sample POOL that is planned once and drawn from many times wants the node order at any size). -------------------- */
@@ -486,8 +500,8 @@ int shine_plan_batch(const shine_tables* t, const shine_step_config* cfg, const 
  *      device int64[SHINE_SURF_PARTS]; the launches that write the indices also count the draws (of the slice, for
  *      shine_sample_sorted_slice) whose bit is set — the surface
  *      samples the eikonal term averages over (shine_batch.py:183-185) — as 64 partial counts (overwritten): hand them to
- *      shine_train_step as n_surf with cfg->n_surf_parts = SHINE_SURF_PARTS.  workspace == NULL returns the required
- *      bytes. --------------------------------------------------------------------------------------------------------- */
+ *      shine_train_step as n_surf with cfg->n_surf_parts = SHINE_SURF_PARTS.  workspace: see the convention.
+ *      ---------------------------------------------------------------------------------------------------------------- */
 int shine_sample_sorted(int64_t pool_size, int64_t n, uint64_t seed, uint64_t stream_id, int32_t* idx_out,
                         void* zero_ptr, size_t zero_bytes, const uint32_t* surf_bits, int64_t* surf_parts, void* workspace,
                         size_t* workspace_bytes, void* stream);
@@ -513,7 +527,7 @@ int shine_sample_sorted_finish(int64_t pool_size, int64_t n, int64_t slice_begin
  *      flags[l]: uint8 [rows[l]] from shine_mark_touched (OR-reduced over the ranks), rows[l] = the level's row count
  *      WITHOUT the trash row (= the trash row's index).
  *      shine_touched_index: ascending ids of the flagged rows per level -> idx_out[l] (capacity rows[l]) and
- *        counts_dev[l] (device int64); workspace == NULL returns the required bytes.
+ *        counts_dev[l] (device int64).  workspace: see the convention.
  *      shine_touched_pack: msg = [the listed rows of level 0, level 1, ... (8 floats each)][the L trash rows]; counts =
  *        the HOST copy of counts_dev (the message size is needed on the host for the collective anyway).
  *      shine_touched_unpack: the reverse; clears flags[l] at the listed rows when flags is given. */
@@ -534,7 +548,7 @@ int shine_touched_unpack(int32_t n_levels, float* const* grads, const int32_t* c
  *        the host array of the <= 8 trash-row ids, whose flags stay set: every miss lands there), and so does the tail.  A
  *        second micro-batch of the same step can therefore accumulate into the same bucket and be packed separately.  More
  *        than cap flagged rows: msg[1] = 1 and the excess rows stay behind (the result is then incomplete — size cap from
- *        a measured step, and check overflow_out).  workspace == NULL returns the required bytes.
+ *        a measured step, and check overflow_out).  workspace: see the convention.
  *      shine_rows_unpack_add: msgs = world messages back to back (the all-gather's output, this rank's included): every row
  *        is added into the bucket, one launch per rank in rank order (bit-identical results on every rank), the tails are
  *        summed in rank order and — tail_add == 0 — stored (the first exchange of a step: shine_rows_pack left zeros there) or
@@ -561,7 +575,7 @@ int shine_query_points(const shine_tables* t, const shine_step_config* cfg, cons
  *      filter_isolated_vertices (:240-251) on the device (csrc/shine_mc.hip, csrc/shine_mesh.hip; rules in DESIGN.md "Meshing").
  *      sdf [nx, ny, nz] f32 C order (z fastest); mask [nx, ny, nz] u8 or NULL: cube (x, y, z) is processed iff mask[x, y, z]
  *      (its lowest corner) is set.  A value is "in" iff > level.  Sizes and ids are int64 on the grid, int32 in the mesh.
- *      Workspaces follow rocPRIM's convention: workspace == NULL returns the bytes needed in *workspace_bytes.
+ *      workspace: see the convention.
  *      _mc_count: classify + scan; counts_out (HOST int64[2]) = {V, F}; one small device-to-host copy, so it synchronises the
  *        stream.  SHINE_E_INVALID if V or F >= 2^31 (counts_out still holds them).
  *      _mc_emit: the same grid, level and workspace right after _mc_count: verts_out [V, 3] f32 index units, (x, y, z);
@@ -587,7 +601,7 @@ int shine_mesh_cluster_filter(const int32_t* faces, int64_t n_faces, int32_t min
  *      brick covers is processed); origins (HOST int64 [n, 3]) = each brick's lowest point: multiples of brick, inside the
  *      grid, no two equal.  brick is 1..32; nx * ny * nz must be < 2^60 (it is an index space only); n < 2^31.  Bricks may
  *      reach beyond the grid: what lies outside is ignored.  Everything above is checked on the host before a device is touched.
- *      _mc_sparse_count: workspace == NULL returns the bytes needed (proportional to n * (brick + 1)^3) in *workspace_bytes.
+ *      _mc_sparse_count: workspace: see the convention (proportional to n * (brick + 1)^3).
  *        Otherwise: brick table, classify, scan; counts_out (HOST int64[2]) = {R, F}: R vertex RECORDS (a vertex on a brick face
  *        counts once per brick that uses it: V <= R) and F faces.  Synchronises the stream.  SHINE_E_INVALID if R or F >= 2^31.
  *      _mc_sparse_emit: the same bricks, grid, level and workspace right after _mc_sparse_count, with its R and F.  scratch ==
@@ -630,7 +644,7 @@ int shine_blocks_scatter(const float* sdf, const uint8_t* mask, const int64_t* i
 
 /* ---- mesh evaluation: eval/eval_utils.py (eval_mesh, nn_correspondance, crop_intersection) on the device
  *      (csrc/shine_eval.hip; layout and rules in DESIGN.md 3.10).  All geometry is fp64; counts are int64 and < 2^31.
- *      Workspaces follow rocPRIM's convention: workspace == NULL returns the bytes needed in *workspace_bytes.
+ *      workspace: see the convention.
  *      _fine_per_coarse: fine cells per coarse cell edge of the search grid (a compile-time constant of the library).
  *      _bounds: bounds_out (DEVICE double[6]) = per-axis minimum then maximum of points [n, 3], n > 0.
  *      _box_mask: drop_out [n] u8 = 0 where min_bound <= p <= max_bound on every axis (HOST double[3] each), else 1.
@@ -678,8 +692,7 @@ int shine_eval_metrics(const double* dist_p, int64_t n_p, const double* dist_r, 
                        size_t* workspace_bytes, double* sums_out, void* stream);
 
 /* ---- the frame front-end (csrc/shine_frame.hip): LiDARDataset.process_frame (dataset/lidar_dataset.py:115-290) and
- *      dataSampler.sample (utils/data_sampler.py:18-139) on the device.  Sizes are < 2^31 rows; workspace == NULL returns the
- *      bytes needed in *workspace_bytes.
+ *      dataSampler.sample (utils/data_sampler.py:18-139) on the device.  Sizes are < 2^31 rows; workspace: see the convention.
  *      _frame_filter: preprocess_kitti + the crop box in ONE launch: keeps, in input order, the points with z > min_z,
  *        |p| >= min_range, -pc_radius <= x, y <= pc_radius and min_z <= z <= max_z (all inclusive but the first; fp64, no
  *        fused multiply-add, so the kept set equals numpy's).  points: n rows of `stride` (3 or 4) float32 elements, or fp64
@@ -745,7 +758,7 @@ int shine_pool_window_filter(const float* coord, int64_t n, const float* origin,
  *      (open3d remove_statistical_outlier) and estimate_normal (open3d estimate_normals with KDTreeSearchParamHybrid).  fp64.
  *      The cloud is searched through the grid shine_eval_grid_count / shine_eval_grid_emit built over it: grid, n (= the cloud's
  *      point count), n_fine, n_coarse, origin (HOST double[3]), cell and cells_per_axis (HOST int64[3]) are shine_eval_nn_search's.
- *      Results are in the caller's point order.  workspace == NULL returns the bytes needed in *workspace_bytes.  Squared
+ *      Results are in the caller's point order.  workspace: see the convention.  Squared
  *      distances are (dx*dx + dy*dy) + dz*dz of the fp64 differences, no fused multiply-add.
  *      _knn_search: for every point its k (1..32) nearest points of the cloud, itself included at distance 0, limited to squared
  *        distance <= radius * radius if radius >= 0 (radius < 0: unbounded).  Ascending squared distance, equal distances by

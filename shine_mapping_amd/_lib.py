@@ -245,7 +245,11 @@ _SIGNATURES = {
     "shine_iter_graph_commit": (C.c_int, [_P]),
     "shine_iter_graph_launch": (C.c_int, [_P, C.c_int32, _P]),
     "shine_iter_graph_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "shine_iter_graph_operand_image_floats": (C.c_int, []),
+    "shine_iter_graph_set_operand_image": (C.c_int, [_P, _P]),
 }
+_SIGNATURES["shine_iter_graph_set_step"] = (C.c_int, [_P] + _SIGNATURES["shine_train_step"][1][:-1])
+_SIGNATURES["shine_iter_graph_set_finish"] = (C.c_int, [_P] + _SIGNATURES["shine_finish_iteration"][1][:-1])
 
 _lib = None
 _check = None
@@ -260,47 +264,35 @@ def exported_symbols():
     return sorted(_SIGNATURES)
 
 
-def lib():
-    """Load (once) and return the ctypes handle; raises if the HIP library is not built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.isfile(LIB_PATH):
-        raise ShineHipError(
-            "libshine_hip.so not found at %s — build it with `python -m shine_mapping_amd.build` "
-            "(there is no fallback path)" % LIB_PATH
-        )
-    h = C.CDLL(LIB_PATH)
+def _load(path, missing):
+    """Load the library at `path` and bind every signature of the table; `missing`: what to say if the file is not there."""
+    if not os.path.isfile(path):
+        raise ShineHipError(missing % path)
+    h = C.CDLL(path)
     for name, (res, args) in _SIGNATURES.items():
         fn = getattr(h, name)  # AttributeError if the symbol is missing: loud by design
         fn.restype = res
         fn.argtypes = args
-    _lib = h
     return h
 
 
-_SIGNATURES["shine_iter_graph_operand_image_floats"] = (C.c_int, [])
-_SIGNATURES["shine_iter_graph_set_operand_image"] = (C.c_int, [_P, _P])
-_SIGNATURES["shine_iter_graph_set_step"] = (C.c_int, [_P] + _SIGNATURES["shine_train_step"][1][:-1])
-_SIGNATURES["shine_iter_graph_set_finish"] = (C.c_int, [_P] + _SIGNATURES["shine_finish_iteration"][1][:-1])
+def lib():
+    """Load (once) and return the ctypes handle; raises if the HIP library is not built."""
+    global _lib
+    if _lib is None:
+        _lib = _load(LIB_PATH, "libshine_hip.so not found at %s — build it with `python -m shine_mapping_amd.build` "
+                               "(there is no fallback path)")
+    return _lib
 
 
 def check_lib():
     """The CHECK library (tests / tools only): same ABI, plus the kernel behind StepOptions.kernel_variant 1.  Table
     handles are plain process memory with one layout in both libraries, so a handle made by one works in the other."""
     global _check
-    if _check is not None:
-        return _check
-    if not os.path.isfile(CHECK_LIB_PATH):
-        raise ShineHipError("libshine_check.so not found at %s — `python -m shine_mapping_amd.build` builds it next to the "
-                            "product library" % CHECK_LIB_PATH)
-    h = C.CDLL(CHECK_LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
-        fn = getattr(h, name)
-        fn.restype = res
-        fn.argtypes = args
-    _check = h
-    return h
+    if _check is None:
+        _check = _load(CHECK_LIB_PATH, "libshine_check.so not found at %s — `python -m shine_mapping_amd.build` builds it next "
+                                       "to the product library")
+    return _check
 
 
 def check(code: int, what: str = "", library=None):
@@ -309,6 +301,43 @@ def check(code: int, what: str = "", library=None):
     if code != 0:
         msg = (library if library is not None else lib()).shine_error_string(code)
         raise ShineHipError("%s failed (%d): %s" % (what or "libshine_hip call", code, (msg or b"").decode()))
+
+
+# The workspace convention of include/shine_hip.h from Python.  WS and WS_BYTES stand in an argument list where the entry point
+# takes `void* workspace` and `size_t* workspace_bytes`.
+WS, WS_BYTES = object(), object()
+
+
+def workspace(nbytes, device):
+    """an uninitialised device buffer of `nbytes` bytes (at least one: an empty tensor has no address)"""
+    import torch
+
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
+def _call_ws(fn, args, ws_ptr, need, what=None):
+    rc = fn(*[ws_ptr if a is WS else C.byref(need) if a is WS_BYTES else a for a in args])
+    if rc != 0:
+        check(rc, what() if callable(what) else what or fn.__name__)
+
+
+def workspace_bytes(fn, *args):
+    """the size query alone: the bytes `fn` answers for `args` (WS / WS_BYTES mark the two workspace arguments)"""
+    need = C.c_size_t(0)
+    _call_ws(fn, args, None, need)
+    return need.value
+
+
+def call_with_workspace(fn, device, *args, what=None):
+    """Query, allocate, call: `fn(*args)` with a fresh workspace on `device` where `args` holds WS, its size where it holds WS_BYTES;
+    the query passes the same arguments with workspace = NULL.  `what` names the call in an error (default: the entry
+    point), as a string or as a callable asked after the failed call, which can then quote what the call left in its outputs.
+    -> (the workspace tensor, its c_size_t size), for a caller whose next call reads the workspace again."""
+    need = C.c_size_t(0)
+    _call_ws(fn, args, None, need, what)
+    ws = workspace(need.value, device)
+    _call_ws(fn, args, ws.data_ptr(), need, what)
+    return ws, need
 
 
 def ptr_array(ptrs):

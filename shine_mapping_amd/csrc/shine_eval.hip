@@ -472,21 +472,21 @@ struct GridScratch {
 };
 
 int grid_scratch(void* ws, long long n, hipStream_t st, GridScratch* s) {
-  Carve c{(char*)ws};
-  s->k0 = (unsigned long long*)c.take((size_t)n * 8);
-  s->k1 = (unsigned long long*)c.take((size_t)n * 8);
-  s->v0 = (unsigned long long*)c.take((size_t)n * 8);
-  s->v1 = (unsigned long long*)c.take((size_t)n * 8);
-  s->fflag = (unsigned char*)c.take((size_t)n);
-  s->cflag = (unsigned char*)c.take((size_t)n);
-  s->frank = (int*)c.take((size_t)n * 4);
-  s->crank = (int*)c.take((size_t)n * 4);
+  shine::Arena c(ws);
+  s->k0 = c.take<unsigned long long>((size_t)n);
+  s->k1 = c.take<unsigned long long>((size_t)n);
+  s->v0 = c.take<unsigned long long>((size_t)n);
+  s->v1 = c.take<unsigned long long>((size_t)n);
+  s->fflag = c.take<unsigned char>((size_t)n);
+  s->cflag = c.take<unsigned char>((size_t)n);
+  s->frank = c.take<int>((size_t)n);
+  s->crank = c.take<int>((size_t)n);
   size_t sort_bytes = 0, scan_bytes = 0;
   SHINE_HIP_CHECK(shine::prim_sort_pairs_u64(nullptr, sort_bytes, nullptr, nullptr, nullptr, nullptr, (size_t)n, 0u, 64u, st));
   SHINE_HIP_CHECK(shine::prim_scan_flags(nullptr, scan_bytes, nullptr, nullptr, (size_t)n, st));
   s->tmp_bytes = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-  s->tmp = c.take(s->tmp_bytes);
-  s->bytes = c.off;
+  s->tmp = c.take_bytes(s->tmp_bytes);
+  s->bytes = c.bytes();
   return SHINE_OK;
 }
 
@@ -526,18 +526,15 @@ extern "C" int shine_eval_fine_per_coarse(void) { return FINE_PER_COARSE; }
 extern "C" int shine_eval_bounds(const double* points, int64_t n, void* workspace, size_t* workspace_bytes, double* bounds_out,
                                  void* stream) {
   if (!workspace_bytes || bad_count(n)) return shine::set_error(SHINE_E_INVALID, "shine_eval_bounds: bad size (n must be < 2^31)");
-  const size_t need = align256((size_t)RED_BLOCKS * 6 * 8);
-  if (!workspace) {
-    *workspace_bytes = need;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < need) return shine::set_error(SHINE_E_INVALID, "shine_eval_bounds: workspace too small");
+  shine::Arena c(workspace);
+  double* part = c.take<double>((size_t)RED_BLOCKS * 6);
+  SHINE_WORKSPACE_GATE(c.bytes(), workspace, workspace_bytes, "shine_eval_bounds");
   if (n == 0 || !points || !bounds_out) return shine::set_error(SHINE_E_INVALID, "shine_eval_bounds: empty cloud or null argument");
   hipStream_t st = (hipStream_t)stream;
   const int blocks = (int)(grid_of(n) < (unsigned)RED_BLOCKS ? grid_of(n) : (unsigned)RED_BLOCKS);
-  hipLaunchKernelGGL(k_bounds_partial, dim3(blocks), dim3(T), 0, st, points, (long long)n, (double*)workspace);
+  hipLaunchKernelGGL(k_bounds_partial, dim3(blocks), dim3(T), 0, st, points, (long long)n, part);
   SHINE_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_bounds_final, dim3(1), dim3(64), 0, st, (const double*)workspace, blocks, bounds_out);
+  hipLaunchKernelGGL(k_bounds_final, dim3(1), dim3(64), 0, st, (const double*)part, blocks, bounds_out);
   SHINE_HIP_CHECK(hipGetLastError());
   return SHINE_OK;
 }
@@ -560,14 +557,10 @@ extern "C" int shine_eval_sample_mesh(const double* verts, int64_t n_verts, cons
     return shine::set_error(SHINE_E_INVALID, "shine_eval_sample_mesh: bad sizes (V, F and n must be < 2^31)");
   const long long nf = n_faces;
   const int blocks = (int)((nf + 4 * T - 1) / (4 * T));
-  Carve c{(char*)workspace};
-  auto* cum = (double*)c.take((size_t)nf * 8);
-  auto* tot = (double*)c.take((size_t)(blocks > 0 ? blocks : 1) * 8);
-  if (!workspace) {
-    *workspace_bytes = c.off;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < c.off) return shine::set_error(SHINE_E_INVALID, "shine_eval_sample_mesh: workspace too small");
+  shine::Arena c(workspace);
+  double* cum = c.take<double>((size_t)nf);
+  double* tot = c.take<double>((size_t)(blocks > 0 ? blocks : 1));
+  SHINE_WORKSPACE_GATE(c.bytes(), workspace, workspace_bytes, "shine_eval_sample_mesh");
   if (n == 0) return SHINE_OK;
   if (nf == 0) return shine::set_error(SHINE_E_INVALID, "shine_eval_sample_mesh: a mesh without triangles cannot be sampled");
   if (!verts || !faces || !points_out) return shine::set_error(SHINE_E_INVALID, "shine_eval_sample_mesh: null argument");
@@ -593,11 +586,7 @@ extern "C" int shine_eval_voxel_down(const double* points, int64_t n, const doub
   hipStream_t st = (hipStream_t)stream;
   GridScratch s;
   if (int rc = grid_scratch(workspace, n, st, &s)) return rc;
-  if (!workspace) {
-    *workspace_bytes = s.bytes;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < s.bytes) return shine::set_error(SHINE_E_INVALID, "shine_eval_voxel_down: workspace too small");
+  SHINE_WORKSPACE_GATE(s.bytes, workspace, workspace_bytes, "shine_eval_voxel_down");
   if (!n_out || !origin || !(voxel > 0.0)) return shine::set_error(SHINE_E_INVALID, "shine_eval_voxel_down: null argument or voxel <= 0");
   *n_out = 0;
   if (n == 0) return SHINE_OK;
@@ -623,11 +612,7 @@ extern "C" int shine_voxel_down_attr(const double* points, const double* attrs, 
   hipStream_t st = (hipStream_t)stream;
   GridScratch s;
   if (int rc = grid_scratch(workspace, n, st, &s)) return rc;
-  if (!workspace) {
-    *workspace_bytes = s.bytes;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < s.bytes) return shine::set_error(SHINE_E_INVALID, "shine_voxel_down_attr: workspace too small");
+  SHINE_WORKSPACE_GATE(s.bytes, workspace, workspace_bytes, "shine_voxel_down_attr");
   *n_out = 0;
   if (n == 0) return SHINE_OK;
   const long long nn = n;
@@ -644,11 +629,7 @@ extern "C" int shine_eval_grid_count(const double* ref, int64_t n, const double*
   hipStream_t st = (hipStream_t)stream;
   GridScratch s;
   if (int rc = grid_scratch(workspace, n, st, &s)) return rc;
-  if (!workspace) {
-    *workspace_bytes = s.bytes;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < s.bytes) return shine::set_error(SHINE_E_INVALID, "shine_eval_grid_count: workspace too small");
+  SHINE_WORKSPACE_GATE(s.bytes, workspace, workspace_bytes, "shine_eval_grid_count");
   if (!ref || !origin || !counts_out || !(cell > 0.0)) return shine::set_error(SHINE_E_INVALID, "shine_eval_grid_count: null argument or cell <= 0");
   const Vec3 o{origin[0], origin[1], origin[2]};
   const long long nn = n;
@@ -670,7 +651,7 @@ extern "C" int shine_eval_grid_emit(const double* ref, int64_t n, const void* wo
   if (!grid_bytes || bad_count(n) || n == 0 || n_fine < 1 || n_fine > n || n_coarse < 1 || n_coarse > n_fine)
     return shine::set_error(SHINE_E_INVALID, "shine_eval_grid_emit: bad sizes");
   const GridLayout L = grid_layout(grid, n, n_fine, n_coarse);
-  if (!grid) {
+  if (!grid) {  // (by hand, not SHINE_WORKSPACE_GATE: the grid is a result the caller keeps, and its message says so)
     *grid_bytes = L.bytes;
     return SHINE_OK;
   }
@@ -678,8 +659,8 @@ extern "C" int shine_eval_grid_emit(const double* ref, int64_t n, const void* wo
   hipStream_t st = (hipStream_t)stream;
   GridScratch s;
   if (int rc = grid_scratch(const_cast<void*>(workspace), n, st, &s)) return rc;
-  if (!workspace || workspace_bytes < s.bytes || !ref)
-    return shine::set_error(SHINE_E_INVALID, "shine_eval_grid_emit: needs the workspace of shine_eval_grid_count");
+  SHINE_WORKSPACE_FITS(s.bytes, workspace, workspace_bytes, "shine_eval_grid_emit");  // (the one shine_eval_grid_count filled)
+  if (!ref) return shine::set_error(SHINE_E_INVALID, "shine_eval_grid_emit: null ref");
   const long long nn = n;
   SHINE_HIP_CHECK(hipMemsetAsync(L.table, 0xff, (size_t)L.cap * sizeof(Cell), st));
   LAUNCH(k_grid_emit, nn, ref, (const unsigned long long*)s.k1, (const unsigned long long*)s.v1, (const unsigned char*)s.fflag,
@@ -698,19 +679,15 @@ extern "C" int shine_eval_nn_search(const void* grid, int64_t n_ref, int64_t n_f
     return shine::set_error(SHINE_E_INVALID, "shine_eval_nn_search: bad sizes");
   hipStream_t st = (hipStream_t)stream;
   const long long nq = n_query;
-  Carve c{(char*)workspace};
-  auto* k0 = (unsigned long long*)c.take((size_t)nq * 8);
-  auto* k1 = (unsigned long long*)c.take((size_t)nq * 8);
-  auto* v0 = (unsigned long long*)c.take((size_t)nq * 8);
-  auto* v1 = (unsigned long long*)c.take((size_t)nq * 8);
+  shine::Arena c(workspace);
+  auto* k0 = c.take<unsigned long long>((size_t)nq);
+  auto* k1 = c.take<unsigned long long>((size_t)nq);
+  auto* v0 = c.take<unsigned long long>((size_t)nq);
+  auto* v1 = c.take<unsigned long long>((size_t)nq);
   size_t sort_bytes = 0;
   SHINE_HIP_CHECK(shine::prim_sort_pairs_u64(nullptr, sort_bytes, nullptr, nullptr, nullptr, nullptr, (size_t)nq, 0u, 64u, st));
-  void* tmp = c.take(sort_bytes);
-  if (!workspace) {
-    *workspace_bytes = c.off;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < c.off) return shine::set_error(SHINE_E_INVALID, "shine_eval_nn_search: workspace too small");
+  void* tmp = c.take_bytes(sort_bytes);
+  SHINE_WORKSPACE_GATE(c.bytes(), workspace, workspace_bytes, "shine_eval_nn_search");
   if (nq == 0) return SHINE_OK;
   if (!grid || !origin || !cells_per_axis || !query || !index_out || !dist_out || !keep_out || !(cell > 0.0) || !(truncation >= 0.0))
     return shine::set_error(SHINE_E_INVALID, "shine_eval_nn_search: null argument, cell <= 0 or truncation < 0");
@@ -727,14 +704,10 @@ extern "C" int shine_eval_nn_search(const void* grid, int64_t n_ref, int64_t n_f
 extern "C" int shine_eval_metrics(const double* dist_p, int64_t n_p, const double* dist_r, int64_t n_r, double threshold,
                                   void* workspace, size_t* workspace_bytes, double* sums_out, void* stream) {
   if (!workspace_bytes || bad_count(n_p) || bad_count(n_r)) return shine::set_error(SHINE_E_INVALID, "shine_eval_metrics: bad sizes");
-  Carve c{(char*)workspace};
-  auto* part = (double*)c.take((size_t)RED_BLOCKS * 6 * 8);
-  auto* done = (unsigned int*)c.take(4);
-  if (!workspace) {
-    *workspace_bytes = c.off;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < c.off) return shine::set_error(SHINE_E_INVALID, "shine_eval_metrics: workspace too small");
+  shine::Arena c(workspace);
+  double* part = c.take<double>((size_t)RED_BLOCKS * 6);
+  unsigned int* done = c.take<unsigned int>(1);
+  SHINE_WORKSPACE_GATE(c.bytes(), workspace, workspace_bytes, "shine_eval_metrics");
   if (!sums_out || (n_p && !dist_p) || (n_r && !dist_r)) return shine::set_error(SHINE_E_INVALID, "shine_eval_metrics: null argument");
   hipStream_t st = (hipStream_t)stream;
   const long long big = n_p > n_r ? n_p : n_r;

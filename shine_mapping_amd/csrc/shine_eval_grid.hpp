@@ -16,18 +16,7 @@ constexpr long long AXIS_MAX = (1ll << AXIS_BITS) - 1;
 constexpr double MARGIN = 1.0 / (1 << 20);       // cell units: slack of every box bound (cell assignment rounds at ~2^-32)
 constexpr unsigned long long EMPTY = ~0ull;
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline bool bad_count(int64_t n) { return n < 0 || n >= (1ll << 31); }
-
-struct Carve {
-  char* base;
-  size_t off = 0;
-  void* take(size_t b) {
-    char* p = base ? base + off : nullptr;
-    off += align256(b);
-    return p;
-  }
-};
 
 struct Vec3 {
   double x, y, z;
@@ -99,17 +88,17 @@ struct GridLayout {
 };
 
 inline GridLayout grid_layout(void* buf, long long n, long long n_fine, long long n_coarse) {
-  Carve c{(char*)buf};
+  Arena c(buf);
   GridLayout L;
-  L.pts = (double*)c.take((size_t)n * 24);
-  L.sidx = (int*)c.take((size_t)n * 4);
-  L.fine = (Cell*)c.take((size_t)n_fine * sizeof(Cell));
-  L.coarse = (Cell*)c.take((size_t)n_coarse * sizeof(Cell));
+  L.pts = c.take<double>((size_t)n * 3);
+  L.sidx = c.take<int>((size_t)n);
+  L.fine = c.take<Cell>((size_t)n_fine);
+  L.coarse = c.take<Cell>((size_t)n_coarse);
   long long cap = 16;
   while (cap < 2 * n_coarse) cap <<= 1;
   L.cap = cap;
-  L.table = (Cell*)c.take((size_t)cap * sizeof(Cell));
-  L.bytes = c.off;
+  L.table = c.take<Cell>((size_t)cap);
+  L.bytes = c.bytes();
   return L;
 }
 

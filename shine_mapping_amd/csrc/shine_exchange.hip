@@ -57,8 +57,6 @@ __global__ void k_touched_move(ExchangeArgs a, float* msg) {
   else *g = msg[t];
 }
 
-static size_t xalign(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace shine
 
 using namespace shine;
@@ -73,15 +71,11 @@ extern "C" int shine_touched_index(int32_t n_levels, const uint8_t* const* flags
   for (int l = 0; l < n_levels; ++l) max_rows = rows[l] > max_rows ? rows[l] : max_rows;
   size_t scan_bytes = 0;
   SHINE_HIP_CHECK(prim_scan_flags(nullptr, scan_bytes, nullptr, nullptr, (size_t)(max_rows > 0 ? max_rows : 1), st));
-  const size_t need = xalign(scan_bytes) + xalign((size_t)max_rows * sizeof(int));
-  if (!workspace) {
-    *workspace_bytes = need;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < need) return set_error(SHINE_E_INVALID, "shine_touched_index: workspace too small");
+  Arena ws(workspace);
+  void* tmp = ws.take_bytes(scan_bytes);
+  int* pos = ws.take<int>((size_t)max_rows);
+  SHINE_WORKSPACE_GATE(ws.bytes(), workspace, workspace_bytes, "shine_touched_index");
   if (!flags || !idx_out || !counts_dev) return set_error(SHINE_E_INVALID, "shine_touched_index: null argument");
-  char* tmp = (char*)workspace;
-  int* pos = (int*)(tmp + xalign(scan_bytes));
   for (int l = 0; l < n_levels; ++l) {
     const long long n = rows[l];
     if (n <= 0) {
@@ -229,17 +223,13 @@ extern "C" int shine_rows_pack(uint8_t* flags, int64_t n_rows, const int64_t* ke
   hipStream_t st = (hipStream_t)stream;
   size_t scan_bytes = 0;
   SHINE_HIP_CHECK(prim_scan_flags(nullptr, scan_bytes, nullptr, nullptr, (size_t)n_rows, st));
-  const size_t need = xalign(scan_bytes) + xalign((size_t)n_rows * sizeof(int));
-  if (!workspace) {
-    *workspace_bytes = need;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < need) return set_error(SHINE_E_INVALID, "shine_rows_pack: workspace too small");
+  Arena ws(workspace);
+  void* tmp = ws.take_bytes(scan_bytes);
+  int* pos = ws.take<int>((size_t)n_rows);
+  SHINE_WORKSPACE_GATE(ws.bytes(), workspace, workspace_bytes, "shine_rows_pack");
   if (!flags || !bucket || !msg) return set_error(SHINE_E_INVALID, "shine_rows_pack: null argument");
   if (((size_t)bucket | (size_t)msg) & 15) return set_error(SHINE_E_INVALID, "shine_rows_pack: bucket and msg must be 16-byte aligned");
   if (cap & 3) return set_error(SHINE_E_INVALID, "shine_rows_pack: cap must be a multiple of 4 (16-byte aligned value rows)");
-  char* tmp = (char*)workspace;
-  int* pos = (int*)(tmp + xalign(scan_bytes));
   size_t sb = scan_bytes;
   SHINE_HIP_CHECK(prim_scan_flags(tmp, sb, (const unsigned char*)flags, pos, (size_t)n_rows, st));
   hipLaunchKernelGGL(k_rows_pack, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, (unsigned char*)flags,

@@ -480,16 +480,6 @@ __global__ __launch_bounds__(T) void k_window_compact(const unsigned char* __res
   if (tile == n_tiles - 1 && threadIdx.x == 0) *total = excl + count;
 }
 
-struct Carve {
-  char* base;
-  size_t off = 0;
-  void* take(size_t bytes) {
-    void* p = base ? base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return p;
-  }
-};
-
 constexpr long long MAX_ROWS = (1ll << 31) - 1;  // (the tile ranks and the tile count are ints)
 
 // the chained prefix's scratch: {counter, total, a second count} in one 256-byte slot, then one state word per tile
@@ -500,14 +490,15 @@ struct ChainScratch {
   unsigned long long* state;
   size_t clear_bytes;
 };
-ChainScratch carve_chain(Carve& c, long long n_tiles) {
+ChainScratch carve_chain(Arena& c, long long n_tiles) {
   ChainScratch s;
-  char* head = (char*)c.take(256);
-  s.counter = (unsigned int*)head;
-  s.total = (long long*)(head ? head + 8 : nullptr);
-  s.extra = (unsigned long long*)(head ? head + 16 : nullptr);
-  s.state = (unsigned long long*)c.take((size_t)(n_tiles > 0 ? n_tiles : 1) * 8);
-  s.clear_bytes = 256 + (((size_t)(n_tiles > 0 ? n_tiles : 1) * 8 + 255) & ~(size_t)255);
+  const size_t before = c.bytes();
+  unsigned long long* head = c.take<unsigned long long>(3);  // counter | total | extra, 8 bytes each
+  s.counter = reinterpret_cast<unsigned int*>(head);
+  s.total = reinterpret_cast<long long*>(head ? head + 1 : nullptr);
+  s.extra = head ? head + 2 : nullptr;
+  s.state = c.take<unsigned long long>((size_t)(n_tiles > 0 ? n_tiles : 1));
+  s.clear_bytes = c.bytes() - before;
   return s;
 }
 
@@ -523,13 +514,9 @@ extern "C" int shine_frame_filter(const void* points, int64_t n, int32_t is_fp64
     return set_error(SHINE_E_INVALID, "shine_frame_filter: bad size (0 <= n < 2^31, workspace_bytes required)");
   if (stride != 3 && stride != 4) return set_error(SHINE_E_INVALID, "shine_frame_filter: stride must be 3 or 4 elements per point");
   const long long n_tiles = (n + FI * T - 1) / (FI * T);
-  Carve c{(char*)workspace};
+  Arena c(workspace);
   ChainScratch s = carve_chain(c, n_tiles);
-  if (!workspace) {
-    *workspace_bytes = c.off;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < c.off) return set_error(SHINE_E_INVALID, "shine_frame_filter: workspace too small");
+  SHINE_WORKSPACE_GATE(c.bytes(), workspace, workspace_bytes, "shine_frame_filter");
   if (!n_out) return set_error(SHINE_E_INVALID, "shine_frame_filter: null n_out");
   if (!(pc_radius >= 0.0) || !(max_z >= min_z) || min_range != min_range)
     return set_error(SHINE_E_INVALID, "shine_frame_filter: pc_radius < 0, max_z < min_z or a NaN bound");
@@ -563,13 +550,9 @@ extern "C" int shine_sem_frame_filter(const void* points, int64_t n, int32_t is_
   if (stride != 3 && stride != 4)
     return set_error(SHINE_E_INVALID, "shine_sem_frame_filter: stride must be 3 or 4 elements per point");
   const long long n_tiles = (n + FI * T - 1) / (FI * T);
-  Carve c{(char*)workspace};
+  Arena c(workspace);
   ChainScratch s = carve_chain(c, n_tiles);
-  if (!workspace) {
-    *workspace_bytes = c.off;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < c.off) return set_error(SHINE_E_INVALID, "shine_sem_frame_filter: workspace too small");
+  SHINE_WORKSPACE_GATE(c.bytes(), workspace, workspace_bytes, "shine_sem_frame_filter");
   if (!n_out || !n_unknown_out) return set_error(SHINE_E_INVALID, "shine_sem_frame_filter: null n_out or n_unknown_out");
   if (!(pc_radius >= 0.0) || !(max_z >= min_z) || range_min != range_min)
     return set_error(SHINE_E_INVALID, "shine_sem_frame_filter: pc_radius < 0, max_z < min_z or a NaN bound");
@@ -608,13 +591,9 @@ extern "C" int shine_depth_unproject(const void* depth, int32_t is_float32, int3
   if (row_pitch < width) return set_error(SHINE_E_INVALID, "shine_depth_unproject: row_pitch must be >= width (in pixels)");
   const long long n = (long long)width * height;
   const long long n_tiles = (n + DV * T - 1) / (DV * T);
-  Carve c{(char*)workspace};
+  Arena c(workspace);
   ChainScratch s = carve_chain(c, n_tiles);
-  if (!workspace) {
-    *workspace_bytes = c.off;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < c.off) return set_error(SHINE_E_INVALID, "shine_depth_unproject: workspace too small");
+  SHINE_WORKSPACE_GATE(c.bytes(), workspace, workspace_bytes, "shine_depth_unproject");
   if (!n_out) return set_error(SHINE_E_INVALID, "shine_depth_unproject: null n_out");
   if (!(fx != 0.0) || !(fy != 0.0) || fx != fx || fy != fy || cx != cx || cy != cy)
     return set_error(SHINE_E_INVALID, "shine_depth_unproject: fx and fy must be non-zero, no NaN intrinsics");
@@ -697,14 +676,10 @@ extern "C" int shine_pool_window_filter(const float* coord, int64_t n, const flo
   if (!workspace_bytes || n < 0 || n > MAX_ROWS)
     return set_error(SHINE_E_INVALID, "shine_pool_window_filter: bad size (0 <= n < 2^31, workspace_bytes required)");
   const long long n_tiles = (n + WI * T - 1) / (WI * T);
-  Carve c{(char*)workspace};
+  Arena c(workspace);
   ChainScratch s = carve_chain(c, n_tiles);
-  auto* flags = (unsigned char*)c.take((size_t)(n > 0 ? n : 1));
-  if (!workspace) {
-    *workspace_bytes = c.off;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < c.off) return set_error(SHINE_E_INVALID, "shine_pool_window_filter: workspace too small");
+  unsigned char* flags = c.take<unsigned char>((size_t)(n > 0 ? n : 1));
+  SHINE_WORKSPACE_GATE(c.bytes(), workspace, workspace_bytes, "shine_pool_window_filter");
   if (!n_out || !origin) return set_error(SHINE_E_INVALID, "shine_pool_window_filter: null n_out or origin");
   if (!(radius > 0.0f)) return set_error(SHINE_E_INVALID, "shine_pool_window_filter: radius must be > 0");
   if (n_arrays < 1 || n_arrays > MAX_ARRAYS || !src || !dst || !words)

@@ -313,12 +313,12 @@ struct NnScratch {
 };
 
 NnScratch nn_scratch(void* ws, long long n) {
-  Carve c{(char*)ws};
+  shine::Arena c(ws);
   NnScratch s;
-  s.list0 = (int*)c.take((size_t)n * 4);
-  s.list1 = (int*)c.take((size_t)n * 4);
-  s.count = (int*)c.take(4);
-  s.bytes = c.off;
+  s.list0 = c.take<int>((size_t)n);
+  s.list1 = c.take<int>((size_t)n);
+  s.count = c.take<int>(1);
+  s.bytes = c.bytes();
   return s;
 }
 
@@ -406,11 +406,7 @@ extern "C" int shine_knn_search(const void* grid, int64_t n, int64_t n_fine, int
                                 int32_t* idx_out, double* d2_out, int32_t* count_out, int32_t* rounds_out, void* stream) {
   if (int rc = check_sizes("shine_knn_search", "k", n, n_fine, n_coarse, k, workspace_bytes)) return rc;
   const NnScratch s = nn_scratch(workspace, n);
-  if (!workspace) {
-    *workspace_bytes = s.bytes;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < s.bytes) return shine::set_error(SHINE_E_INVALID, "shine_knn_search: workspace too small");
+  SHINE_WORKSPACE_GATE(s.bytes, workspace, workspace_bytes, "shine_knn_search");
   if (!idx_out || !d2_out || !count_out || radius != radius)
     return shine::set_error(SHINE_E_INVALID, "shine_knn_search: null argument or radius is NaN");
   GridDev g;
@@ -423,11 +419,7 @@ extern "C" int shine_sor_mean_dist(const void* grid, int64_t n, int64_t n_fine, 
                                    double* mean_dist_out, double* stats_out, int32_t* rounds_out, void* stream) {
   if (int rc = check_sizes("shine_sor_mean_dist", "k", n, n_fine, n_coarse, k, workspace_bytes)) return rc;
   const NnScratch s = nn_scratch(workspace, n);
-  if (!workspace) {
-    *workspace_bytes = s.bytes;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < s.bytes) return shine::set_error(SHINE_E_INVALID, "shine_sor_mean_dist: workspace too small");
+  SHINE_WORKSPACE_GATE(s.bytes, workspace, workspace_bytes, "shine_sor_mean_dist");
   if (!mean_dist_out || !stats_out) return shine::set_error(SHINE_E_INVALID, "shine_sor_mean_dist: null argument");
   GridDev g;
   if (int rc = check_grid("shine_sor_mean_dist", grid, n, n_fine, n_coarse, origin, cell, cells_per_axis, &g)) return rc;
@@ -443,11 +435,7 @@ extern "C" int shine_frame_normals(const void* grid, int64_t n, int64_t n_fine, 
                                    void* workspace, size_t* workspace_bytes, double* normals_out, void* stream) {
   if (int rc = check_sizes("shine_frame_normals", "max_nn", n, n_fine, n_coarse, max_nn, workspace_bytes)) return rc;
   const NnScratch s = nn_scratch(workspace, n);
-  if (!workspace) {
-    *workspace_bytes = s.bytes;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < s.bytes) return shine::set_error(SHINE_E_INVALID, "shine_frame_normals: workspace too small");
+  SHINE_WORKSPACE_GATE(s.bytes, workspace, workspace_bytes, "shine_frame_normals");
   if (!normals_out || !viewpoint || !(radius >= 0.0) || radius == INFINITY)
     return shine::set_error(SHINE_E_INVALID, "shine_frame_normals: null argument or radius not a finite number >= 0");
   GridDev g;

@@ -90,6 +90,7 @@ class Arena {
     off_ += (count * sizeof(T) + 255) & ~(size_t)255;
     return reinterpret_cast<T*>(p);
   }
+  void* take_bytes(size_t bytes) { return take<char>(bytes); }  // untyped storage, e.g. rocPRIM's temporaries
   size_t bytes() const { return off_; }
 
  private:
@@ -125,6 +126,23 @@ struct shine_tables {
   do {                                                             \
     hipError_t e__ = (expr);                                       \
     if (e__ != hipSuccess) return shine::set_hip_error(e__, #expr); \
+  } while (0)
+
+// The workspace convention of include/shine_hip.h, once.  `need` is what the entry point's Arena counted (bytes()), `entry` its
+// name as a string literal.  Both return from the caller, like SHINE_HIP_CHECK.
+//   SHINE_WORKSPACE_FITS: refuses a missing or short workspace (`have` bytes) — all an entry point with a by-value size needs.
+//   SHINE_WORKSPACE_GATE: workspace == NULL answers the size query; otherwise as above with *workspace_bytes; else falls through.
+#define SHINE_WORKSPACE_FITS(need, workspace, have, entry) \
+  do {                                                     \
+    if (!(workspace) || (have) < (need)) return shine::set_error(SHINE_E_INVALID, entry ": workspace too small"); \
+  } while (0)
+#define SHINE_WORKSPACE_GATE(need, workspace, workspace_bytes, entry)    \
+  do {                                                                   \
+    if (!(workspace)) {                                                  \
+      *(workspace_bytes) = (need);                                       \
+      return SHINE_OK;                                                   \
+    }                                                                    \
+    SHINE_WORKSPACE_FITS(need, workspace, *(workspace_bytes), entry);    \
   } while (0)
 
 namespace shine {

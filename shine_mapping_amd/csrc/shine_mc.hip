@@ -194,7 +194,7 @@ McWork mc_layout(void* base, long long N, hipStream_t st) {
   w.tile_fbase = a.take<int>(tiles);
   w.totals = a.take<unsigned long long>(2);
   (void)shine::prim_scan_int(nullptr, w.scan_bytes, nullptr, nullptr, tiles, st);
-  w.scan_tmp = a.take<char>(w.scan_bytes);
+  w.scan_tmp = a.take_bytes(w.scan_bytes);
   w.bytes = a.bytes();
   return w;
 }
@@ -218,12 +218,8 @@ extern "C" int shine_mc_count(const float* sdf, const uint8_t* mask, int64_t nx,
   hipStream_t st = (hipStream_t)stream;
   const long long N = nx * ny * nz;
   McWork w = mc_layout(workspace, N, st);
-  if (!workspace) {
-    *workspace_bytes = w.bytes;
-    return SHINE_OK;
-  }
-  if (!counts_out) return shine::set_error(SHINE_E_INVALID, "shine_mc_count: null counts_out");
-  if (*workspace_bytes < w.bytes) return shine::set_error(SHINE_E_INVALID, "shine_mc_count: workspace too small");
+  if (workspace && !counts_out) return shine::set_error(SHINE_E_INVALID, "shine_mc_count: null counts_out");
+  SHINE_WORKSPACE_GATE(w.bytes, workspace, workspace_bytes, "shine_mc_count");
   counts_out[0] = counts_out[1] = 0;
   if (N == 0) return SHINE_OK;
   const long long tiles = (N + MC_TILE - 1) / MC_TILE;
@@ -244,7 +240,7 @@ extern "C" int shine_mc_emit(const float* sdf, const uint8_t* mask, int64_t nx, 
   const long long N = nx * ny * nz;
   if (N == 0) return SHINE_OK;
   McWork w = mc_layout(workspace, N, st);
-  if (!workspace || workspace_bytes < w.bytes) return shine::set_error(SHINE_E_INVALID, "shine_mc_emit: workspace too small");
+  SHINE_WORKSPACE_FITS(w.bytes, workspace, workspace_bytes, "shine_mc_emit");
   if (!verts_out || !faces_out) return shine::set_error(SHINE_E_INVALID, "shine_mc_emit: null output");
   const long long tiles = (N + MC_TILE - 1) / MC_TILE;
   McGrid g = {sdf, mask, nx, ny, nz, N, level};

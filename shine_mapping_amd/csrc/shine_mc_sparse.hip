@@ -264,7 +264,7 @@ SpWork sp_layout(void* base, long long n_bricks, int B, hipStream_t st) {
   w.brick_fbase = a.take<int>(n);
   w.totals = a.take<u64>(2);
   (void)shine::prim_scan_int(nullptr, w.scan_bytes, nullptr, nullptr, n, st);
-  w.scan_tmp = a.take<char>(w.scan_bytes);
+  w.scan_tmp = a.take_bytes(w.scan_bytes);
   w.bytes = a.bytes();
   return w;
 }
@@ -309,7 +309,7 @@ SpScratch sp_scratch(void* base, long long n_records, long long n_faces, unsigne
   (void)shine::prim_sort_pairs_u64(nullptr, sort_f, nullptr, nullptr, nullptr, nullptr, F, 0u, fbits, st);
   (void)shine::prim_scan_flags(nullptr, scan, nullptr, nullptr, C, st);
   s.tmp_bytes = std::max(sort_v, std::max(sort_f, scan));
-  s.tmp = a.take<char>(s.tmp_bytes);
+  s.tmp = a.take_bytes(s.tmp_bytes);
   s.bytes = a.bytes();
   return s;
 }
@@ -385,12 +385,8 @@ extern "C" int shine_mc_sparse_count(const float* values, const uint8_t* mask, c
     std::vector<int> nbr;
     if (sp_brick_table(origins, n, brick, nx, ny, nz, nbr)) return SHINE_E_INVALID;
     SpWork w = sp_layout(workspace, n, brick, st);
-    if (!workspace) {
-      *workspace_bytes = w.bytes;
-      return SHINE_OK;
-    }
-    if (!counts_out) return shine::set_error(SHINE_E_INVALID, "shine_mc_sparse_count: null counts_out");
-    if (*workspace_bytes < w.bytes) return shine::set_error(SHINE_E_INVALID, "shine_mc_sparse_count: workspace too small");
+    if (workspace && !counts_out) return shine::set_error(SHINE_E_INVALID, "shine_mc_sparse_count: null counts_out");
+    SHINE_WORKSPACE_GATE(w.bytes, workspace, workspace_bytes, "shine_mc_sparse_count");
     counts_out[0] = counts_out[1] = 0;
     if (n == 0 || nx == 0 || ny == 0 || nz == 0) return SHINE_OK;
     hipError_t e = hipMemcpyAsync(w.org, origins, (size_t)n * 24, hipMemcpyHostToDevice, st);
@@ -422,7 +418,7 @@ extern "C" int shine_mc_sparse_emit(const float* values, const uint8_t* mask, in
   const u64 points = (u64)nx * (u64)ny * (u64)nz;
   const unsigned vbits = key_bits(points * 4 - 1), fbits = key_bits(points * 8 - 1);
   SpScratch s = sp_scratch(scratch, C, F, vbits, fbits, st);
-  if (!scratch) {
+  if (!scratch) {  // (by hand, not SHINE_WORKSPACE_GATE: the scratch has its own message, after checks only a real call passes)
     *scratch_bytes = s.bytes;
     return SHINE_OK;
   }
@@ -433,7 +429,7 @@ extern "C" int shine_mc_sparse_emit(const float* values, const uint8_t* mask, in
   if (!verts_out || (F > 0 && !faces_out)) return shine::set_error(SHINE_E_INVALID, "shine_mc_sparse_emit: null output");
   if (*scratch_bytes < s.bytes) return shine::set_error(SHINE_E_INVALID, "shine_mc_sparse_emit: scratch too small");
   SpWork w = sp_layout(workspace, n, brick, st);
-  if (!workspace || workspace_bytes < w.bytes) return shine::set_error(SHINE_E_INVALID, "shine_mc_sparse_emit: workspace too small");
+  SHINE_WORKSPACE_FITS(w.bytes, workspace, workspace_bytes, "shine_mc_sparse_emit");
   SpGrid g = {values, mask, w.org, w.nbr, nx, ny, nz, brick, brick + 1, level};
   SpRecords o = {s.vkeys, s.vvals, s.fkeys, s.fvals, s.frec};
   if ((brick + 1) * (brick + 1) * (brick + 1) <= SP_CAP_SMALL) launch_emit<SP_CAP_SMALL>(g, n, w, o, st);

@@ -173,12 +173,8 @@ extern "C" int shine_mesh_vertex_normals(const double* verts, int64_t n_verts, c
   size_t sort_bytes = 0;
   const unsigned end_bit = 32 + bits_for(n_verts);
   SHINE_HIP_CHECK(shine::prim_sort_keys_u64(nullptr, sort_bytes, nullptr, nullptr, (size_t)nk, 0u, end_bit, st));
-  void* tmp = c.take<char>(sort_bytes);
-  if (!workspace) {
-    *workspace_bytes = c.bytes();
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < c.bytes()) return shine::set_error(SHINE_E_INVALID, "shine_mesh_vertex_normals: workspace too small");
+  void* tmp = c.take_bytes(sort_bytes);
+  SHINE_WORKSPACE_GATE(c.bytes(), workspace, workspace_bytes, "shine_mesh_vertex_normals");
   if (n_verts == 0) return SHINE_OK;
   if (!verts || !normals_out || (n_faces && !faces)) return shine::set_error(SHINE_E_INVALID, "shine_mesh_vertex_normals: null argument");
   SHINE_HIP_CHECK(hipMemsetAsync(start, 0, n_verts * 8, st));
@@ -218,12 +214,8 @@ extern "C" int shine_mesh_cluster_filter(const int32_t* faces, int64_t n_faces, 
   SHINE_HIP_CHECK(shine::prim_sort_pairs_u64(nullptr, sort_bytes, nullptr, nullptr, nullptr, nullptr, (size_t)nk, 0u, 64u, st));
   SHINE_HIP_CHECK(shine::prim_scan_flags(nullptr, scan_bytes, nullptr, nullptr, (size_t)n_faces, st));
   const size_t tmp_bytes = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-  void* tmp = c.take<char>(tmp_bytes);
-  if (!workspace) {
-    *workspace_bytes = c.bytes();
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < c.bytes()) return shine::set_error(SHINE_E_INVALID, "shine_mesh_cluster_filter: workspace too small");
+  void* tmp = c.take_bytes(tmp_bytes);
+  SHINE_WORKSPACE_GATE(c.bytes(), workspace, workspace_bytes, "shine_mesh_cluster_filter");
   if (!kept_out) return shine::set_error(SHINE_E_INVALID, "shine_mesh_cluster_filter: null kept_out");
   *kept_out = 0;
   if (n_faces == 0) return SHINE_OK;

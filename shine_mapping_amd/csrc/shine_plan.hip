@@ -151,8 +151,6 @@ __global__ __launch_bounds__(256) void k_plan_unsorted(PlanArgs a) {
   a.perm[i] = (int)i;
 }
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace shine
 
 using namespace shine;
@@ -170,22 +168,20 @@ extern "C" int shine_plan_batch(const shine_tables* t, const shine_step_config* 
   const size_t nb = (size_t)t->n_buckets, cnt = (size_t)(n > 0 ? n : 1);
   size_t scan_bytes = 0;
   SHINE_HIP_CHECK(prim_scan_int(nullptr, scan_bytes, nullptr, nullptr, nb, st));
-  const size_t o_count = 0, o_bucket = o_count + align256(nb * 4), o_local = o_bucket + align256(cnt * 4),
-               o_slots = o_local + align256(cnt * 4), o_scan = o_slots + align256(cnt * (size_t)L * 4),
-               need = o_scan + align256(scan_bytes);
+  Arena ws(workspace);
+  int* const w_count = ws.take<int>(nb);
+  int* const w_bucket = ws.take<int>(cnt);
+  int* const w_local = ws.take<int>(cnt);
+  int* const w_slots = ws.take<int>(cnt * (size_t)L);
+  void* const w_scan = ws.take_bytes(scan_bytes);
   if (zero_ptr && (((size_t)zero_ptr | zero_bytes) & 15))
     return set_error(SHINE_E_INVALID, "shine_plan_batch: zero buffer must be 16-byte aligned and sized");
-  if (!workspace) {
-    *workspace_bytes = need;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < need) return set_error(SHINE_E_INVALID, "shine_plan_batch: workspace too small");
+  SHINE_WORKSPACE_GATE(ws.bytes(), workspace, workspace_bytes, "shine_plan_batch");
   if (n == 0) {
     if (zero_ptr && zero_bytes) SHINE_HIP_CHECK(hipMemsetAsync(zero_ptr, 0, zero_bytes, st));
     return SHINE_OK;
   }
   if (!coord || !perm_out || !slots_out) return set_error(SHINE_E_INVALID, "shine_plan_batch: null coord/perm/slots");
-  char* w = (char*)workspace;
   PlanArgs a = {};
   for (int s = 0; s < L; ++s) {
     const TableLevel& T = t->lv[s];
@@ -201,13 +197,13 @@ extern "C" int shine_plan_batch(const shine_tables* t, const shine_step_config* 
   a.n_levels = L;
   a.res_leaf = (float)(1u << cfg->max_level);
   a.first_miss_bucket = (int)(t->n_buckets - MISS_BUCKETS);
-  a.count = (int*)(w + o_count);
-  a.bucket = (int*)(w + o_bucket);
-  a.local = (int*)(w + o_local);
+  a.count = w_count;
+  a.bucket = w_bucket;
+  a.local = w_local;
   a.zero_ptr = (float4*)zero_ptr;
   a.zero_n16 = zero_ptr ? (long long)(zero_bytes / 16) : 0;
   a.ablate = cfg->kernel_variant >> 8;
-  a.slots_tmp = (int*)(w + o_slots);
+  a.slots_tmp = w_slots;
   a.perm = (int*)perm_out;
   a.slots_sorted = (int*)slots_out;
   if (n <= PLAN_UNSORTED_MAX && !(a.ablate & 15)) {  // (kernel_variant 0x800: tests / measurement — the counting sort for every size)
@@ -221,7 +217,7 @@ extern "C" int shine_plan_batch(const shine_tables* t, const shine_step_config* 
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
   hipLaunchKernelGGL(k_plan_count, grid, block, 0, st, a);
   SHINE_HIP_CHECK(hipGetLastError());
-  SHINE_HIP_CHECK(prim_scan_int(w + o_scan, scan_bytes, a.count, a.count, nb, st));
+  SHINE_HIP_CHECK(prim_scan_int(w_scan, scan_bytes, a.count, a.count, nb, st));
   hipLaunchKernelGGL(k_plan_scatter, grid, block, 0, st, a);
   SHINE_HIP_CHECK(hipGetLastError());
   return SHINE_OK;

@@ -121,8 +121,6 @@ __global__ __launch_bounds__(256) void k_sample_fused(int nblocks, long long n, 
   sample_fused_block(sm, (int)blockIdx.x, nblocks, n, pool, seed, stream, stream_dev, idx, surf_bits, surf_parts);
 }
 
-static size_t align256s(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace shine
 
 using namespace shine;
@@ -138,12 +136,9 @@ static int sample_sorted_impl(int64_t pool_size, int64_t n, uint64_t seed, uint6
   hipStream_t st = (hipStream_t)stream;
   const long long n1 = (long long)n + 1;  // n draws + the closing spacing
   const long long nblocks = (n1 + SB - 1) / SB;
-  const size_t need = align256s((size_t)nblocks * sizeof(double));
-  if (!workspace) {
-    *workspace_bytes = need;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < need) return set_error(SHINE_E_INVALID, "shine_sample_sorted: workspace too small");
+  Arena ws(workspace);
+  double* bs = ws.take<double>((size_t)nblocks);  // pass 1's block sums
+  SHINE_WORKSPACE_GATE(ws.bytes(), workspace, workspace_bytes, "shine_sample_sorted");
   if (zero_ptr && (((size_t)zero_ptr | zero_bytes) & 15))
     return set_error(SHINE_E_INVALID, "shine_sample_sorted: zero buffer must be 16-byte aligned and sized");
   // pass 2 over the blocks that hold the slice (an empty slice still runs one block: it advances the device stream id)
@@ -164,7 +159,6 @@ static int sample_sorted_impl(int64_t pool_size, int64_t n, uint64_t seed, uint6
     SHINE_HIP_CHECK(hipGetLastError());
     return SHINE_OK;
   }
-  double* bs = (double*)workspace;
   hipLaunchKernelGGL(k_sample_pass1, dim3((unsigned)nblocks), dim3(256), 0, st, bs, n1, (unsigned long long)seed,
                      (unsigned long long)stream_id, (const unsigned long long*)stream_dev, (float4*)zero_ptr,
                      zero_ptr ? (long long)(zero_bytes / 16) : 0ll, (long long*)surf_parts);
@@ -211,6 +205,7 @@ extern "C" int shine_sample_sorted_finish(int64_t pool_size, int64_t n, int64_t 
                                           size_t workspace_bytes, void* stream) {
   if (slice_n < 0) slice_n = n - slice_begin;
   const long long nblocks = ((long long)n + 1 + SB - 1) / SB;
+  // (not SHINE_WORKSPACE_FITS: the bound is the block sums this launch reads, unrounded, and one message covers all arguments)
   if (n < 1 || pool_size < 1 || pool_size > 0x7fffffffll || slice_begin < 0 || slice_n < 0 || slice_begin + slice_n > n ||
       !stream_state || !idx_out || !workspace || workspace_bytes < (size_t)nblocks * sizeof(double) ||
       (surf_parts && !surf_bits))

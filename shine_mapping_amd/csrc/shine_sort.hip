@@ -48,8 +48,6 @@ __global__ void k_sort_perm(const unsigned long long* vals, long long n, int* pe
   if (i < n) perm[i] = (int)vals[i];
 }
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // The radix sort is the library's one (u64 key, u64 value) instantiation (shine_prims.hip): rounds 1-2 carried four sort
 // configurations here — 3.5 MB of code object for a function the hot path no longer calls (a batch is ordered by the
 // counting sort of shine_plan.hip, ~2x faster than any radix sort at these sizes).
@@ -60,20 +58,14 @@ static int sort_impl(const float* coord, long long n, float res, const SortBox& 
   const size_t cnt = (size_t)(n > 0 ? n : 1);
   size_t tmp_bytes = 0;
   SHINE_HIP_CHECK(prim_sort_pairs_u64(nullptr, tmp_bytes, nullptr, nullptr, nullptr, nullptr, cnt, 0u, end_bit, st));
-  const size_t kb = align256(cnt * sizeof(K)), vb = align256(cnt * 8);
-  const size_t need = 2 * kb + 2 * vb + align256(tmp_bytes);
-  if (!workspace) {
-    *workspace_bytes = need;
-    return SHINE_OK;
-  }
-  if (*workspace_bytes < need) return set_error(SHINE_E_INVALID, "shine_morton_sort: workspace too small");
+  Arena ws(workspace);
+  K* k0 = ws.take<K>(cnt);
+  K* k1 = ws.take<K>(cnt);
+  unsigned long long* v0 = ws.take<unsigned long long>(cnt);
+  unsigned long long* v1 = ws.take<unsigned long long>(cnt);
+  void* tmp = ws.take_bytes(tmp_bytes);
+  SHINE_WORKSPACE_GATE(ws.bytes(), workspace, workspace_bytes, "shine_morton_sort");
   if (n == 0) return SHINE_OK;
-  char* w = (char*)workspace;
-  K* k0 = (K*)w;
-  K* k1 = (K*)(w + kb);
-  unsigned long long* v0 = (unsigned long long*)(w + 2 * kb);
-  unsigned long long* v1 = (unsigned long long*)(w + 2 * kb + vb);
-  void* tmp = w + 2 * kb + 2 * vb;
   hipLaunchKernelGGL((k_sort_keys<K>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, coord, n, res, box, k0, v0);
   SHINE_HIP_CHECK(hipGetLastError());
   SHINE_HIP_CHECK(prim_sort_pairs_u64(tmp, tmp_bytes, k0, k1, v0, v1, (size_t)n, 0u, end_bit, st));

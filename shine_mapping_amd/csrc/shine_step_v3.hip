@@ -162,8 +162,7 @@ int prepare_step_v3(StepLaunch* out, const shine_tables* t, const shine_step_con
   a.waves_total = g.waves;
   a.prof = g_prof_buffer;
   const size_t need = (size_t)g.blocks * PART_STRIDE * sizeof(float);
-  if (!workspace || workspace_bytes < need)
-    return set_error(SHINE_E_INVALID, "shine_train_step_v3: workspace too small (shine_train_step_workspace_bytes)");
+  SHINE_WORKSPACE_FITS(need, workspace, workspace_bytes, "shine_train_step_v3");  // (need: shine_train_step_workspace_bytes)
   a.partials = (float*)workspace;
   // touched-row flags: set by the scatter of the MARK build (steps whose every level has a gradient table: a level without
   // one is not walked), by a marking pass in front of the step otherwise
@@ -286,8 +285,7 @@ extern "C" int shine_interp_sdf_backward(const shine_tables* t, const shine_step
   a.tiles = g.tiles;
   a.waves_total = g.waves;
   const size_t need = (size_t)g.blocks * PART_STRIDE * sizeof(float);
-  if (!workspace || workspace_bytes < need)
-    return set_error(SHINE_E_INVALID, "shine_interp_sdf_backward: workspace too small (shine_train_step_workspace_bytes)");
+  SHINE_WORKSPACE_FITS(need, workspace, workspace_bytes, "shine_interp_sdf_backward");  // (need: shine_train_step_workspace_bytes)
   a.partials = (float*)workspace;
   hipStream_t st = (hipStream_t)stream;
   DrawRiderArgs no_rider = {};

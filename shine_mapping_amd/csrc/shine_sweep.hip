@@ -192,12 +192,17 @@ extern "C" int shine_importance_chunks(const int32_t* perm, int64_t n, int64_t b
   if (n > 0x7fffffffll) return set_error(SHINE_E_INVALID, "shine_importance_chunks: pool exceeds the int32 index range");
   unsigned end_bit = 1;
   while ((1ll << end_bit) <= (long long)n_chunks) ++end_bit;  // keys 0 .. n_chunks
-  const size_t ab = ((size_t)n * 8 + 255) & ~(size_t)255;
   size_t tmp_bytes = 0;
   if (bs > SWEEP_SORT_MAX)
     SHINE_HIP_CHECK(prim_sort_pairs_u64(nullptr, tmp_bytes, nullptr, nullptr, nullptr, nullptr, (size_t)(n > 0 ? n : 1), 0u,
                                         end_bit, (hipStream_t)stream));
-  const size_t need = bs <= SWEEP_SORT_MAX ? 256 : 4 * ab + tmp_bytes;  // (the two-launch form needs none)
+  Arena ws(workspace);
+  unsigned long long *k0 = ws.take<unsigned long long>((size_t)n), *k1 = ws.take<unsigned long long>((size_t)n);
+  unsigned long long *v0 = ws.take<unsigned long long>((size_t)n), *v1 = ws.take<unsigned long long>((size_t)n);
+  void* const tmp = ws.take_bytes(0);  // rocPRIM's temporaries start here; their tmp_bytes are added below, unrounded
+  // Not SHINE_WORKSPACE_GATE: the two-launch form uses no workspace and asks for a token 256 bytes, the radix form's size ends
+  // unrounded, and one message covers the null arguments too.
+  const size_t need = bs <= SWEEP_SORT_MAX ? 256 : ws.bytes() + tmp_bytes;
   if (!workspace) {
     *workspace_bytes = need;
     return SHINE_OK;
@@ -230,13 +235,10 @@ extern "C" int shine_importance_chunks(const int32_t* perm, int64_t n, int64_t b
     SHINE_HIP_CHECK(hipGetLastError());
     return SHINE_OK;
   }
-  char* w = (char*)workspace;
-  unsigned long long *k0 = (unsigned long long*)w, *k1 = (unsigned long long*)(w + ab);
-  unsigned long long *v0 = (unsigned long long*)(w + 2 * ab), *v1 = (unsigned long long*)(w + 3 * ab);
   hipLaunchKernelGGL(k_sweep_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, perm, (long long)n, interval,
                      (int)down_rate, (int)n_chunks, k0, v0);
   SHINE_HIP_CHECK(hipGetLastError());
-  SHINE_HIP_CHECK(prim_sort_pairs_u64(w + 4 * ab, tmp_bytes, k0, k1, v0, v1, (size_t)n, 0u, end_bit, st));
+  SHINE_HIP_CHECK(prim_sort_pairs_u64(tmp, tmp_bytes, k0, k1, v0, v1, (size_t)n, 0u, end_bit, st));
   hipLaunchKernelGGL(k_sweep_members, dim3((unsigned)((kept + 255) / 256)), dim3(256), 0, st, v1, kept, (int*)idx_out);
   SHINE_HIP_CHECK(hipGetLastError());
   return SHINE_OK;
@@ -332,8 +334,8 @@ extern "C" int shine_importance_sweep(const shine_tables* t, const shine_step_co
   sa.bpc = (int)g.blocks;
   sa.grad_stride = (long long)gf;
   sa.flag_stride = (long long)fb;
-  if (!workspace || workspace_bytes < (size_t)group * (size_t)g.blocks * PART_STRIDE * sizeof(float))
-    return set_error(SHINE_E_INVALID, "shine_importance_sweep: workspace too small (shine_importance_sweep_sizes)");
+  SHINE_WORKSPACE_FITS((size_t)group * (size_t)g.blocks * PART_STRIDE * sizeof(float), workspace, workspace_bytes,
+                       "shine_importance_sweep");  // (the size shine_importance_sweep_sizes answers)
   const void* fn = sweep_fn(L);
 
   long long max_rows = 0;

@@ -203,10 +203,6 @@ class PointCloud:
         return ev.bounds(self.points)[1]
 
 
-def _ws(nbytes, device):
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
-
-
 def frame_filter(points, min_z, max_z, min_range, pc_radius):
     """preprocess_kitti + the crop box (shine_frame_filter): points = device [n,3] / [n,4] float32 or float64, contiguous.  Keeps,
     in input order, z > min_z, |p| >= min_range, |x|, |y| <= pc_radius, min_z <= z <= max_z.  -> fp64 [k,3] on the device."""
@@ -219,15 +215,11 @@ def frame_filter(points, min_z, max_z, min_range, pc_radius):
     out = torch.empty((n, 3), dtype=torch.float64, device=points.device)
     if n == 0:
         return out
-    lib, st = _lib.lib(), _lib.current_stream_handle()
-    need = C.c_size_t(0)
-    args = (n, int(points.dtype == torch.float64), int(points.shape[1]), float(min_z), float(max_z), float(min_range),
-            float(pc_radius))
-    _lib.check(lib.shine_frame_filter(None, *args, None, C.byref(need), None, None, st), "shine_frame_filter")
-    ws = _ws(need.value, points.device)
     kept = C.c_int64(0)
-    _lib.check(lib.shine_frame_filter(points.data_ptr(), *args, ws.data_ptr(), C.byref(need), out.data_ptr(), C.byref(kept), st),
-               "shine_frame_filter")
+    _lib.call_with_workspace(
+        _lib.lib().shine_frame_filter, points.device, points.data_ptr(), n, int(points.dtype == torch.float64),
+        int(points.shape[1]), float(min_z), float(max_z), float(min_range), float(pc_radius), _lib.WS, _lib.WS_BYTES,
+        out.data_ptr(), C.byref(kept), _lib.current_stream_handle())
     return out[:kept.value]
 
 
@@ -258,17 +250,12 @@ def sem_frame_filter(points, labels, label_map, range_min, filter_moving, filter
     if n == 0:
         return out, cls
     lut = label_map.device_lut(points.device)
-    lib, st = _lib.lib(), _lib.current_stream_handle()
-    need = C.c_size_t(0)
-    is64, stride = int(points.dtype == torch.float64), int(points.shape[1])
-    tail = (float(range_min), int(bool(filter_moving)), int(bool(filter_outlier)), float(min_z), float(max_z), float(pc_radius))
-    _lib.check(lib.shine_sem_frame_filter(None, n, is64, stride, None, None, *tail, None, C.byref(need), None, None, None, None, st),
-               "shine_sem_frame_filter")
-    ws = _ws(need.value, points.device)
     kept, unknown = C.c_int64(0), C.c_int64(0)
-    _lib.check(lib.shine_sem_frame_filter(points.data_ptr(), n, is64, stride, labels.data_ptr(), lut.data_ptr(), *tail, ws.data_ptr(),
-                                          C.byref(need), out.data_ptr(), cls.data_ptr(), C.byref(kept), C.byref(unknown), st),
-               "shine_sem_frame_filter")
+    _lib.call_with_workspace(
+        _lib.lib().shine_sem_frame_filter, points.device, points.data_ptr(), n, int(points.dtype == torch.float64),
+        int(points.shape[1]), labels.data_ptr(), lut.data_ptr(), float(range_min), int(bool(filter_moving)),
+        int(bool(filter_outlier)), float(min_z), float(max_z), float(pc_radius), _lib.WS, _lib.WS_BYTES, out.data_ptr(),
+        cls.data_ptr(), C.byref(kept), C.byref(unknown), _lib.current_stream_handle())
     if unknown.value > 0:
         ids = labels.to(torch.int64) & 0xFFFF
         bad = torch.unique(ids[lut[ids] < 0]).tolist()  # (candidates: the kernel counted those among them that pass the filters)
@@ -314,13 +301,10 @@ def knn(points, k, radius=None, return_rounds=False):
     idx = torch.empty((n, k), dtype=torch.int32, device=dev)
     d2 = torch.empty((n, k), dtype=torch.float64, device=dev)
     count = torch.empty(n, dtype=torch.int32, device=dev)
-    lib, st = _lib.lib(), _lib.current_stream_handle()
-    need, rounds = C.c_size_t(0), C.c_int32(0)
-    r = -1.0 if radius is None else float(radius)
-    _lib.check(lib.shine_knn_search(None, *args[1:], k, r, None, C.byref(need), None, None, None, None, st), "shine_knn_search")
-    ws = _ws(need.value, dev)
-    _lib.check(lib.shine_knn_search(*args, k, r, ws.data_ptr(), C.byref(need), idx.data_ptr(), d2.data_ptr(), count.data_ptr(),
-                                    C.byref(rounds), st), "shine_knn_search")
+    rounds = C.c_int32(0)
+    _lib.call_with_workspace(
+        _lib.lib().shine_knn_search, dev, *args, k, -1.0 if radius is None else float(radius), _lib.WS, _lib.WS_BYTES,
+        idx.data_ptr(), d2.data_ptr(), count.data_ptr(), C.byref(rounds), _lib.current_stream_handle())
     return (idx, d2, count, int(rounds.value)) if return_rounds else (idx, d2, count)
 
 
@@ -344,12 +328,9 @@ def statistical_outlier_mask(points, nb_neighbors, std_ratio, return_rounds=Fals
     n, dev = grid.n, grid.ref.device
     avg = torch.empty(n, dtype=torch.float64, device=dev)
     stats = torch.empty(2, dtype=torch.float64, device=dev)
-    lib, st = _lib.lib(), _lib.current_stream_handle()
-    need, rounds = C.c_size_t(0), C.c_int32(0)
-    _lib.check(lib.shine_sor_mean_dist(None, *args[1:], k, None, C.byref(need), None, None, None, st), "shine_sor_mean_dist")
-    ws = _ws(need.value, dev)
-    _lib.check(lib.shine_sor_mean_dist(*args, k, ws.data_ptr(), C.byref(need), avg.data_ptr(), stats.data_ptr(), C.byref(rounds),
-                                       st), "shine_sor_mean_dist")
+    rounds = C.c_int32(0)
+    _lib.call_with_workspace(_lib.lib().shine_sor_mean_dist, dev, *args, k, _lib.WS, _lib.WS_BYTES, avg.data_ptr(),
+                             stats.data_ptr(), C.byref(rounds), _lib.current_stream_handle())
     mean, ssq = (float(v) for v in stats.cpu())
     std = float(np.sqrt(ssq / (n - 1))) if n > 1 else 0.0
     threshold = mean + float(std_ratio) * std
@@ -372,12 +353,8 @@ def estimate_normals(points, radius, max_nn, viewpoint=(0.0, 0.0, 0.0)):
         raise ValueError("estimate_normals: radius must be a finite length >= 0, got %r" % (radius,))
     grid, args = _frame_grid(points, "estimate_normals")
     out = torch.empty((grid.n, 3), dtype=torch.float64, device=grid.ref.device)
-    lib, st = _lib.lib(), _lib.current_stream_handle()
-    need = C.c_size_t(0)
-    _lib.check(lib.shine_frame_normals(None, *args[1:], radius, k, None, None, C.byref(need), None, st), "shine_frame_normals")
-    ws = _ws(need.value, out.device)
-    _lib.check(lib.shine_frame_normals(*args, radius, k, ev._d3(viewpoint), ws.data_ptr(), C.byref(need), out.data_ptr(), st),
-               "shine_frame_normals")
+    _lib.call_with_workspace(_lib.lib().shine_frame_normals, out.device, *args, radius, k, ev._d3(viewpoint), _lib.WS,
+                             _lib.WS_BYTES, out.data_ptr(), _lib.current_stream_handle())
     return out
 
 
@@ -470,17 +447,12 @@ def pool_window_filter(coord, origin, radius, arrays):
         return outs, 0
     if not (coord.is_cuda and coord.is_contiguous() and coord.dtype == torch.float32 and coord.dim() == 2 and coord.shape[1] == 3):
         raise ValueError("pool_window_filter: coord must be a contiguous device [n,3] float32 tensor")
-    lib, st = _lib.lib(), _lib.current_stream_handle()
     o3 = (C.c_float * 3)(*[float(v) for v in origin])
     src, dst = _lib.ptr_array([a.data_ptr() for a in arrays]), _lib.ptr_array([a.data_ptr() for a in outs])
     w = (C.c_int32 * len(words))(*words)
-    need = C.c_size_t(0)
     kept = C.c_int64(0)
-    _lib.check(lib.shine_pool_window_filter(None, n, o3, float(radius), len(arrays), src, dst, w, None, C.byref(need), None, st),
-               "shine_pool_window_filter")
-    ws = _ws(need.value, coord.device)
-    _lib.check(lib.shine_pool_window_filter(coord.data_ptr(), n, o3, float(radius), len(arrays), src, dst, w, ws.data_ptr(),
-                                            C.byref(need), C.byref(kept), st), "shine_pool_window_filter")
+    _lib.call_with_workspace(_lib.lib().shine_pool_window_filter, coord.device, coord.data_ptr(), n, o3, float(radius), len(arrays),
+                             src, dst, w, _lib.WS, _lib.WS_BYTES, C.byref(kept), _lib.current_stream_handle())
     return outs, int(kept.value)
 
 

@@ -96,11 +96,9 @@ def morton_order(octree, coord: torch.Tensor) -> torch.Tensor:
     skey = key + (n, wide, tuple(cfg.sort_bits))
     sized = _WS.get(skey)
     if sized is None:  # size query once per (batch size, key bits); ONE grow-only buffer per device behind it
-        q = C.c_size_t(0)
-        _lib.check(lib.shine_morton_sort(C.byref(cfg), None, n, None, None, C.byref(q), stream),
-                   "shine_morton_sort")
+        sized = _lib.workspace_bytes(lib.shine_morton_sort, C.byref(cfg), None, n, None, _lib.WS, _lib.WS_BYTES, stream)
         _WS.clear_sizes(key)
-        sized = _WS[skey] = int(q.value)
+        _WS[skey] = sized
     ent = _WS.get(key)
     if ent is None or ent.numel() < sized:
         ent = _WS[key] = torch.empty(max(sized + sized // 4, 1), dtype=torch.uint8, device=coord.device)
@@ -138,11 +136,10 @@ def plan_batch(octree, coord: torch.Tensor, zero: torch.Tensor = None, _debug_va
     key = ("plan", str(coord.device))
     sized = _WS.get(key + (n, octree._n_buckets))
     if sized is None:
-        q = C.c_size_t(0)
-        _lib.check(lib.shine_plan_batch(t.handle, C.byref(cfg), None, n, None, None, None, 0, None, C.byref(q),
-                                        stream), "shine_plan_batch")
+        sized = _lib.workspace_bytes(lib.shine_plan_batch, t.handle, C.byref(cfg), None, n, None, None, None, 0, _lib.WS,
+                                     _lib.WS_BYTES, stream)
         _WS.clear_sizes(key)
-        sized = _WS[key + (n, octree._n_buckets)] = int(q.value)
+        _WS[key + (n, octree._n_buckets)] = sized
     ent = _WS.get(key)
     if ent is None or ent.numel() < sized:
         ent = _WS[key] = torch.empty(max(sized + sized // 4, 1), dtype=torch.uint8, device=coord.device)
@@ -223,11 +220,10 @@ class TouchedRowReducer(GradReducer):
         rows = [int(p.shape[0]) - 1 for p in feats]
         st = getattr(self, "_dev_state", None)
         if st is None or st["rows"] != rows or st["dev"] != dev:
-            need = C.c_size_t(0)
-            _lib.check(lib.shine_touched_index(L, None, _lib.i64_array(rows), None, None, None, C.byref(need), stream),
-                       "shine_touched_index")
-            st = dict(rows=rows, dev=dev, ws=torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=dev),
-                      ws_bytes=int(need.value), idx=[torch.empty(max(r, 1), dtype=torch.int32, device=dev) for r in rows],
+            need = _lib.workspace_bytes(lib.shine_touched_index, L, None, _lib.i64_array(rows), None, None, _lib.WS, _lib.WS_BYTES,
+                                        stream)
+            st = dict(rows=rows, dev=dev, ws=_lib.workspace(need, dev), ws_bytes=need,
+                      idx=[torch.empty(max(r, 1), dtype=torch.int32, device=dev) for r in rows],
                       counts=torch.zeros(L, dtype=torch.int64, device=dev), rows_arr=_lib.i64_array(rows))
             self._dev_state = st
         need = C.c_size_t(st["ws_bytes"])
@@ -377,10 +373,9 @@ class RowGatherReducer(GradReducer):
             lib = _lib.lib()
             stream = _lib.current_stream_handle()
             if self._ws is None:
-                need = C.c_size_t(0)
-                _lib.check(lib.shine_rows_pack(None, self.n_rows, None, 0, None, 0, self.tail_n, self.capacity, None, None,
-                                               C.byref(need), stream), "shine_rows_pack")
-                self._ws = (torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=dev), int(need.value))
+                need = _lib.workspace_bytes(lib.shine_rows_pack, None, self.n_rows, None, 0, None, 0, self.tail_n, self.capacity, None,
+                                            _lib.WS, _lib.WS_BYTES, stream)
+                self._ws = (_lib.workspace(need, dev), need)
             need = C.c_size_t(self._ws[1])
             _lib.check(lib.shine_rows_pack(self._flags_flat.data_ptr(), self.n_rows, _lib.i64_array(self._keep), len(self._keep),
                                            flat.data_ptr(), tail_off, self.tail_n, self.capacity, msg.data_ptr(),

@@ -91,10 +91,6 @@ def _faces(x, device):
     return t.contiguous()
 
 
-def _ws(nbytes, device):
-    return _torch().empty(max(int(nbytes), 1), dtype=_torch().uint8, device=device)
-
-
 def _d3(v):
     return (C.c_double * 3)(*[float(x) for x in v])
 
@@ -118,13 +114,9 @@ def bounds(points):
     if pts.shape[0] == 0:
         raise ValueError("bounds of an empty cloud")
     torch = _torch()
-    lib, st = _lib.lib(), _stream()
-    need = C.c_size_t(0)
-    _lib.check(lib.shine_eval_bounds(None, pts.shape[0], None, C.byref(need), None, st), "shine_eval_bounds")
-    ws = _ws(need.value, pts.device)
     out = torch.empty(6, dtype=torch.float64, device=pts.device)
-    _lib.check(lib.shine_eval_bounds(pts.data_ptr(), pts.shape[0], ws.data_ptr(), C.byref(need), out.data_ptr(), st),
-               "shine_eval_bounds")
+    _lib.call_with_workspace(_lib.lib().shine_eval_bounds, pts.device, pts.data_ptr(), pts.shape[0], _lib.WS, _lib.WS_BYTES,
+                             out.data_ptr(), _stream())
     b = out.cpu().numpy()
     return b[:3].copy(), b[3:].copy()
 
@@ -167,15 +159,9 @@ def sample_points_uniformly(verts, faces, n, seed=0, uniforms=None, return_trian
     out = torch.empty((n, 3), dtype=torch.float64, device=v.device)
     tri = torch.empty(n, dtype=torch.int32, device=v.device) if return_triangles else None
     if n:
-        lib, st = _lib.lib(), _stream()
-        need = C.c_size_t(0)
-        _lib.check(lib.shine_eval_sample_mesh(None, v.shape[0], None, f.shape[0], n, 0, None, None, C.byref(need), None, None, st),
-                   "shine_eval_sample_mesh")
-        ws = _ws(need.value, v.device)
-        _lib.check(lib.shine_eval_sample_mesh(v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0], n, int(seed) & (2 ** 64 - 1),
-                                              u.data_ptr() if u is not None else None, ws.data_ptr(), C.byref(need),
-                                              out.data_ptr(), tri.data_ptr() if tri is not None else None, st),
-                   "shine_eval_sample_mesh")
+        _lib.call_with_workspace(_lib.lib().shine_eval_sample_mesh, v.device, v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0], n,
+                                 int(seed) & (2 ** 64 - 1), u.data_ptr() if u is not None else None, _lib.WS, _lib.WS_BYTES,
+                                 out.data_ptr(), tri.data_ptr() if tri is not None else None, _stream())
     return (out, tri) if return_triangles else out
 
 
@@ -222,26 +208,20 @@ def voxel_down_sample(points, voxel, return_keys=False, attrs=None):
     _check_axis_bits(lo, hi, origin, voxel, "voxel_down_sample")
     pts = _points(points)
     lib, st = _lib.lib(), _stream()
-    need = C.c_size_t(0)
     out = torch.empty((n, 3), dtype=torch.float64, device=pts.device)
     keys = torch.empty(n, dtype=torch.int64, device=pts.device) if return_keys else None
+    keys_ptr = keys.data_ptr() if keys is not None else None
     m = C.c_int64(0)
     if att is None:
-        _lib.check(lib.shine_eval_voxel_down(None, n, None, voxel, None, C.byref(need), None, None, None, st), "shine_eval_voxel_down")
-        ws = _ws(need.value, pts.device)
-        _lib.check(lib.shine_eval_voxel_down(pts.data_ptr(), n, _d3(origin), voxel, ws.data_ptr(), C.byref(need), out.data_ptr(),
-                                             keys.data_ptr() if keys is not None else None, C.byref(m), st), "shine_eval_voxel_down")
+        _lib.call_with_workspace(lib.shine_eval_voxel_down, pts.device, pts.data_ptr(), n, _d3(origin), voxel, _lib.WS,
+                                 _lib.WS_BYTES, out.data_ptr(), keys_ptr, C.byref(m), st)
         aout = None
     else:
         att = att.to(device=pts.device, dtype=torch.float64).contiguous()
         a = int(att.shape[1])
-        _lib.check(lib.shine_voxel_down_attr(None, None, a, n, None, voxel, None, C.byref(need), None, None, None, None, st),
-                   "shine_voxel_down_attr")
-        ws = _ws(need.value, pts.device)
         aout = torch.empty((n, a), dtype=torch.float64, device=pts.device)
-        _lib.check(lib.shine_voxel_down_attr(pts.data_ptr(), att.data_ptr(), a, n, _d3(origin), voxel, ws.data_ptr(), C.byref(need),
-                                             out.data_ptr(), aout.data_ptr(), keys.data_ptr() if keys is not None else None,
-                                             C.byref(m), st), "shine_voxel_down_attr")
+        _lib.call_with_workspace(lib.shine_voxel_down_attr, pts.device, pts.data_ptr(), att.data_ptr(), a, n, _d3(origin), voxel,
+                                 _lib.WS, _lib.WS_BYTES, out.data_ptr(), aout.data_ptr(), keys_ptr, C.byref(m), st)
         aout = aout[:m.value].clone()
     return result(out[:m.value].clone(), keys[:m.value].clone() if keys is not None else None, aout)
 
@@ -271,13 +251,9 @@ class NNGrid:
         self._build()
 
     def _count(self, cell):
-        lib, st = _lib.lib(), _stream()
-        need = C.c_size_t(0)
-        _lib.check(lib.shine_eval_grid_count(None, self.n, None, cell, None, C.byref(need), None, st), "shine_eval_grid_count")
-        ws = _ws(need.value, self.ref.device)
         counts = (C.c_int64 * 2)()
-        _lib.check(lib.shine_eval_grid_count(self.ref.data_ptr(), self.n, _d3(self.lo), cell, ws.data_ptr(), C.byref(need), counts,
-                                             st), "shine_eval_grid_count")
+        ws, need = _lib.call_with_workspace(_lib.lib().shine_eval_grid_count, self.ref.device, self.ref.data_ptr(), self.n,
+                                            _d3(self.lo), cell, _lib.WS, _lib.WS_BYTES, counts, _stream())
         return ws, need.value, int(counts[0]), int(counts[1])
 
     def _estimate_spacing(self, extent, floor_cell):
@@ -289,15 +265,12 @@ class NNGrid:
         return h0 / math.sqrt(self.n / max(n_fine, 1))
 
     def _build(self):
-        lib, st = _lib.lib(), _stream()
         self.cells_per_axis = _check_axis_bits(self.lo, self.hi, self.lo, self.cell, "nn_correspondence")
         ws, ws_bytes, self.n_fine, self.n_coarse = self._count(self.cell)
-        need = C.c_size_t(0)
-        _lib.check(lib.shine_eval_grid_emit(None, self.n, None, 0, self.n_fine, self.n_coarse, None, C.byref(need), st),
-                   "shine_eval_grid_emit")
-        self.grid = _ws(need.value, self.ref.device)
-        _lib.check(lib.shine_eval_grid_emit(self.ref.data_ptr(), self.n, ws.data_ptr(), ws_bytes, self.n_fine, self.n_coarse,
-                                            self.grid.data_ptr(), C.byref(need), st), "shine_eval_grid_emit")
+        # (the grid is a result, sized and refused like a workspace: the placeholders stand for `grid` and `grid_bytes`)
+        self.grid, _ = _lib.call_with_workspace(_lib.lib().shine_eval_grid_emit, self.ref.device, self.ref.data_ptr(), self.n,
+                                                ws.data_ptr(), ws_bytes, self.n_fine, self.n_coarse, _lib.WS, _lib.WS_BYTES,
+                                                _stream())
 
     @property
     def coarse_cell(self):
@@ -327,15 +300,10 @@ class NNGrid:
         keep = torch.empty(nq, dtype=torch.uint8, device=q.device)
         st_dev = torch.zeros(2, dtype=torch.int32, device=q.device) if stats else None
         if nq:
-            lib, st = _lib.lib(), _stream()
-            need = C.c_size_t(0)
-            args = (self.n, self.n_fine, self.n_coarse, _d3(self.lo), self.cell, (C.c_int64 * 3)(*[int(c) for c in self.cells_per_axis]))
-            _lib.check(lib.shine_eval_nn_search(None, *args, None, nq, truncation, None, C.byref(need), None, None, None, None, st),
-                       "shine_eval_nn_search")
-            ws = _ws(need.value, q.device)
-            _lib.check(lib.shine_eval_nn_search(self.grid.data_ptr(), *args, q.data_ptr(), nq, truncation, ws.data_ptr(),
-                                                C.byref(need), idx.data_ptr(), dist.data_ptr(), keep.data_ptr(),
-                                                st_dev.data_ptr() if stats else None, st), "shine_eval_nn_search")
+            _lib.call_with_workspace(
+                _lib.lib().shine_eval_nn_search, q.device, self.grid.data_ptr(), self.n, self.n_fine, self.n_coarse, _d3(self.lo),
+                self.cell, (C.c_int64 * 3)(*[int(c) for c in self.cells_per_axis]), q.data_ptr(), nq, truncation, _lib.WS,
+                _lib.WS_BYTES, idx.data_ptr(), dist.data_ptr(), keep.data_ptr(), st_dev.data_ptr() if stats else None, _stream())
         keep = keep.bool()
         if stats:
             mc, mf = (int(v) for v in st_dev.cpu())
@@ -373,15 +341,10 @@ def distance_sums(dist_p, dist_r, threshold):
     torch = _torch()
     dp = dist_p.detach().double().contiguous()
     dr = dist_r.detach().to(dp.device).double().contiguous()
-    lib, st = _lib.lib(), _stream()
-    need = C.c_size_t(0)
-    _lib.check(lib.shine_eval_metrics(None, dp.numel(), None, dr.numel(), float(threshold), None, C.byref(need), None, st),
-               "shine_eval_metrics")
-    ws = _ws(need.value, dp.device)
     out = torch.empty(8, dtype=torch.float64, device=dp.device)
-    _lib.check(lib.shine_eval_metrics(dp.data_ptr() if dp.numel() else None, dp.numel(), dr.data_ptr() if dr.numel() else None,
-                                      dr.numel(), float(threshold), ws.data_ptr(), C.byref(need), out.data_ptr(), st),
-               "shine_eval_metrics")
+    _lib.call_with_workspace(_lib.lib().shine_eval_metrics, dp.device, dp.data_ptr() if dp.numel() else None, dp.numel(),
+                             dr.data_ptr() if dr.numel() else None, dr.numel(), float(threshold), _lib.WS, _lib.WS_BYTES,
+                             out.data_ptr(), _stream())
     return out.cpu().numpy()
 
 

@@ -125,7 +125,7 @@ def cal_feature_importance(data, octree, mlp, sigma, bs, down_rate=1, loss_reduc
                                                 C.byref(group), C.byref(scratch_bytes), C.byref(ws_bytes)),
                "shine_importance_sweep_sizes")
     scratch = _zero_scratch(dev, scratch_bytes.value)
-    ws = torch.empty(ws_bytes.value, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(ws_bytes.value, dev)
     try:
         _lib.check(
             lib.shine_importance_sweep(

@@ -95,10 +95,6 @@ def ensure_grid_fits(shape, with_mask=True, per_point_extra=0, free_bytes=None, 
     return need
 
 
-def _ws(nbytes, device):
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
-
-
 def marching_cubes(sdf, mask=None, level=0.0):
     """Marching cubes of a device grid `sdf [X,Y,Z]` (f32, C order) with an optional mask of the same shape (cube (x,y,z) is
     processed iff mask[x,y,z]); rules in DESIGN.md "Meshing".  Returns (verts [V,3] f32 index units (x, y, z), faces [F,3]
@@ -113,12 +109,10 @@ def marching_cubes(sdf, mask=None, level=0.0):
     X, Y, Z = (int(v) for v in sdf.shape)
     lib, st = _lib.lib(), _stream()
     mp = mask.data_ptr() if mask is not None else None
-    need = C.c_size_t(0)
-    _lib.check(lib.shine_mc_count(sdf.data_ptr(), mp, X, Y, Z, float(level), None, C.byref(need), None, st), "shine_mc_count")
-    ws = _ws(need.value, sdf.device)
     counts = (C.c_int64 * 2)()
-    rc = lib.shine_mc_count(sdf.data_ptr(), mp, X, Y, Z, float(level), ws.data_ptr(), C.byref(need), counts, st)
-    _lib.check(rc, "shine_mc_count (%dx%dx%d grid: %d vertices, %d faces)" % (X, Y, Z, counts[0], counts[1]))
+    ws, need = _lib.call_with_workspace(
+        lib.shine_mc_count, sdf.device, sdf.data_ptr(), mp, X, Y, Z, float(level), _lib.WS, _lib.WS_BYTES, counts, st,
+        what=lambda: "shine_mc_count (%dx%dx%d grid: %d vertices, %d faces)" % (X, Y, Z, counts[0], counts[1]))
     nv, nf = int(counts[0]), int(counts[1])
     verts = torch.empty((nv, 3), dtype=torch.float32, device=sdf.device)
     faces = torch.empty((nf, 3), dtype=torch.int32, device=sdf.device)
@@ -158,29 +152,25 @@ def marching_cubes_sparse(values, mask, origins, shape, level=0.0):
     lib, st = _lib.lib(), _stream()
     vp, mp = (values.data_ptr() if n else None), (mask.data_ptr() if mask is not None and n else None)
     op = org.ctypes.data_as(C.POINTER(C.c_int64))
-    need = C.c_size_t(0)
-    _lib.check(lib.shine_mc_sparse_count(vp, mp, op, n, B, X, Y, Z, float(level), None, C.byref(need), None, st),
-               "shine_mc_sparse_count")
-    if n == 0:
-        return verts, faces
-    ws = _ws(need.value, dev)
     counts = (C.c_int64 * 2)()
-    rc = lib.shine_mc_sparse_count(vp, mp, op, n, B, X, Y, Z, float(level), ws.data_ptr(), C.byref(need), counts, st)
-    _lib.check(rc, "shine_mc_sparse_count (%d bricks of %d^3 in %dx%dx%d: %d vertex records, %d faces)"
-               % (n, B, X, Y, Z, counts[0], counts[1]))
+    count_args = (vp, mp, op, n, B, X, Y, Z, float(level), _lib.WS, _lib.WS_BYTES, counts, st)
+    if n == 0:
+        _lib.workspace_bytes(lib.shine_mc_sparse_count, *count_args)  # (the query checks the arguments)
+        return verts, faces
+    ws, need = _lib.call_with_workspace(
+        lib.shine_mc_sparse_count, dev, *count_args,
+        what=lambda: "shine_mc_sparse_count (%d bricks of %d^3 in %dx%dx%d: %d vertex records, %d faces)"
+        % (n, B, X, Y, Z, counts[0], counts[1]))
     nr, nf = int(counts[0]), int(counts[1])
     if nr == 0 and nf == 0:
         return verts, faces
-    sneed = C.c_size_t(0)
     nv = C.c_int64(0)
-    _lib.check(lib.shine_mc_sparse_emit(vp, mp, n, B, X, Y, Z, float(level), ws.data_ptr(), need.value, nr, nf, None,
-                                        C.byref(sneed), None, None, C.byref(nv), st), "shine_mc_sparse_emit")
-    scratch = _ws(sneed.value, dev)
     verts = torch.empty((nr, 3), dtype=torch.float32, device=dev)
     faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
-    _lib.check(lib.shine_mc_sparse_emit(vp, mp, n, B, X, Y, Z, float(level), ws.data_ptr(), need.value, nr, nf, scratch.data_ptr(),
-                                        C.byref(sneed), verts.data_ptr(), faces.data_ptr(), C.byref(nv), st),
-               "shine_mc_sparse_emit")
+    # (the placeholders stand for the scratch and its size: the same convention)
+    scratch, _ = _lib.call_with_workspace(lib.shine_mc_sparse_emit, dev, vp, mp, n, B, X, Y, Z, float(level), ws.data_ptr(),
+                                          need.value, nr, nf, _lib.WS, _lib.WS_BYTES, verts.data_ptr(), faces.data_ptr(),
+                                          C.byref(nv), st)
     del scratch, ws
     # (a vertex on a brick face has one record per brick that uses it: V <= records; the copy lets the larger buffer go)
     return (verts if nv.value == nr else verts[:nv.value].clone()), faces
@@ -355,14 +345,12 @@ def vertex_normals_device(verts, faces):
     faces = faces.detach().to(torch.int32).contiguous()
     nv, nf = verts.shape[0], faces.shape[0]
     out = torch.zeros((nv, 3), dtype=torch.float64, device=verts.device)
-    lib, st = _lib.lib(), _stream()
-    need = C.c_size_t(0)
-    _lib.check(lib.shine_mesh_vertex_normals(None, nv, None, nf, None, C.byref(need), None, st), "shine_mesh_vertex_normals")
+    fn = _lib.lib().shine_mesh_vertex_normals
+    args = (verts.data_ptr(), nv, faces.data_ptr() if nf else None, nf, _lib.WS, _lib.WS_BYTES, out.data_ptr(), _stream())
     if nv == 0:
-        return out
-    ws = _ws(need.value, verts.device)
-    _lib.check(lib.shine_mesh_vertex_normals(verts.data_ptr(), nv, faces.data_ptr() if nf else None, nf, ws.data_ptr(),
-                                             C.byref(need), out.data_ptr(), st), "shine_mesh_vertex_normals")
+        _lib.workspace_bytes(fn, *args)  # (the query checks the arguments)
+    else:
+        _lib.call_with_workspace(fn, verts.device, *args)
     return out
 
 
@@ -372,18 +360,16 @@ def cluster_filter_device(faces, min_tri, return_clusters=False):
     numbering: clusters in the order of their first triangle)."""
     faces = faces.detach().to(torch.int32).contiguous()
     nf = faces.shape[0]
-    lib, st = _lib.lib(), _stream()
-    need = C.c_size_t(0)
-    _lib.check(lib.shine_mesh_cluster_filter(None, nf, int(min_tri), None, C.byref(need), None, None, None, st),
-               "shine_mesh_cluster_filter")
     out = torch.empty((nf, 3), dtype=torch.int32, device=faces.device)
     clusters = torch.empty(nf, dtype=torch.int32, device=faces.device) if return_clusters else None
     kept = C.c_int64(0)
-    if nf:
-        ws = _ws(need.value, faces.device)
-        _lib.check(lib.shine_mesh_cluster_filter(faces.data_ptr(), nf, int(min_tri), ws.data_ptr(), C.byref(need),
-                                                 clusters.data_ptr() if clusters is not None else None, out.data_ptr(),
-                                                 C.byref(kept), st), "shine_mesh_cluster_filter")
+    fn = _lib.lib().shine_mesh_cluster_filter
+    args = (faces.data_ptr(), nf, int(min_tri), _lib.WS, _lib.WS_BYTES, clusters.data_ptr() if clusters is not None else None,
+            out.data_ptr(), C.byref(kept), _stream())
+    if nf == 0:
+        _lib.workspace_bytes(fn, *args)  # (the query checks the arguments)
+    else:
+        _lib.call_with_workspace(fn, faces.device, *args)
     out = out[:kept.value]
     return (out, clusters) if return_clusters else out
 

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .dataset import LiDARDataset, _rows_to_pose, _ws, csv_odom_to_transforms, natural_key
+from .dataset import LiDARDataset, _rows_to_pose, csv_odom_to_transforms, natural_key
 
 FLIP = np.diag([1.0, -1.0, -1.0, 1.0])  # the converter's extrinsic for PrimeSense / Neural-RGBD frames (:42,55)
 FILTER_OFF = (-np.inf, np.inf, 0.0, np.inf)  # min_z, max_z, min_range, pc_radius that keep every valid pixel
@@ -172,16 +172,13 @@ def unproject_depth(depth, intrinsics, cam_to_sensor=None, max_depth_m=5.0, filt
     idx = torch.empty((n,), dtype=torch.int32, device=img.device) if return_index else None
     if n == 0:
         return (pts, idx) if return_index else pts
-    lib, st = _lib.lib(), _lib.current_stream_handle()
     pitch = int(img.stride(0)) if h > 1 else w
-    args = (int(is_f32), w, h, pitch, intrinsics.fx, intrinsics.fy, intrinsics.cx, intrinsics.cy, intrinsics.depth_scale,
-            float(max_depth_m), m16, min_z, max_z, min_range, pc_radius)
-    need = C.c_size_t(0)
-    _lib.check(lib.shine_depth_unproject(None, *args, None, C.byref(need), None, None, None, st), "shine_depth_unproject")
-    ws = _ws(need.value, img.device)
     kept = C.c_int64(0)
-    _lib.check(lib.shine_depth_unproject(img.data_ptr(), *args, ws.data_ptr(), C.byref(need), pts.data_ptr(),
-                                         idx.data_ptr() if return_index else None, C.byref(kept), st), "shine_depth_unproject")
+    _lib.call_with_workspace(
+        _lib.lib().shine_depth_unproject, img.device, img.data_ptr(), int(is_f32), w, h, pitch, intrinsics.fx, intrinsics.fy,
+        intrinsics.cx, intrinsics.cy, intrinsics.depth_scale, float(max_depth_m), m16, min_z, max_z, min_range, pc_radius,
+        _lib.WS, _lib.WS_BYTES, pts.data_ptr(), idx.data_ptr() if return_index else None, C.byref(kept),
+        _lib.current_stream_handle())
     k = int(kept.value)
     return (pts[:k], idx[:k]) if return_index else pts[:k]
 

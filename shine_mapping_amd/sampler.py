@@ -36,16 +36,11 @@ def importance_chunks(perm, n, bs, down_rate=1):
 
     n, bs, down_rate = int(n), int(bs), int(down_rate)
     n_chunks = math.ceil(n / (bs * down_rate))
-    lib = _lib.lib()
     perm = perm.to(torch.int32).contiguous()
     idx = torch.empty(n, dtype=torch.int32, device=perm.device)
     begin = (C.c_int64 * (n_chunks + 1))()
-    need = C.c_size_t()
-    _lib.check(lib.shine_importance_chunks(None, n, bs, down_rate, None, None, n_chunks, None, C.byref(need), None),
-               "shine_importance_chunks")
-    ws = torch.empty(need.value, dtype=torch.uint8, device=perm.device)
-    _lib.check(lib.shine_importance_chunks(perm.data_ptr(), n, bs, down_rate, idx.data_ptr(), begin, n_chunks, ws.data_ptr(),
-                                           C.byref(need), _lib.current_stream_handle()), "shine_importance_chunks")
+    _lib.call_with_workspace(_lib.lib().shine_importance_chunks, perm.device, perm.data_ptr(), n, bs, down_rate, idx.data_ptr(),
+                             begin, n_chunks, _lib.WS, _lib.WS_BYTES, _lib.current_stream_handle())
     largest = max((begin[c + 1] - begin[c] for c in range(n_chunks)), default=0)
     return idx, begin, n_chunks, largest
 
@@ -237,14 +232,8 @@ class SortedPool:
         # carried the first pass of exactly this draw (ops marks the pool when it launches one); otherwise both passes run
         pass1_done = bool(pass1_done and graph_safe and self._rider_for == nd)
         self._rider_for = None
-        ws = self._ws.get((nd, self.size))
+        ws = self._draw_workspace(nd)
         none13 = (None, None)
-        if ws is None:
-            need = C.c_size_t(0)
-            _lib.check(lib.shine_sample_sorted(self.size, nd, self.seed, 0, None, None, 0, *none13, None, C.byref(need),
-                                               stream), "shine_sample_sorted")
-            ws = (torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=dev), nd, int(need.value))
-            self._ws[(nd, self.size)] = ws
         idx = out if out is not None else torch.empty(n, dtype=torch.int32, device=dev)
         need = C.c_size_t(ws[2])
         zero_args = (zero.data_ptr() if zero is not None else None,
@@ -280,6 +269,17 @@ class SortedPool:
             self.draws += 1
         return idx
 
+    def _draw_workspace(self, nd):
+        """(buffer, nd, bytes) of a draw of `nd` from this pool: allocated once per (nd, pool size), kept as long as the pool —
+        captured graphs and shine_next_draw records hold its address"""
+        ws = self._ws.get((nd, self.size))
+        if ws is None:
+            need = _lib.workspace_bytes(_lib.lib().shine_sample_sorted, self.size, nd, self.seed, 0, None, None, 0, None, None,
+                                        _lib.WS, _lib.WS_BYTES, _lib.current_stream_handle())
+            ws = (_lib.workspace(need, self.device), nd, need)
+            self._ws[(nd, self.size)] = ws
+        return ws
+
     def draw_chain(self, n, idx, buckets=None, surf=False):
         """DrawChain(self, ...): every step's own two launches draw the next batch (and clear the next step's bucket)"""
         return DrawChain(self, n, idx, buckets=buckets, surf=surf)
@@ -293,13 +293,7 @@ class SortedPool:
         Keeps the device stream state of graph_safe draws."""
         dev = self.device
         nsp = int(n_global) if n_global is not None else int(n)
-        ws = self._ws.get((nsp, self.size))
-        if ws is None:
-            need = C.c_size_t(0)
-            _lib.check(_lib.lib().shine_sample_sorted(self.size, nsp, self.seed, 0, None, None, 0, None, None, None,
-                                                      C.byref(need), _lib.current_stream_handle()), "shine_sample_sorted")
-            ws = (torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=dev), nsp, int(need.value))
-            self._ws[(nsp, self.size)] = ws
+        ws = self._draw_workspace(nsp)
         if out is None:
             out = torch.empty(int(n), dtype=torch.int32, device=dev)  # (the step's rider does not write indices)
         if self._stream_state is None:

@@ -50,7 +50,7 @@ def entry_points_alone(drive, frame_id, reps):
     """each entry point on the cloud process_frame hands it: normals on the cropped frame, SOR and k-NN on the down-sampled one"""
     from shine_mapping_amd import _lib, synth
     from shine_mapping_amd import evaluation as ev
-    from shine_mapping_amd.dataset import LiDARDataset, _frame_grid, _ws, frame_filter
+    from shine_mapping_amd.dataset import LiDARDataset, _frame_grid, frame_filter
 
     cfg = synth.dataset_config("kitti", drive, **PARAMS)
     ds = LiDARDataset(cfg, None)
@@ -74,7 +74,7 @@ def entry_points_alone(drive, frame_id, reps):
     n = grid.n
     nrm = torch.empty((n, 3), dtype=torch.float64, device="cuda")
     lib.shine_frame_normals(None, *args[1:], cfg.normal_radius_m, cfg.normal_max_nn, None, None, C.byref(need), None, st)
-    ws = _ws(need.value, nrm.device)
+    ws = _lib.workspace(need.value, nrm.device)
     vp = (C.c_double * 3)(0.0, 0.0, 0.0)
     out["shine_frame_normals_ms"] = timed(lambda: _lib.check(lib.shine_frame_normals(
         *args, cfg.normal_radius_m, cfg.normal_max_nn, vp, ws.data_ptr(), C.byref(need), nrm.data_ptr(), st), "shine_frame_normals"))
@@ -85,7 +85,7 @@ def entry_points_alone(drive, frame_id, reps):
     avg = torch.empty(n, dtype=torch.float64, device="cuda")
     stats = torch.empty(2, dtype=torch.float64, device="cuda")
     lib.shine_sor_mean_dist(None, *args[1:], cfg.sor_nn, None, C.byref(need), None, None, None, st)
-    ws = _ws(need.value, avg.device)
+    ws = _lib.workspace(need.value, avg.device)
     out["shine_sor_mean_dist_ms"] = timed(lambda: _lib.check(lib.shine_sor_mean_dist(
         *args, cfg.sor_nn, ws.data_ptr(), C.byref(need), avg.data_ptr(), stats.data_ptr(), C.byref(rounds), st), "shine_sor_mean_dist"))
     out["shine_sor_mean_dist_launches"] = int(rounds.value)
