@@ -250,9 +250,12 @@ int shine_bce_loss(const float* pred, const float* sdf_label, const float* weigh
                    int32_t reduction_sum, float* loss_out, float* dpred_out, void* stream);
 
 /* ---- Tier A (strict drop-in): the other training objectives of the yamls, each loss and its derivative in ONE launch.
- *      workspace: SHINE_LOSS_WORKSPACE_BYTES of 8-byte aligned device memory, ZERO when first used; every call leaves it zero
- *      again.  Calls that share a workspace must not overlap (one workspace per stream).  The loss is summed in fp64 partials
- *      that the last workgroup adds up in a fixed order: repeated calls give the same bits at any size.
+ *      TICKET WORKSPACES (SHINE_LOSS_WORKSPACE_BYTES here, SHINE_SEM_WORKSPACE_BYTES below): the workgroups of a launch leave
+ *      partial sums there and count their arrivals; the last to arrive adds the partials up in a fixed order, so repeated calls
+ *      give the same bits at any size.  The memory is ZERO before the first call that uses it; every call leaves its counters
+ *      zero again (the partials are overwritten before they are read).  Calls that share a workspace must not overlap (one
+ *      workspace per stream).
+ *      workspace: SHINE_LOSS_WORKSPACE_BYTES of 8-byte aligned device memory.  The loss is summed in fp64 partials.
  *
  *      sdf_diff_loss (utils/loss.py:6-14), main_loss_type sdf_l1 / sdf_l2: diff_m = (pred - sdf_label) / scale,
  *      *loss_out = sum(weight * diff_m^2) / n (l2_loss != 0) or sum(weight * |diff_m|) / n; dpred_out [n] (or NULL) =
@@ -277,8 +280,7 @@ int shine_ray_render_loss(const float* x, const float* y, const float* d_meas, i
  *      the argmax of logp (the first index wins ties); either may be NULL, not both.
  *      _backward: given grad_logp [n, n_class] = d loss / d logp and the saved logp: grad_feat_out [n, 8] (overwritten) or NULL;
  *      grad_mlp: NULL (a frozen decoder) or 6 outputs shaped like mlp, OVERWRITTEN with bit-reproducible sums.  workspace:
- *      SHINE_SEM_WORKSPACE_BYTES of 256-byte aligned device memory, zero when first used, left zero again (only read with
- *      grad_mlp); calls sharing one must not overlap.
+ *      SHINE_SEM_WORKSPACE_BYTES of 256-byte aligned device memory, a ticket workspace (above; only read with grad_mlp).
  *      _query_labels: Mesher.query_points(query_sem=True) (utils/mesher.py:33-108): label_out [n] = sem_label(query_feature(coord,
  *      faster=True)), the interpolation of shine_query_points, in one launch. */
 #define SHINE_SEM_MAX_CLASSES 32
@@ -305,8 +307,8 @@ int shine_sem_query_labels(const shine_tables* t, const shine_step_config* cfg, 
  *      trash row included (NULL array / NULL entries: no gradient for that level).  mlp / n_class as for shine_sem_forward.
  *      grad_mlp: NULL (a frozen head: only feature grads are written) or 6 tensors shaped like mlp that the sums are ADDED to by
  *      the workgroup that finishes them; those sums and *sem_loss_out (float, the UNWEIGHTED mean) are bit-identical from call to
- *      call.  workspace: SHINE_SEM_WORKSPACE_BYTES as for shine_sem_backward (always needed: the loss is summed there), zero when
- *      first used, left zero: the launch can be captured into a HIP graph.  n == 0 launches nothing and writes a loss of 0.
+ *      call.  workspace: SHINE_SEM_WORKSPACE_BYTES as for shine_sem_backward (always needed: the loss is summed there); no
+ *      call clears it, so the launch can be captured into a HIP graph.  n == 0 launches nothing and writes a loss of 0.
  *      SHINE_E_INVALID before anything touches the device: a null table handle, coord_stride other than 3 or 8, decimation < 1,
  *      n_class outside 1..SHINE_SEM_MAX_CLASSES, null arguments, more than 4 featured levels. */
 int shine_sem_train_step(const shine_tables* t, const shine_step_config* cfg, const float* coord, int32_t coord_stride,

@@ -315,6 +315,30 @@ def workspace(nbytes, device):
     return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
 
 
+def zeroed_workspace(nbytes, device):
+    """`nbytes` of zeroed device memory for an entry point that sums across workgroups inside its launch (SHINE_LOSS_ /
+    SHINE_SEM_WORKSPACE_BYTES): zero before the first call, left zero by every call (include/shine_hip.h)"""
+    import torch
+
+    return torch.zeros(nbytes // 8, dtype=torch.float64, device=device)
+
+
+_TICKET_WORKSPACES = {}  # (device index, stream, bytes) -> its zeroed workspace
+
+
+def ticket_workspace(device, nbytes):
+    """the zeroed workspace of `nbytes` for the current stream of `device` (launches on one stream never overlap)"""
+    import torch
+
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    key = (idx, current_stream_handle() if idx == torch.cuda.current_device() else torch.cuda.current_stream(idx).cuda_stream,
+           nbytes)
+    ws = _TICKET_WORKSPACES.get(key)
+    if ws is None:
+        ws = _TICKET_WORKSPACES[key] = zeroed_workspace(nbytes, torch.device("cuda", idx))
+    return ws
+
+
 def _call_ws(fn, args, ws_ptr, need, what=None):
     rc = fn(*[ws_ptr if a is WS else C.byref(need) if a is WS_BYTES else a for a in args])
     if rc != 0:

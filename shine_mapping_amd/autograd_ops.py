@@ -581,18 +581,11 @@ class ShineTrainStep(torch.autograd.Function):
 
 SEM_MAX_CLASSES = 32  # include/shine_hip.h SHINE_SEM_MAX_CLASSES
 SEM_WORKSPACE_BYTES = 2621440  # SHINE_SEM_WORKSPACE_BYTES
-_SEM_WORKSPACES = {}  # (device index, stream) -> the zeroed workspace of shine_sem_backward
 
 
 def sem_workspace(device):
-    """SHINE_SEM_WORKSPACE_BYTES of zeroed device memory for the current stream of `device` (the backward leaves its ticket
-    counters zero again; launches on one stream never overlap)"""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    key = (idx, _lib.current_stream_handle() if idx == torch.cuda.current_device() else torch.cuda.current_stream(idx).cuda_stream)
-    ws = _SEM_WORKSPACES.get(key)
-    if ws is None:
-        ws = _SEM_WORKSPACES[key] = torch.zeros(SEM_WORKSPACE_BYTES // 8, dtype=torch.float64, device=torch.device("cuda", idx))
-    return ws
+    """the workspace of shine_sem_backward / shine_sem_train_step for the current stream of `device`"""
+    return _lib.ticket_workspace(device, SEM_WORKSPACE_BYTES)
 
 
 def sem_forward(feat, mlp, want_logp=True, want_label=False):

@@ -20,7 +20,8 @@
 //                       assignment, so pruning never hides the exact nearest point; distances are computed from the
 //                       original fp64 coordinates.
 //   metrics             one launch: the sums, sums of squares and below-threshold counts of the two distance arrays (fixed
-//                       partition into blocks, the last block to finish adds the partials in block order).
+//                       partition into blocks, the last block to arrive — shine_arrive.hpp — adds the partials in block order).
+#include "shine_arrive.hpp"
 #include "shine_eval_grid.hpp"
 
 namespace {
@@ -418,7 +419,7 @@ __global__ __launch_bounds__(T) void k_metrics(const double* __restrict__ dp, lo
                                                long long nr, double threshold, double* __restrict__ part,
                                                unsigned int* __restrict__ done, double* __restrict__ out) {
   __shared__ MetricShared sm;
-  __shared__ bool is_last;
+  __shared__ unsigned is_last;
   double acc[6] = {0, 0, 0, 0, 0, 0};  // sum p, sum p^2, count p < thr, sum r, sum r^2, count r < thr
   for (long long i = (long long)blockIdx.x * T + threadIdx.x; i < np; i += (long long)gridDim.x * T) {
     const double d = dp[i];
@@ -443,19 +444,10 @@ __global__ __launch_bounds__(T) void k_metrics(const double* __restrict__ dp, lo
     for (int w = 0; w < T / 64; ++w) t += sm.v[threadIdx.x][w];
     part[6 * blockIdx.x + threadIdx.x] = t;
   }
-  __threadfence();
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned int ticket = __hip_atomic_fetch_add(done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    is_last = ticket == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (!is_last) return;
-  __threadfence();
+  if (!shine::arrive_last(done, gridDim.x, &is_last)) return;  // (the entry point clears `done` in front of every launch)
   if (threadIdx.x < 6) {
     double t = 0.0;
-    for (unsigned int b = 0; b < gridDim.x; ++b)
-      t += __hip_atomic_load(part + 6 * b + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (unsigned int b = 0; b < gridDim.x; ++b) t += part[6 * b + threadIdx.x];
     out[threadIdx.x] = t;
   }
   if (threadIdx.x == 6) out[6] = (double)np;

@@ -5,8 +5,9 @@
 //
 // Each is ONE launch that writes the loss and d loss / d (prediction) for an upstream gradient of 1 — what the torch composite
 // computes in a dozen small forward launches and more in its backward.  The grid-wide sum is deterministic: every workgroup
-// publishes an fp64 partial, the last one to arrive (agent-scope release / acquire on a ticket counter) adds them up in a fixed
-// order and resets the counter.  Repeated calls give the same bits.
+// publishes an fp64 partial, the last one to arrive (shine_arrive.hpp) adds them up in a fixed order and resets the counter.
+// Repeated calls give the same bits.
+#include "shine_arrive.hpp"
 #include "shine_internal.hpp"
 
 // The composite rounds every product and sum on its own; so do these kernels (no a * b + c contracted into one rounding).
@@ -42,26 +43,12 @@ __device__ void grid_sum(double acc, double scale, double* ws, float* loss_out, 
   if (threadIdx.x == 0) {
     double t = 0.0;
     for (int k = 0; k < NW; ++k) t += s_red[k];
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(ws + blockIdx.x), (unsigned long long)__double_as_longlong(t),
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned ticket = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_red[NW] = (ticket == gridDim.x - 1) ? 1.0 : 0.0;
+    ws[blockIdx.x] = t;
   }
-  __syncthreads();
-  if (s_red[NW] == 0.0) return;  // not the last workgroup
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  __syncthreads();
+  if (!arrive_last(cnt, gridDim.x, reinterpret_cast<unsigned*>(s_red + NW))) return;
   double v = 0.0;
-  for (int k = threadIdx.x; k < (int)gridDim.x; k += NT)
-    v += __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<unsigned long long*>(ws + k), __ATOMIC_RELAXED,
-                                                           __HIP_MEMORY_SCOPE_AGENT));
+  for (int k = threadIdx.x; k < (int)gridDim.x; k += NT) v += ws[k];
   v = wave_sum_d(v);
-  __syncthreads();  // (every wave has read s_red[NW])
   if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) {

@@ -1,7 +1,8 @@
 // shine_sem_head.hpp — the semantic head's device code shared by shine_semantic.hip (forward, backward, mesh labels) and
 // shine_sem_step.hip (the training loop's NLL launch): the weight pointers, the two hidden layers, the class layer with its
-// log-softmax, and the layout of the per-workgroup weight-grad partials that the ticket reduction sums.
+// log-softmax, the layout of the per-workgroup weight-grad partials and the two-level ticket sum over them (sem_grid_sum).
 #pragma once
+#include "shine_arrive.hpp"
 #include "shine_internal.hpp"
 
 namespace shine {
@@ -96,6 +97,67 @@ SEM_ROW_LOOP(2)
     if (c == 0 || lp > bv) bv = lp, best = c;  // (strictly greater: the first of equal values wins, torch.argmax's rule)
   }
   return best;
+}
+
+// where element k of a partial vector lands in the six gradient tensors (null: padding behind the C classes of Wc / bc)
+__device__ __forceinline__ float* sem_grad_slot(const SemGradPtrs& gp, int k, int C) {
+  if (k < P_B1) return gp.g[0] + (k - P_W1);
+  if (k < P_W2) return gp.g[1] + (k - P_B1);
+  if (k < P_B2) return gp.g[2] + (k - P_W2);
+  if (k < P_WC) return gp.g[3] + (k - P_B2);
+  if (k < P_BC) return k - P_WC < C * H ? gp.g[4] + (k - P_WC) : nullptr;
+  return k - P_BC < C ? gp.g[5] + (k - P_BC) : nullptr;
+}
+
+// The sum over the grid of the workgroups' partial vectors (STRIDE floats each at ws + kCounterBytes, stored by the caller), in
+// two ticket levels (shine_arrive.hpp): the last workgroup of each run of kGroup to arrive sums that run's partials in index
+// order, the last run to finish sums the run sums in index order and stores them to (ADD: adds them to) the six tensors of gp.
+// With STRIDE = P_N + 4 the float at P_N is summed along and *loss_out = its sum * loss_scale.  Only the columns of four floats
+// from c0 on are summed (a frozen head: c0 = P_N / 4, the loss alone).  Called by every thread of every workgroup; leaves the
+// counters zero.  verdict: one LDS word.
+template <int STRIDE, bool ADD>
+__device__ __forceinline__ void sem_grid_sum(unsigned char* ws, int c0, const SemGradPtrs& gp, int C, float* loss_out,
+                                             float loss_scale, unsigned* verdict) {
+  static_assert((STRIDE == P_N || STRIDE == P_N + 4) && P_N % 4 == 0 && P_B1 % 4 == 0 && P_BC % 4 == 0, "float4 walk");
+  unsigned* cnt = reinterpret_cast<unsigned*>(ws);
+  const float* part = reinterpret_cast<const float*>(ws + kCounterBytes);
+  float* runsum = reinterpret_cast<float*>(ws + kCounterBytes) + (size_t)kMaxBlocks * STRIDE;  // [kGroups][STRIDE]
+  const unsigned G = gridDim.x;
+  const unsigned grp = blockIdx.x / kGroup;
+  const unsigned g0 = grp * kGroup;
+  const unsigned gsz = (G - g0) < (unsigned)kGroup ? (G - g0) : (unsigned)kGroup;
+  const unsigned ngrp = (G + kGroup - 1) / kGroup;
+
+  if (!arrive_last(cnt + 1 + grp, gsz, verdict)) return;
+  for (int c = c0 + threadIdx.x; c < STRIDE / 4; c += kThreads) {
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (unsigned b = 0; b < gsz; ++b) {
+      const float4 v = *reinterpret_cast<const float4*>(part + (size_t)(g0 + b) * STRIDE + 4 * c);
+      s.x += v.x, s.y += v.y, s.z += v.z, s.w += v.w;
+    }
+    *reinterpret_cast<float4*>(runsum + (size_t)grp * STRIDE + 4 * c) = s;
+  }
+  if (threadIdx.x == 0) __hip_atomic_store(cnt + 1 + grp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next call
+
+  if (!arrive_last(cnt, ngrp, verdict)) return;
+  for (int c = c0 + threadIdx.x; c < STRIDE / 4; c += kThreads) {
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (unsigned r = 0; r < ngrp; ++r) {
+      const float4 v = *reinterpret_cast<const float4*>(runsum + (size_t)r * STRIDE + 4 * c);
+      s.x += v.x, s.y += v.y, s.z += v.z, s.w += v.w;
+    }
+    if (4 * c == P_N) {
+      loss_out[0] = s.x * loss_scale;
+      continue;
+    }
+    const float sv[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float* dst = sem_grad_slot(gp, 4 * c + e, C);
+      if (dst) *dst = ADD ? *dst + sv[e] : sv[e];
+    }
+  }
+  if (threadIdx.x == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 inline int fill_mlp(SemArgsPtrs* p, const float* const* mlp, int32_t n_class, const char* what) {

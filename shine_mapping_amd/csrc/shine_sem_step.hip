@@ -266,74 +266,9 @@ SEM_ROW_LOOP(8)
     }
     if (lane == 0) mine[P_N] = vals[39];
   }
-  unsigned* cnt = reinterpret_cast<unsigned*>(a.ws);
-  float* runsum = part + (size_t)kMaxBlocks * PS;  // [kGroups][PS]
-  const unsigned G = gridDim.x;
-  const unsigned grp = blockIdx.x / kGroup;
-  const unsigned g0 = grp * kGroup;
-  const unsigned gsz = (G - g0) < (unsigned)kGroup ? (G - g0) : (unsigned)kGroup;
-  const unsigned ngrp = (G + kGroup - 1) / kGroup;
-  // the sums below walk the partial vectors four floats at a time (PS, every tensor's offset and the loss's slot P_N are
-  // multiples of four; the three floats behind the loss are summed along and never used)
-  static_assert(PS % 4 == 0 && P_N % 4 == 0 && P_B1 % 4 == 0 && P_BC % 4 == 0, "float4 walk");
-  const int c0 = wgrad ? 0 : P_N / 4;  // a frozen head: only the loss is summed
-
-  // level 1: the last workgroup of this run to arrive sums the run's partials in index order
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned tk = __hip_atomic_fetch_add(cnt + 1 + grp, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    s_flag = (tk == gsz - 1) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (s_flag == 0u) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  for (int c = c0 + threadIdx.x; c <= P_N / 4; c += (int)blockDim.x) {
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (unsigned b = 0; b < gsz; ++b) {
-      const float4 v = *reinterpret_cast<const float4*>(part + (size_t)(g0 + b) * PS + 4 * c);
-      s.x += v.x, s.y += v.y, s.z += v.z, s.w += v.w;
-    }
-    *reinterpret_cast<float4*>(runsum + (size_t)grp * PS + 4 * c) = s;
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(cnt + 1 + grp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next call
-    const unsigned tk = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    s_flag = (tk == ngrp - 1) ? 2u : 0u;
-  }
-  __syncthreads();
-  if (s_flag != 2u) return;
-  // level 2: the last run to finish sums the run sums in index order, ADDS the six gradients and writes the loss
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  for (int c = c0 + threadIdx.x; c <= P_N / 4; c += (int)blockDim.x) {
-    float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (unsigned q = 0; q < ngrp; ++q) {
-      const float4 v = *reinterpret_cast<const float4*>(runsum + (size_t)q * PS + 4 * c);
-      s4.x += v.x, s4.y += v.y, s4.z += v.z, s4.w += v.w;
-    }
-    const float sv[4] = {s4.x, s4.y, s4.z, s4.w};
-    if (4 * c == P_N) {
-      a.loss_out[0] = sv[0] * a.inv_m;
-      continue;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int k = 4 * c + e;
-      const float s = sv[e];
-      if (k < P_B1) a.gp.g[0][k - P_W1] += s;
-      else if (k < P_W2) a.gp.g[1][k - P_B1] += s;
-      else if (k < P_B2) a.gp.g[2][k - P_W2] += s;
-      else if (k < P_WC) a.gp.g[3][k - P_B2] += s;
-      else if (k < P_BC) {
-        if (k - P_WC < a.C * H) a.gp.g[4][k - P_WC] += s;
-      } else if (k - P_BC < a.C) {
-        a.gp.g[5][k - P_BC] += s;
-      }
-    }
-  }
-  if (threadIdx.x == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // ADDS the six gradients and writes the loss (the three floats behind the loss's slot are summed along and never used); a
+  // frozen head: only the loss's column is summed
+  sem_grid_sum<PS, true>(a.ws, wgrad ? 0 : P_N / 4, a.gp, a.C, a.loss_out, a.inv_m, &s_flag);
 }
 
 // Launch shape: four waves per workgroup, a tile each, at most kMaxBlocks workgroups with a grid stride past 64 K rows; it

@@ -11,8 +11,7 @@
 // rounded logp with the first index winning ties, exactly torch.argmax(sem_label_prob(f)).
 //
 // Weight grads are repeat-bit-identical: every wave accumulates its tiles in a fixed order, the four waves of a workgroup are
-// summed in a fixed order, and the workgroups' partials meet in two ticket levels (shine_loss_modes.hip's scheme): the last
-// workgroup of each run of kGroup to arrive sums that run's partials in index order, the last run to finish sums the run sums.
+// summed in a fixed order, and the workgroups' partials meet in the two ticket levels of shine_sem_head.hpp's sem_grid_sum.
 #include "shine_sem_head.hpp"
 
 namespace shine {
@@ -187,54 +186,7 @@ SEM_ROW_LOOP(8)
       mine[P_B1 + jj] = vals[38];
     }
   }
-  unsigned* cnt = reinterpret_cast<unsigned*>(ws);
-  float* runsum = part + (size_t)kMaxBlocks * P_N;  // [kGroups][P_N]
-  const unsigned G = gridDim.x;
-  const unsigned grp = blockIdx.x / kGroup;
-  const unsigned g0 = grp * kGroup;
-  const unsigned gsz = (G - g0) < (unsigned)kGroup ? (G - g0) : (unsigned)kGroup;
-  const unsigned ngrp = (G + kGroup - 1) / kGroup;
-
-  // level 1: the last workgroup of this run to arrive sums the run's partials in index order
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned tk = __hip_atomic_fetch_add(cnt + 1 + grp, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    s_flag = (tk == gsz - 1) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (s_flag == 0u) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  for (int k = threadIdx.x; k < P_N; k += kThreads) {
-    float a = 0.f;
-    for (unsigned b = 0; b < gsz; ++b) a += part[(size_t)(g0 + b) * P_N + k];
-    runsum[(size_t)grp * P_N + k] = a;
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __hip_atomic_store(cnt + 1 + grp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next call
-    const unsigned tk = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    s_flag = (tk == ngrp - 1) ? 2u : 0u;
-  }
-  __syncthreads();
-  if (s_flag != 2u) return;
-  // level 2: the last run to finish sums the run sums in index order and writes the six gradients
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  for (int k = threadIdx.x; k < P_N; k += kThreads) {
-    float a = 0.f;
-    for (unsigned r = 0; r < ngrp; ++r) a += runsum[(size_t)r * P_N + k];
-    if (k < P_B1) gp.g[0][k - P_W1] = a;
-    else if (k < P_W2) gp.g[1][k - P_B1] = a;
-    else if (k < P_B2) gp.g[2][k - P_W2] = a;
-    else if (k < P_WC) gp.g[3][k - P_B2] = a;
-    else if (k < P_BC) {
-      if (k - P_WC < C * H) gp.g[4][k - P_WC] = a;
-    } else if (k - P_BC < C) {
-      gp.g[5][k - P_BC] = a;
-    }
-  }
-  if (threadIdx.x == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  sem_grid_sum<P_N, false>(ws, 0, gp, C, nullptr, 0.f, &s_flag);  // writes the six gradients
 }
 
 // ---- mesh labels: the interpolation of shine_query_points (shine_query.hip), then the head above; nothing but the label leaves

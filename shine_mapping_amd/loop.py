@@ -224,7 +224,7 @@ class GraphedIteration:
         if any(train) != all(train):
             raise ValueError("the semantic head's six tensors must all train or all be frozen")
         self._sem_train = all(train)
-        self._sem_ws = torch.zeros(SEM_WORKSPACE_BYTES // 8, dtype=torch.float64, device=dev)
+        self._sem_ws = _lib.zeroed_workspace(SEM_WORKSPACE_BYTES, dev)  # (its own: the captured graph holds the address)
         self._sem_out = torch.zeros(1, dtype=torch.float32, device=dev)
         self.sem_loss = self._sem_out[0]
 

@@ -64,18 +64,9 @@ def sdf_bce_loss(pred, label, sigma, weight, weighted=False, bce_reduction="mean
     return _bce_composite(pred, label, sigma, weight, weighted, bce_reduction)
 
 
-_WORKSPACES = {}  # (device index, stream) -> the zeroed workspace of shine_sdf_diff_loss / shine_ray_render_loss
-
-
 def loss_workspace(device):
-    """SHINE_LOSS_WORKSPACE_BYTES of zeroed device memory for the current stream of `device` (the kernels leave it zero again;
-    calls on one stream never overlap)"""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    key = (idx, _lib.current_stream_handle() if idx == torch.cuda.current_device() else torch.cuda.current_stream(idx).cuda_stream)
-    ws = _WORKSPACES.get(key)
-    if ws is None:
-        ws = _WORKSPACES[key] = torch.zeros(LOSS_WORKSPACE_BYTES // 8, dtype=torch.float64, device=torch.device("cuda", idx))
-    return ws
+    """the workspace of shine_sdf_diff_loss / shine_ray_render_loss for the current stream of `device`"""
+    return _lib.ticket_workspace(device, LOSS_WORKSPACE_BYTES)
 
 
 LOSS_WORKSPACE_BYTES = 16384  # include/shine_hip.h SHINE_LOSS_WORKSPACE_BYTES

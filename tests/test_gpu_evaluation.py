@@ -314,12 +314,15 @@ def test_nn_correspondence_outliers_are_bounded_and_not_slower_than_the_tree():
 # ------------------------------------------------------------------------------------------------ metrics, eval_mesh
 def test_distance_sums_equal_numpy():
     rng = np.random.default_rng(61)
-    dp, dr = rng.random(1234567) * 0.2, rng.random(54321) * 2.0
-    s = ev.distance_sums(torch.as_tensor(dp).cuda(), torch.as_tensor(dr).cuda(), 0.05)
-    want = [dp.sum(), (dp ** 2).sum(), (dp < 0.05).sum(), dr.sum(), (dr ** 2).sum(), (dr < 0.05).sum(), len(dp), len(dr)]
-    assert np.allclose(s, want, rtol=RTOL, atol=0) and s[2] == want[2] and s[5] == want[5]
-    s2 = ev.distance_sums(torch.as_tensor(dp).cuda(), torch.as_tensor(dr).cuda(), 0.05)
-    assert np.array_equal(s, s2)
+    # (n_p, n_r); the longer one sets the grid: one workgroup of 256, two, exactly the 256 workgroups of the reduction without
+    # and with a strided tail, and many strides
+    for n_p, n_r in ((1234567, 54321), (1, 1), (256, 100), (100, 257), (65536, 3), (1000, 65537)):
+        dp, dr = rng.random(n_p) * 0.2, rng.random(n_r) * 2.0
+        s = ev.distance_sums(torch.as_tensor(dp).cuda(), torch.as_tensor(dr).cuda(), 0.05)
+        want = [dp.sum(), (dp ** 2).sum(), (dp < 0.05).sum(), dr.sum(), (dr ** 2).sum(), (dr < 0.05).sum(), len(dp), len(dr)]
+        assert np.allclose(s, want, rtol=RTOL, atol=0) and s[2] == want[2] and s[5] == want[5], (n_p, n_r)
+        s2 = ev.distance_sums(torch.as_tensor(dp).cuda(), torch.as_tensor(dr).cuda(), 0.05)
+        assert np.array_equal(s, s2), (n_p, n_r)
     e = ev.distance_sums(torch.zeros(0, dtype=torch.float64).cuda(), torch.as_tensor(dr).cuda(), 0.05)
     assert e[:3].tolist() == [0, 0, 0] and e[6] == 0 and e[7] == len(dr)
     m = ev.metrics_from_sums(e, 0.02, 0.05, 0.2, 2.0)

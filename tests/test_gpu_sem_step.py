@@ -135,7 +135,9 @@ def _assert_close(what, got, ref, tol=STEP_TOL):
 
 # ---- 1. one step against the composite
 @pytest.mark.parametrize("C", [1, 21, 32])
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 4096 + 17])
+# (a workgroup is 256 rows, a first-level run of the ticket sums 16 workgroups, the grid 256 workgroups at most: 257 = two
+# workgroups, 4096 = exactly one full run, 4096 + 17 = a run of one behind it, 65537 = every workgroup and a grid-stride pass)
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 4096, 4096 + 17, 65537])
 def test_one_step_matches_the_composite(workload, n, C):
     wl = workload
     sem = _head(C)
