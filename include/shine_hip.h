@@ -316,6 +316,40 @@ int shine_sem_train_step(const shine_tables* t, const shine_step_config* cfg, co
                          const float* const* feats, const int64_t* rows, float* const* grad_feats, const float* const* mlp,
                          int32_t n_class, float* const* grad_mlp, float* sem_loss_out, void* workspace, void* stream);
 
+/* ---- Tier B with normal_loss_on: the surface-normal term of one training iteration (shine_batch.py:192-197) in ONE launch,
+ *      beside shine_train_step on the same batch.  With g_i = d pred_i / d coord_i (no sigma_sigmoid: a positive factor on g
+ *      changes neither the loss nor any gradient) and n_surf = the number of rows with weight > 0:
+ *        gh_i = g_i / |g_i| if |g_i| > 0, else 0;  normal_loss = 1 / n_surf * sum over weight_i > 0 of |gh_i - normal_i|_2
+ *        (0 when n_surf == 0), and weight_n * d normal_loss / d {feature tables, W1, W2, w3}; no bias receives anything.
+ *      Two deliberate differences from the reference's three lines: its g / g.norm(2, dim=-1) does not broadcast for n other
+ *      than 1 or 3 (keepdim=True is meant), and with that repaired a row whose g is exactly zero (a point that misses every
+ *      level, a dead unit) makes the loss NaN — THE GUARD: such a row stays in the denominator, contributes |normal_i| to the
+ *      loss and gets no gradient, the eikonal term's convention.  A row with |gh_i - normal_i| == 0 gets no gradient either.
+ *      coord / coord_stride / idx as for shine_sem_train_step (3: a plain [n,3] array; 8: 32-byte pool records).  weight: rows
+ *      of weight_stride floats whose first is the weight — 1: an array (also the separate weight array of a 4-level pool);
+ *      8: word 4 of the pool's records, passed as record base + 4 floats.  normal: float32 [.,3], labels that need not be unit
+ *      vectors.  Batch position i reads row idx[i] (without idx: row i) of coord, weight AND normal; a row with weight <= 0
+ *      reads neither its coordinate nor its normal.  n_surf: int64 on the device — one count (n_surf_parts <= 1), or
+ *      n_surf_parts partial counts the kernel adds up (the draw's surf_parts, as shine_train_step takes them); under data
+ *      parallelism the caller supplies the global count.
+ *      feats / rows / grad_feats as for shine_sem_train_step: grad_feats[s] [rows_s+1,8] is ACCUMULATED INTO with fp32 atomics,
+ *      trash row included (NULL array / NULL entries: no gradient for that level).  mlp: the six decoder tensors W1 [32,8],
+ *      b1, W2 [32,32], b2, w3 [32], b3.  grad_mlp: NULL (a frozen decoder: only feature grads and the loss are produced) or 6
+ *      tensors shaped like mlp; the sums are ADDED to entries 0, 2 and 4 by the workgroup that finishes them, entries 1, 3, 5
+ *      are not touched.  Those sums and *normal_loss_out (float, the UNWEIGHTED mean; summed in fp64 partials and divided in
+ *      fp64) are bit-identical from call to call.  workspace: SHINE_NORMAL_WORKSPACE_BYTES of 256-byte aligned device memory,
+ *      a ticket workspace (above): zero before the first call, left zero by every call, never cleared by a call, so the launch
+ *      can be captured into a HIP graph.  n == 0 launches nothing and writes a loss of 0.
+ *      SHINE_E_INVALID before anything touches the device: a null table handle / cfg / coord / weight / normal / n_surf /
+ *      loss_out / workspace / decoder tensor, n < 0, coord_stride other than 3 or 8, weight_stride other than 1 or 8, more than
+ *      4 featured levels. */
+#define SHINE_NORMAL_WORKSPACE_BYTES 1429888
+int shine_normal_train_step(const shine_tables* t, const shine_step_config* cfg, const float* coord, int32_t coord_stride,
+                            const int32_t* idx, const float* weight, int32_t weight_stride, const float* normal,
+                            const int64_t* n_surf, int32_t n_surf_parts, int64_t n, float weight_n, const float* const* feats,
+                            const int64_t* rows, float* const* grad_feats, const float* const* mlp, float* const* grad_mlp,
+                            float* normal_loss_out, void* workspace, void* stream);
+
 /* ---- Tier A (strict drop-in): the backward of FeatureOctree.query_feature as autograd derives it from
  *      model/feature_octree.py:222-234, and its own backward (needed by get_gradient(create_graph=True),
  *      utils/tools.py:175-185, when the eikonal term is differentiated, shine_batch.py:182-185).

@@ -841,12 +841,14 @@ class LiDARDataset:
         key = (self._pool_version, self.octree._tables_epoch)
         if self._sorted is None or self._sorted[1] != key:
             # (semantic_on: the labels travel with the pool, checked against the head's class count)
-            sem = dict(sem_label=self.sem_label_pool, n_class=int(self.config.sem_class_count) + 1) if self.semantic else {}
+            extra = dict(sem_label=self.sem_label_pool, n_class=int(self.config.sem_class_count) + 1) if self.semantic else {}
+            if self.estimate_normal:  # (the normals travel with the pool: loop.GraphedIteration(normal=...) reads them)
+                extra["normal_label"] = self.normal_label_pool
             if self._sorted is None:
-                sp = SortedPool(self.octree, self.coord_pool, self.sdf_label_pool, self.weight_pool, seed=self.seed, **sem)
+                sp = SortedPool(self.octree, self.coord_pool, self.sdf_label_pool, self.weight_pool, seed=self.seed, **extra)
             else:
                 sp = self._sorted[0]
-                sp.rebuild(self.coord_pool, self.sdf_label_pool, self.weight_pool, **sem)
+                sp.rebuild(self.coord_pool, self.sdf_label_pool, self.weight_pool, **extra)
             self._sorted = (sp, key)
             self._sorted_perm = sp.perm.long()
         return self._sorted[0]

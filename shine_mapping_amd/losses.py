@@ -164,6 +164,27 @@ def batch_ray_rendering_loss(x, y, d_meas, neus_on=True):
     return batch_ray_rendering_loss_composite(x, y, d_meas, neus_on)
 
 
+def normal_loss(g, normal_label, weight):
+    """The surface-normal term of the drivers' normal_loss_on branch (shine_batch.py:192-197) in a form that can be evaluated:
+
+        surf = weight > 0;  gh = g / |g| where |g| > 0, else 0;  loss = mean over surf of |gh - normal_label|_2  (0 without a surface row)
+
+    g [N,3] = get_gradient(coord, pred) (times sigma_sigmoid or not: gh does not change), normal_label [N,3], weight [N].
+    The reference's lines differ in two ways, both defects: `g / g.norm(2, dim=-1)` divides [N,3] by [N] and fails to broadcast
+    for N other than 1 or 3 (keepdim=True is meant), and with that repaired a surface row whose g is exactly zero — a point that
+    misses every level, a dead unit — is 0/0 and turns the mean into NaN.  The guard is the eikonal term's: such a row stays in
+    the denominator, contributes |normal_label| and gets no gradient.  Rows with weight <= 0 do not read their label (it may be
+    NaN).  Plain differentiable torch with no host sync: the composite ops.fused_normal_step (Tier B, one HIP launch) is checked
+    against, and what a Tier A driver calls in place of the reference's three lines."""
+    surf = weight > 0
+    gn = g.norm(2, dim=-1, keepdim=True)
+    live = gn > 0
+    gh = torch.where(live, g / torch.where(live, gn, torch.ones_like(gn)), torch.zeros_like(g))
+    label = torch.where(surf.unsqueeze(-1), normal_label.to(g.dtype), torch.zeros_like(g))
+    per = (gh - label).norm(2, dim=-1)  # (the reference's .abs() in front of a 2-norm changes nothing)
+    return torch.where(surf, per, torch.zeros_like(per)).sum() / surf.sum().clamp_min(1).to(g.dtype)
+
+
 def get_gradient(inputs, outputs):
     """utils/tools.py:175-185: d outputs / d inputs with create_graph=True.  For the pred of the fused query_feature -> sdf
     node and its own coord: one launch (autograd_ops.InterpSdfGradCoord); otherwise the reference's autograd call."""

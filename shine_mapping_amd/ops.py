@@ -360,6 +360,116 @@ def fused_sem_step(octree, sem_decoder, coord, sem_label, weight_s, decimation=1
     return out.view(())
 
 
+def fused_normal_step(octree, decoder, coord, weight, normal_label, weight_n, n_surf=None, pool=None, idx=None,
+                      grad_buffers=None, out=None, workspace=None):
+    """The surface-normal term of one training iteration (shine_batch.py:192-197) in ONE launch (shine_normal_train_step):
+
+        g = get_gradient(coord, decoder.sdf(octree.query_feature(coord)))
+        normal_loss = losses.normal_loss(g, normal_label, weight);  (weight_n * normal_loss).backward()
+
+    — the definition of losses.normal_loss: the reference's lines with keepdim repaired and a zero-gradient guard (a surface row
+    whose g is exactly zero stays in the mean's denominator, contributes |normal_label| and gets no gradient).  No sigma: a
+    positive factor on g changes nothing.
+    Array mode: coord [N,3] float32, weight [N] float32 (> 0: a surface sample), normal_label [N,3] float32 (need not be unit
+    vectors; rows with weight <= 0 are not read), optionally idx (CUDA int32: batch position i reads row idx[i] of all three).
+    Pool mode: pool = a SortedPool built with normal_label= and idx = pool.draw(n): the batch is read straight out of the pool's
+    records (coord / weight / normal_label are ignored).  `n_surf`: the number of surface rows as an int64 device tensor of one
+    element, or the draw's partial counts (pool.surf_parts_buffer(), summed in the kernel); default (weight > 0).sum() on the
+    device; under data parallelism the caller passes the global count.
+    Returns the UNWEIGHTED normal_loss as a 0-dim float32 device tensor (no host sync, no grad_fn — the gradients are already in
+    place; `out`: a float32 tensor of one element to write it to).  Accumulates into ``.grad`` of octree.hier_features[*] and of
+    the decoder's W1, W2, w3 exactly as fused_train_step does (dense, trash row included; the biases receive nothing), or into
+    `grad_buffers` = (L feature-grad tensors, 6 decoder-grad tensors | None) instead.  A decoder whose parameters do not
+    require grad (freeze_model) gets no gradient: only the feature grads are written.
+    `workspace`: SHINE_NORMAL_WORKSPACE_BYTES of zeroed device memory the caller owns (default: the current stream's,
+    autograd_ops.normal_workspace)."""
+    t = octree._require_tables()  # (the kernel probes the hash tables from the coordinates)
+    mlp = decoder.fused_params()
+    if n_surf is not None and not isinstance(n_surf, torch.Tensor):
+        raise ValueError("n_surf must be a contiguous CUDA int64 tensor (one count, or the draw's partial counts)")
+
+    def _idx_ok(i):
+        return i.is_cuda and i.dtype == torch.int32 and i.is_contiguous()
+
+    if pool is not None:
+        if idx is None or not _idx_ok(idx):
+            raise ValueError("pool mode needs idx = SortedPool.draw(n) (CUDA int32)")
+        if pool.tables_epoch != octree._tables_epoch:
+            raise RuntimeError("the octree grew since the pool was planned: call SortedPool.rebuild()")
+        normal = getattr(pool, "normal_label", None)
+        if normal is None:
+            raise ValueError("pool mode needs a SortedPool built with normal_label=")
+        if getattr(pool, "rec", None) is not None:
+            src, stride = pool.rec, 8
+            if pool._weight_sep is None:  # word 4 of the 32-byte records
+                w_ptr, w_stride, w_keep = pool.rec.data_ptr() + 16, 8, pool.rec
+            else:
+                w_ptr, w_stride, w_keep = pool._weight_sep.data_ptr(), 1, pool._weight_sep
+        else:
+            soa = pool.soa()
+            src, stride = soa[0], 3
+            w_ptr, w_stride, w_keep = soa[2].data_ptr(), 1, soa[2]
+        n = int(idx.numel())
+        if n_surf is None:
+            n_surf = (pool.weight[idx.long()] > 0).sum()
+    else:
+        if not all(isinstance(x, torch.Tensor) for x in (coord, weight, normal_label)):
+            raise ValueError("array mode needs coord [N,3], weight [N] and normal_label [N,3] (or pool= and idx=)")
+        src, stride = octree._check_coord(coord.detach()), 3
+        normal = normal_label
+        w_keep = _f32(weight, "weight")
+        w_ptr, w_stride = w_keep.data_ptr(), 1
+        n = int(src.shape[0])
+        if w_keep.dim() != 1 or w_keep.numel() != n:
+            raise ValueError("weight must hold one value per coordinate")
+        if idx is not None:
+            if not _idx_ok(idx):
+                raise ValueError("idx must be a contiguous CUDA int32 tensor")
+            n = int(idx.numel())
+        if n_surf is None:
+            n_surf = ((w_keep[idx.long()] if idx is not None else w_keep) > 0).sum()
+    if not (isinstance(normal, torch.Tensor) and normal.is_cuda and normal.dtype == torch.float32 and normal.is_contiguous()
+            and normal.dim() == 2 and normal.shape[1] == 3):
+        raise ValueError("normal_label must be a contiguous CUDA float32 [N,3] tensor")
+    if pool is None and normal.shape[0] != src.shape[0]:
+        raise ValueError("normal_label must hold one normal per coordinate")
+    dev = src.device
+    if not (n_surf.is_cuda and n_surf.dtype == torch.int64 and n_surf.is_contiguous() and n_surf.numel() >= 1):
+        raise ValueError("n_surf must be a contiguous CUDA int64 tensor (one count, or the draw's partial counts)")
+    if not decoder._params_on(dev, mlp):
+        raise ValueError("the decoder's parameters must be CUDA float32 contiguous on the batch's device")
+    gfeat, gmlp = grad_buffers if grad_buffers is not None else (None, None)
+    if gfeat is None:
+        gfeat = [_dense_grad(p) if p.requires_grad else None for p in octree.feature_list()]
+    if grad_buffers is None:
+        train = [p.requires_grad for p in mlp]
+        if any(train) != all(train):
+            raise ValueError("the decoder's six tensors must all require grad or all be frozen")
+        gmlp = [_dense_grad(p) for p in mlp] if all(train) else None
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.numel() == 1):
+        raise ValueError("out must be a CUDA float32 tensor of one element")
+    ws = workspace if workspace is not None else autograd_ops.normal_workspace(dev)
+    cfg = octree.step_config()
+    _lib.check(
+        _lib.lib().shine_normal_train_step(
+            t.handle, C.byref(cfg), src.data_ptr(), stride, idx.data_ptr() if idx is not None else None, w_ptr, w_stride,
+            normal.data_ptr(), n_surf.data_ptr(), int(n_surf.numel()), n, float(weight_n),
+            octree.feature_ptrs(), octree.row_counts(),
+            _lib.ptr_array([g.data_ptr() if g is not None else None for g in gfeat]),
+            _lib.ptr_array([p.data_ptr() for p in mlp]),
+            _lib.ptr_array([g.data_ptr() for g in gmlp]) if gmlp is not None else None,
+            out.data_ptr(), ws.data_ptr(), _stream(),
+        ),
+        "shine_normal_train_step",
+    )
+    del w_keep
+    if not torch.cuda.is_current_stream_capturing():
+        octree._tables_read_done()
+    return out.view(())
+
+
 def octree_interp(octree, coord):
     """FeatureOctree.query_feature (model/feature_octree.py:237-244) -> [N,8]; also fills hierarchical_indices."""
     needs_grad = torch.is_grad_enabled() and (

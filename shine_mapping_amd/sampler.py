@@ -109,7 +109,8 @@ class DrawChain:
 
 
 class SortedPool:
-    def __init__(self, octree, coord, sdf_label, weight, seed=42, canonical=False, sem_label=None, n_class=None):
+    def __init__(self, octree, coord, sdf_label, weight, seed=42, canonical=False, sem_label=None, n_class=None,
+                 normal_label=None):
         """`canonical`: order the samples of one node by their original pool index.  The plan's counting sort places the
         samples of a node in whatever order its atomics retire, so two processes (or two runs) hold the same pool in
         different within-node orders: still a valid pool — draws stay i.i.d. uniform — but not the SAME draw.  Data-parallel
@@ -117,7 +118,10 @@ class SortedPool:
         one device sort of the pool per rebuild.
         `sem_label` (semantic_on): the samples' labels; kept in pool order as `self.sem_label` (int32) for
         ops.fused_sem_step(pool=...).  `n_class` (the semantic head's class count): every rebuild checks 0 <= label < n_class
-        and raises ValueError otherwise (one min / max, outside the iteration)."""
+        and raises ValueError otherwise (one min / max, outside the iteration).
+        `normal_label` (normal_loss_on): the samples' normals [P,3]; kept in pool order as a contiguous float32 [P,3]
+        `self.normal_label` for ops.fused_normal_step(pool=...) — 12 B per sample, paid only when it is given.  Like `sem_label`,
+        a rebuild without it deletes the attribute."""
         self.octree = octree
         self.canonical = bool(canonical)
         self.seed = int(seed)
@@ -126,11 +130,13 @@ class SortedPool:
         self._stream_state = None  # device uint64[4] for graph-replayable draws (loop.GraphedIteration)
         self._rider_for = None     # size of the draw whose first pass the last fused step carried (StepOptions.next_draw)
         self.n_class = None if n_class is None else int(n_class)
-        self.rebuild(coord, sdf_label, weight, sem_label=sem_label)
+        self.rebuild(coord, sdf_label, weight, sem_label=sem_label, normal_label=normal_label)
 
-    def rebuild(self, coord, sdf_label, weight, sem_label=None, n_class=None):
+    def rebuild(self, coord, sdf_label, weight, sem_label=None, n_class=None, normal_label=None):
         if n_class is not None:
             self.n_class = int(n_class)
+        if normal_label is not None and (normal_label.dim() != 2 or tuple(normal_label.shape) != (coord.shape[0], 3)):
+            raise ValueError("normal_label must hold one [3] normal per pool sample")
         if sem_label is not None:
             if sem_label.shape[0] != coord.shape[0] or sem_label.dim() != 1:
                 raise ValueError("sem_label must hold one label per pool sample")
@@ -182,6 +188,10 @@ class SortedPool:
             self.sem_label = sem_label[p].to(torch.int32).contiguous()
         elif hasattr(self, "sem_label"):
             del self.sem_label  # (a rebuild without labels: nothing stale is kept)
+        if normal_label is not None:
+            self.normal_label = normal_label[p].to(torch.float32).contiguous()
+        elif hasattr(self, "normal_label"):
+            del self.normal_label
         self.tables_epoch = self.octree._tables_epoch
         # sampler scratch of other pool sizes is dead weight (a graph captured for the old pool is invalid anyway: the
         # tables epoch moved); without this an object rebuilt every frame pins one buffer per distinct frame size
