@@ -123,19 +123,26 @@ class OctreeInterpBackward(torch.autograd.Function):
             grad_feats = dense
         if any(x is not None for x in gg_feats):
             # d(grad_F_l)/dg: grad_F_l[id] = sum w g  ->  dg += sum_l interp(gg_F_l): the forward kernel on gg tables
-            tabs = [x.detach().contiguous().float() if x is not None else torch.zeros_like(f)
-                    for x, f in zip(gg_feats, feats)]
+            # The kernel is query_feature's: it clears the trash row of every table it is given (set_zero) and reads no row for a
+            # miss.  So it runs on copies (gg_feats are autograd's tensors, not ours to write), and what the reference's graph
+            # sends through the trash row is added here: a miss addresses it with all eight corners, whose weights sum to 1.
+            tabs = [x.detach().to(torch.float32, memory_format=torch.contiguous_format, copy=True) if x is not None
+                    else torch.zeros_like(f, memory_format=torch.contiguous_format) for x, f in zip(gg_feats, feats)]
+            trash = [x[-1].clone() for x in tabs]
             extra = torch.empty((n, 8), dtype=torch.float32, device=c.device)
+            idx = [torch.empty((n, 8), dtype=torch.int64, device=c.device) for _ in feats]  # bottom-up
             from .ops import _dummy_mlp
 
             _lib.check(
                 _lib.lib().shine_forward(
                     t.handle, C.byref(cfg), c.data_ptr(), n, _lib.ptr_array([x.data_ptr() for x in tabs]),
                     octree.row_counts(), _lib.ptr_array([p.data_ptr() for p in _dummy_mlp(c.device)]),
-                    extra.data_ptr(), None, None, None, _stream(),
+                    extra.data_ptr(), None, _lib.ptr_array([o.data_ptr() for o in idx]), None, _stream(),
                 ),
                 "shine_forward",
             )
+            for s, row in enumerate(trash):
+                extra += (idx[len(feats) - 1 - s][:, :1] < 0).to(torch.float32) * row
             grad_g = extra if grad_g is None else grad_g + extra
         # inputs: g, coord, octree, want_coord, *feats   (no second derivative wrt coord: it is a leaf nobody reads)
         return (grad_g, None, None, None) + tuple(grad_feats)
