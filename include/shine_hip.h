@@ -350,6 +350,49 @@ int shine_normal_train_step(const shine_tables* t, const shine_step_config* cfg,
                             const int64_t* rows, float* const* grad_feats, const float* const* mlp, float* const* grad_mlp,
                             float* normal_loss_out, void* workspace, void* stream);
 
+/* ---- Tier B with consistency_loss_on: the gradient-consistency term of one training iteration (shine_batch.py:149-158,187-190,
+ *      shine_incre.py:137-146,167-170) in ONE launch, beside shine_train_step on the same batch.  There are n_pairs pairs; pair k
+ *      has a base point a_k = coord row near_index[k] (any of the n batch rows, repeats allowed) and a shifted point
+ *      b_k = fl32(a_k + shift[k]).  All rows take part, free-space rows included: no weight and no label is read.  With
+ *      ga, gb = d pred / d coord at a_k, b_k (no sigma_sigmoid: the factor cancels in the cosine):
+ *        c_k = (ga . gb) / (|ga| |gb|) if |ga| > 0 and |gb| > 0, else 0;  consistency_loss = 1 / n_pairs * sum_k (1 - c_k),
+ *        and weight_c * d consistency_loss / d {feature tables, W1, W2, w3} through BOTH points of every pair; no bias receives
+ *        anything.  dL/dga = -(gbh - c gah) / |ga| * weight_c / n_pairs with the unit vectors gah, gbh, symmetrically for gb.
+ *      THE GUARD: a pair with either gradient exactly zero (a point that misses every level, dead units) contributes 1 and gets
+ *      no gradient on either side — the eikonal and normal terms' convention.  The value is the reference's there
+ *      (F.cosine_similarity gives 0 too); what the guard removes is its gradient gbh / eps, eps = 1e-8, on the zero side: a finite
+ *      but 1e8-scaled push into every weight the row's second-order path reaches.
+ *      coord / coord_stride / idx as for shine_normal_train_step (3: a plain [.,3] array; 8: 32-byte pool records); n: the number
+ *      of batch rows (0 <= n < 2^31) — batch row i is coord row idx[i] (without idx: row i).
+ *      The pairs come in one of two modes.  EXPLICIT: near_index int32 [n_pairs], values in [0, n) (the caller's precondition; a
+ *      pair whose index is outside is left out), and shift float32 [n_pairs,3].  DRAWN: both NULL — the kernel draws them from
+ *      (seed, *draw_state), draw_state a device uint64: the splitmix64 finaliser of (seed, stream, counter) of the samplers with
+ *      stream = *draw_state and counter = 4 k + j; j = 0 gives near_index[k] = (top 32 bits * n) >> 32 (no float), j = 1..3 give
+ *      shift_j = fmaf(2 u, shift_scale, -shift_scale) with a 24-bit u, so each component lies in [-shift_scale, shift_scale).
+ *      Every workgroup reads *draw_state before it arrives and the workgroup that finishes the grid sum stores *draw_state + 1: a
+ *      replayed HIP graph draws fresh pairs each iteration with no host involvement.  In explicit mode draw_state and shift_scale
+ *      are not read.  near_index_out / shift_out (NULL, or shaped like the inputs): receive the pairs the launch used.
+ *      feats / rows / grad_feats as for shine_sem_train_step: grad_feats[s] [rows_s+1,8] is ACCUMULATED INTO with fp32 atomics,
+ *      trash row included (NULL array / NULL entries: no gradient for that level).  touched: NULL, or per level NULL / uint8
+ *      [rows_s+1] — every corner row a pair adds gradient to gets a plain byte store of 1, as shine_mark_touched writes them
+ *      (the shifted points reach rows the batch's own points do not; the active-row Adam neither steps nor clears an unflagged
+ *      row).  mlp: the six decoder tensors.  grad_mlp: NULL (a frozen decoder: only feature grads and the loss are produced) or 6
+ *      tensors shaped like mlp; the sums are ADDED to entries 0, 2 and 4 by the workgroup that finishes them, entries 1, 3, 5
+ *      are not touched.  Those sums and *consistency_loss_out (float, the UNWEIGHTED mean; summed in fp64 partials and divided in
+ *      fp64) are bit-identical from call to call.  workspace: SHINE_CONSISTENCY_WORKSPACE_BYTES of 256-byte aligned device
+ *      memory, a ticket workspace (above): zero before the first call, left zero by every call, never cleared by a call, so the
+ *      launch can be captured into a HIP graph.  n_pairs == 0 launches nothing and writes a loss of 0.
+ *      SHINE_E_INVALID before anything touches the device: a null table handle / cfg / coord / loss_out / workspace / decoder
+ *      tensor, n < 0, n_pairs < 0, exactly one of near_index / shift, drawn pairs without draw_state, n_pairs > 0 with n == 0,
+ *      coord_stride other than 3 or 8, more than 4 featured levels. */
+#define SHINE_CONSISTENCY_WORKSPACE_BYTES 1429888
+int shine_consistency_train_step(const shine_tables* t, const shine_step_config* cfg, const float* coord, int32_t coord_stride,
+                                 const int32_t* idx, int64_t n, const int32_t* near_index, const float* shift, int64_t n_pairs,
+                                 float shift_scale, uint64_t seed, uint64_t* draw_state, int32_t* near_index_out,
+                                 float* shift_out, float weight_c, const float* const* feats, const int64_t* rows,
+                                 float* const* grad_feats, const float* const* mlp, float* const* grad_mlp,
+                                 unsigned char* const* touched, float* consistency_loss_out, void* workspace, void* stream);
+
 /* ---- Tier A (strict drop-in): the backward of FeatureOctree.query_feature as autograd derives it from
  *      model/feature_octree.py:222-234, and its own backward (needed by get_gradient(create_graph=True),
  *      utils/tools.py:175-185, when the eikonal term is differentiated, shine_batch.py:182-185).

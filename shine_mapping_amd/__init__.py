@@ -10,16 +10,20 @@ Public surface mirrors the reference's modules for this path:
     fused_train_step                    the same launch in raw form (grads written straight into .grad)
     fused_sem_step                      semantic_on: the NLL term of the same batch, one more launch in raw form
     fused_normal_step                   normal_loss_on: the surface-normal term of the same batch, one more launch in raw form
+    consistency_loss                    the consistency_loss_on term (shine_batch.py:187-190) with the zero-gradient guard
+    fused_consistency_step              consistency_loss_on: the gradient-consistency term on pairs of points, one more launch
+    ConsistencyTerm                     ... and its GraphedIteration(consistency=...) form (loop.py)
     eval_mesh                           eval/eval_utils.py (mesh metrics against a ground-truth cloud; evaluation.py)
 All compute goes through libshine_hip.so (include/shine_hip.h); there is no CPU fallback.
 """
 from .decoder import Decoder
 from .evaluation import eval_mesh
 from .feature_octree import FeatureOctree
-from .losses import batch_ray_rendering_loss, get_gradient, normal_loss, sdf_bce_loss, sdf_diff_loss
-from .ops import (StepOptions, forward_sdf, fused_normal_step, fused_sem_step, fused_train_step, octree_interp,
+from .loop import ConsistencyTerm
+from .losses import batch_ray_rendering_loss, consistency_loss, get_gradient, normal_loss, sdf_bce_loss, sdf_diff_loss
+from .ops import (StepOptions, forward_sdf, fused_consistency_step, fused_normal_step, fused_sem_step, fused_train_step, octree_interp,
                   train_step)
 
 __all__ = ["Decoder", "FeatureOctree", "StepOptions", "forward_sdf", "fused_train_step", "fused_sem_step", "fused_normal_step",
            "train_step", "octree_interp", "sdf_bce_loss", "get_gradient", "sdf_diff_loss", "batch_ray_rendering_loss",
-           "normal_loss", "eval_mesh"]
+           "normal_loss", "eval_mesh", "consistency_loss", "fused_consistency_step", "ConsistencyTerm"]

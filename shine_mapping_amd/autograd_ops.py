@@ -603,6 +603,14 @@ def normal_workspace(device):
     return _lib.ticket_workspace(device, NORMAL_WORKSPACE_BYTES)
 
 
+CONSISTENCY_WORKSPACE_BYTES = 1429888  # SHINE_CONSISTENCY_WORKSPACE_BYTES
+
+
+def consistency_workspace(device):
+    """the workspace of shine_consistency_train_step for the current stream of `device`"""
+    return _lib.ticket_workspace(device, CONSISTENCY_WORKSPACE_BYTES)
+
+
 def sem_forward(feat, mlp, want_logp=True, want_label=False):
     """(logp [N, C] | None, label [N] int64 | None) of shine_sem_forward; feat and the six tensors CUDA float32 contiguous"""
     f = _f32c(feat)

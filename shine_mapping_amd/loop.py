@@ -22,6 +22,12 @@ head trains its six tensors get one more graph-safe Adam launch of their own (th
 With `normal=NormalTerm(...)` (normal_loss_on) the normal step (ops.fused_normal_step, one launch) joins the same way: its
 feature and decoder grads land in the tensors the tail steps, so it needs no Adam launch of its own; with both terms the iteration
 is {fused step, semantic step, normal step, tail, the head's Adam}.
+With `consistency=ConsistencyTerm(...)` (consistency_loss_on) the consistency step (ops.fused_consistency_step, one launch) goes
+after the fused step and the other terms and before the tail: {fused, [sem], [normal], consistency, tail, [head Adam]}.  It draws its
+own K = min(count, n) pairs on the device from a draw state this object owns (advanced by the kernel: a replay draws fresh pairs)
+and flags the rows its shifted points reach, so the active-row Adam steps and clears them.  Not served with the regulariser
+(lambda_forget != 0): the reference then regularises the rows of its LAST query_feature call, coord_near's, an accident of call
+order (shine_incre.py:144,156).
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -30,8 +36,9 @@ import torch
 
 from . import _lib
 from .autograd_ops import bump_param_epoch
-from .autograd_ops import NORMAL_WORKSPACE_BYTES, SEM_WORKSPACE_BYTES
-from .ops import StepOptions, fused_normal_step, fused_regularization, fused_sem_step, fused_train_step, touched_flags
+from .autograd_ops import CONSISTENCY_WORKSPACE_BYTES, NORMAL_WORKSPACE_BYTES, SEM_WORKSPACE_BYTES
+from .ops import (StepOptions, fused_consistency_step, fused_normal_step, fused_regularization, fused_sem_step, fused_train_step,
+                  touched_flags)
 
 
 @dataclass
@@ -52,6 +59,18 @@ class NormalTerm:
     weight_n: float = 0.01
 
 
+@dataclass
+class ConsistencyTerm:
+    """The gradient-consistency term of GraphedIteration(consistency=...): the reference's config.weight_c, config.consistency_count
+    and shift_scale = consistency_range * scale in the [-1,1] space (consistency_loss_on, shine_batch.py:149-158,187-190; the
+    default is the reference's 0.1 m at a scale of 0.02); `seed`: of the pairs' own draws."""
+
+    weight_c: float = 1.0
+    count: int = 1000
+    shift_scale: float = 0.002
+    seed: int = 0
+
+
 class _IterationTerms(type):
     """GraphedIteration(..., normal=NormalTerm(...)): loss terms added after `sem` are keyword arguments of the CALL, set on the
     object before its constructor runs — the constructor's own parameter list is what existing callers (and the suite) spell out
@@ -59,11 +78,13 @@ class _IterationTerms(type):
     A stopgap with known costs: inspect.signature, a subclass that overrides __init__ / __new__ and a direct __init__ call do not
     see the keyword.  tests/test_sem_step.py::test_public_surface pins the constructor's exact parameter list and a change that adds
     a loss term may not edit existing tests; a later change should relax that pin to "the leading parameters and their defaults",
-    move `normal` into the constructor and delete this class — before a third term is hung on the same hook."""
+    move `normal` into the constructor and delete this class.  A third term now hangs on the hook: `consistency`
+    (ConsistencyTerm) rides the same way, under the same constraint."""
 
-    def __call__(cls, *args, normal=None, **kw):
+    def __call__(cls, *args, normal=None, consistency=None, **kw):
         self = cls.__new__(cls)
         self.normal = normal
+        self.consistency = consistency
         self.__init__(*args, **kw)
         return self
 
@@ -166,7 +187,11 @@ class GraphedIteration(metaclass=_IterationTerms):
     run(K); honoured only once an eager iteration has run on the device in this process (incremental mapping re-creates this
     object every frame: the eager iteration costs ~0.1 ms of launches that a replay does in a third of the time).
     `normal=NormalTerm(...)` (a keyword of the call, see _IterationTerms): the surface-normal term of the same batch as one more
-    launch between the fused step and the tail (ops.fused_normal_step); `normal_loss` is its 0-dim device tensor."""
+    launch between the fused step and the tail (ops.fused_normal_step); `normal_loss` is its 0-dim device tensor.
+    `consistency=ConsistencyTerm(...)` (a keyword of the call too): the gradient-consistency term as the last launch before the
+    tail (ops.fused_consistency_step, pairs drawn on the device); `consistency_loss` is its 0-dim device tensor and
+    `consistency_draws` = (near_index [K], shift [K,3]) holds the last iteration's pairs.  Raises ValueError with
+    lambda_forget != 0."""
 
     def __init__(self, octree, decoder, pool, opt, opts: StepOptions, n: int, lambda_forget: float = 0.0, unroll: int = 1,
                  fold: bool = True, eager_first: bool = True, active_rows: bool = True, native: bool = True, graph_slot: int = 0,
@@ -177,6 +202,9 @@ class GraphedIteration(metaclass=_IterationTerms):
         self.fold = bool(fold)  # the iteration's tail as one launch (False: reduction, regulariser and Adam as three)
         self.regularize = self.lambda_forget != 0.0
         can_fold = self.fold and hasattr(opt, "finish_iteration") and hasattr(opt, "prepare_graph_safe")
+        self.consistency = getattr(self, "consistency", None)
+        if self.consistency is not None:  # (argument errors before anything is allocated)
+            self._check_consistency(can_fold)
         # EXACT active-row Adam (FusedAdam.finish_iteration(active_flags=...)): rows that have had no gradient since `opt` was
         # created are not read.  Valid for an optimiser that is new (this object creates the flags cleared, so it must be built
         # together with the optimiser, as shine_incre.py:107-109 does every frame) and whose feature groups carry no weight decay
@@ -210,6 +238,9 @@ class GraphedIteration(metaclass=_IterationTerms):
         self.normal_loss = None
         if self.normal is not None:
             self._init_normal(can_fold)
+        self.consistency_loss = self.consistency_draws = None
+        if self.consistency is not None:
+            self._init_consistency(can_fold)
         self.ran_eager = (not self.native) and (bool(eager_first) or dev_key not in _WARMED or not can_fold)
         if can_fold:
             # the optimiser's device-side step state up front: the eager warm-up iteration then runs the SAME two launches the
@@ -274,6 +305,28 @@ class GraphedIteration(metaclass=_IterationTerms):
         self._normal_out = torch.zeros(1, dtype=torch.float32, device=dev)
         self.normal_loss = self._normal_out[0]
 
+    def _check_consistency(self, can_fold):
+        term = self.consistency
+        if not can_fold:
+            raise ValueError("GraphedIteration(consistency=...) needs the folded iteration (fold=True, a FusedAdam optimiser)")
+        if self.regularize:
+            raise ValueError("GraphedIteration(consistency=...) is not served with lambda_forget != 0: the reference regularises "
+                             "the rows of its last query_feature call (coord_near's), an accident of call order")
+        if int(term.count) < 0 or not float(term.shift_scale) >= 0.0:
+            raise ValueError("ConsistencyTerm: count >= 0 and shift_scale >= 0 (consistency_range * scale)")
+
+    def _init_consistency(self, can_fold):
+        """the consistency term's buffers, all made here: a captured graph bakes their addresses in"""
+        term = self.consistency
+        self.native = False  # (the library-built graph holds the two-launch iteration)
+        dev = self.pool.coord.device
+        k = self._consistency_k = min(int(term.count), self.n)
+        self._consistency_ws = _lib.zeroed_workspace(CONSISTENCY_WORKSPACE_BYTES, dev)  # (its own: the graph holds the address)
+        self._consistency_out = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._consistency_state = torch.zeros(1, dtype=torch.int64, device=dev)  # the pairs' stream id, advanced by the kernel
+        self.consistency_draws = (torch.zeros(k, dtype=torch.int32, device=dev), torch.zeros((k, 3), dtype=torch.float32, device=dev))
+        self.consistency_loss = self._consistency_out[0]
+
     def _graph_1(self):
         if self.graph is None:
             self.graph, self._out_1 = _capture(self._body)
@@ -329,7 +382,7 @@ class GraphedIteration(metaclass=_IterationTerms):
                                       idx=idx, touched=self.touched, pending=pending, graph=graph)
         if keep is not None:
             keep["pending"] = pending  # (every device buffer the nodes name stays alive with this object)
-        if self.sem is not None or self.normal is not None:
+        if self.sem is not None or self.normal is not None or self.consistency is not None:
             return self._terms_tail(idx, fold, pending, loss)
         if fold:
             self.opt.finish_iteration(pending, dict(lambda_forget=self.lambda_forget, touched=self.touched,
@@ -344,11 +397,13 @@ class GraphedIteration(metaclass=_IterationTerms):
         return loss, reg
 
     def _terms_tail(self, idx, fold, pending, loss):
-        """semantic_on / normal_loss_on: each term's step on the batch the fused step just read (its touched flags cover the same
-        rows), the tail on the feature tables + decoder — the normal term's decoder grads are in the six tensors it steps —, and,
+        """semantic_on / normal_loss_on / consistency_loss_on: each term's step on the batch the fused step just read (the fused
+        step's touched flags cover the rows of the first two; the consistency step flags the rows its shifted points add), the tail
+        on the feature tables + decoder — the normal and consistency terms' decoder grads are in the six tensors it steps —, and,
         while the semantic head trains, the head's own Adam launch"""
         if not fold:
-            raise RuntimeError("GraphedIteration(sem=... / normal=...): the optimiser has no device-side step state")
+            raise RuntimeError("GraphedIteration(sem=... / normal=... / consistency=...): the optimiser has no device-side step "
+                               "state")
         sem, head = self.sem, []
         if sem is not None:
             fused_sem_step(self.octree, sem.decoder, None, None, float(sem.weight_s), int(sem.decimation), pool=self.pool, idx=idx,
@@ -357,6 +412,12 @@ class GraphedIteration(metaclass=_IterationTerms):
         if self.normal is not None:
             fused_normal_step(self.octree, self.decoder, None, None, None, float(self.normal.weight_n), n_surf=self._surf,
                               pool=self.pool, idx=idx, out=self._normal_out, workspace=self._normal_ws)
+        if self.consistency is not None:  # (last: its flags join the fused step's before the tail reads them)
+            term = self.consistency
+            fused_consistency_step(self.octree, self.decoder, None, float(term.weight_c), n_pairs=self._consistency_k,
+                                   shift_scale=float(term.shift_scale), seed=int(term.seed), draw_state=self._consistency_state,
+                                   pool=self.pool, idx=idx, touched=self.touched, out=self._consistency_out,
+                                   workspace=self._consistency_ws, draws_out=self.consistency_draws)
         self.opt.finish_iteration(pending, dict(lambda_forget=self.lambda_forget, touched=self.touched,
                                                 out=self._reg_out) if self.regularize else None,
                                   next_draw=self.pool.next_draw(self.n, self._idx, self._surf) if self._ahead else None,

@@ -185,6 +185,29 @@ def normal_loss(g, normal_label, weight):
     return torch.where(surf, per, torch.zeros_like(per)).sum() / surf.sum().clamp_min(1).to(g.dtype)
 
 
+def consistency_loss(g_base, g_near):
+    """The gradient-consistency term of the drivers' consistency_loss_on branch (shine_batch.py:149-158,187-190):
+
+        c_k = (ga . gb) / (|ga| |gb|) where |ga| > 0 and |gb| > 0, else 0;  loss = mean over the K pairs of (1 - c_k)  (0 for K = 0)
+
+    g_base [K,3] = get_gradient at the base points coord[near_index], g_near [K,3] = get_gradient at the shifted points (times
+    sigma_sigmoid or not: the factor cancels).  The value is the reference's (1 - F.cosine_similarity(g_near, g_base)).mean(); THE
+    GUARD differs: a pair with either gradient exactly zero — a point that misses every level, dead units — contributes 1 and gets
+    NO gradient on either side, where the reference's line hands the zero side gbh / eps with eps = 1e-8, a finite but 1e8-scaled
+    push into every weight the row's second-order path reaches.  Plain differentiable torch with no host sync: the composite
+    ops.fused_consistency_step (Tier B, one HIP launch) is checked against, and what a Tier A driver calls in place of the
+    reference's F.cosine_similarity line."""
+    if g_base.shape[0] == 0:
+        return (g_base.sum() + g_near.sum()) * 0.0
+    na, nb = g_base.norm(2, dim=-1, keepdim=True), g_near.norm(2, dim=-1, keepdim=True)
+    live = (na > 0) & (nb > 0)
+    one = torch.ones_like(na)
+    ah = g_base / torch.where(live, na, one)
+    bh = g_near / torch.where(live, nb, one)
+    c = torch.where(live.squeeze(-1), (ah * bh).sum(-1), torch.zeros_like(na.squeeze(-1)))
+    return (1.0 - c).sum() / g_base.shape[0]
+
+
 def get_gradient(inputs, outputs):
     """utils/tools.py:175-185: d outputs / d inputs with create_graph=True.  For the pred of the fused query_feature -> sdf
     node and its own coord: one launch (autograd_ops.InterpSdfGradCoord); otherwise the reference's autograd call."""

@@ -470,6 +470,134 @@ def fused_normal_step(octree, decoder, coord, weight, normal_label, weight_n, n_
     return out.view(())
 
 
+def fused_consistency_step(octree, decoder, coord, weight_c, near_index=None, shift=None, n_pairs=None, shift_scale=None, seed=0,
+                           draw_state=None, pool=None, idx=None, touched=None, grad_buffers=None, out=None, workspace=None,
+                           draws_out=None):
+    """The gradient-consistency term of one training iteration (shine_batch.py:149-158,187-190) in ONE launch
+    (shine_consistency_train_step):
+
+        a = coord[near_index];  b = a + shift;  ga, gb = get_gradient at a, b (through the decoder's sdf of the queried features)
+        consistency_loss = losses.consistency_loss(ga, gb);  (weight_c * consistency_loss).backward()
+
+    — the definition of losses.consistency_loss: the mean over the K pairs of 1 - cos(ga, gb), a pair with either gradient exactly
+    zero contributing 1 and getting no gradient (the reference's line pushes gbh / 1e-8 into the zero side).  Every batch row can
+    be a base point, free-space rows included; no weight, no label and no sigma enter.
+    Array mode: coord [N,3] float32, optionally idx (CUDA int32: batch row i is coord[idx[i]]).  Pool mode: pool = a SortedPool
+    and idx = pool.draw(n): the base rows are read straight out of the pool's records (coord is ignored).
+    Explicit pairs: near_index (CUDA int32 [K], values in [0, n) — batch rows, repeats allowed) and shift (CUDA float32 [K,3]).
+    Drawn pairs: both None — the kernel draws K = n_pairs pairs itself from (seed, draw_state[0]) with each shift component in
+    [-shift_scale, shift_scale) (the reference's consistency_range * scale) and advances draw_state (a CUDA int64 tensor of one
+    element the caller owns) by one, so a replayed graph draws fresh pairs every time.  `draws_out` = (int32 [K], float32 [K,3])
+    receives the pairs the launch used.
+    `touched`: the per-level uint8 row flags of ops.touched_flags(octree); every row the term adds gradient to is flagged (the
+    shifted points reach rows the batch's own points do not, and the active-row Adam skips an unflagged row).
+    Returns the UNWEIGHTED consistency_loss as a 0-dim float32 device tensor (no host sync, no grad_fn — the gradients are
+    already in place; `out`: a float32 tensor of one element to write it to).  Accumulates into ``.grad`` of
+    octree.hier_features[*] and of the decoder's W1, W2, w3 exactly as fused_normal_step does, or into `grad_buffers` = (L
+    feature-grad tensors, 6 decoder-grad tensors | None) instead.  A decoder whose parameters do not require grad gets no
+    gradient: only the feature grads are written.
+    `workspace`: SHINE_CONSISTENCY_WORKSPACE_BYTES of zeroed device memory the caller owns (default: the current stream's,
+    autograd_ops.consistency_workspace)."""
+    t = octree._require_tables()  # (the kernel probes the hash tables from the coordinates)
+    mlp = decoder.fused_params()
+
+    def _i32(x):
+        return isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.int32 and x.is_contiguous()
+
+    def _f32k3(x):
+        return (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 2
+                and x.shape[1] == 3)
+
+    if pool is not None:
+        if idx is None or not _i32(idx):
+            raise ValueError("pool mode needs idx = SortedPool.draw(n) (CUDA int32)")
+        if pool.tables_epoch != octree._tables_epoch:
+            raise RuntimeError("the octree grew since the pool was planned: call SortedPool.rebuild()")
+        if getattr(pool, "rec", None) is not None:
+            src, stride = pool.rec, 8
+        else:
+            src, stride = pool.soa()[0], 3
+        n = int(idx.numel())
+    else:
+        if not isinstance(coord, torch.Tensor):
+            raise ValueError("array mode needs coord [N,3] (or pool= and idx=)")
+        src, stride = octree._check_coord(coord.detach()), 3
+        n = int(src.shape[0])
+        if idx is not None:
+            if not _i32(idx):
+                raise ValueError("idx must be a contiguous CUDA int32 tensor")
+            n = int(idx.numel())
+    if (near_index is None) != (shift is None):
+        raise ValueError("near_index and shift come together (both: explicit pairs; neither: drawn pairs)")
+    explicit = near_index is not None
+    if explicit:
+        if not (_i32(near_index) and near_index.dim() == 1):
+            raise ValueError("near_index must be a contiguous CUDA int32 [K] tensor")
+        k = int(near_index.numel())
+        if not (_f32k3(shift) and shift.shape[0] == k):
+            raise ValueError("shift must be a contiguous CUDA float32 [K,3] tensor, one row per near_index entry")
+        if n_pairs is not None and int(n_pairs) != k:
+            raise ValueError("n_pairs must equal the number of explicit pairs")
+    else:
+        if n_pairs is None or int(n_pairs) < 0:
+            raise ValueError("drawn pairs need n_pairs >= 0")
+        k = int(n_pairs)
+        if shift_scale is None or not float(shift_scale) >= 0.0:
+            raise ValueError("drawn pairs need shift_scale >= 0 (consistency_range * scale)")
+        if not (isinstance(draw_state, torch.Tensor) and draw_state.is_cuda and draw_state.dtype == torch.int64
+                and draw_state.numel() == 1):
+            raise ValueError("drawn pairs need draw_state: a CUDA int64 tensor of one element")
+    if k > 0 and n == 0:
+        raise ValueError("pairs need a batch: n_pairs > 0 with no batch row")
+    dev = src.device
+    ni_out = sh_out = None
+    if draws_out is not None:
+        ni_out, sh_out = draws_out
+        if not (_i32(ni_out) and ni_out.numel() >= k and _f32k3(sh_out) and sh_out.shape[0] >= k):
+            raise ValueError("draws_out = (CUDA int32 [K], CUDA float32 [K,3])")
+    if touched is not None and not (len(touched) == octree.featured_level_num
+                                    and all(x.is_cuda and x.dtype == torch.uint8 for x in touched)):
+        raise ValueError("touched = ops.touched_flags(octree): one CUDA uint8 tensor per featured level")
+    if not decoder._params_on(dev, mlp):
+        raise ValueError("the decoder's parameters must be CUDA float32 contiguous on the batch's device")
+    gfeat, gmlp = grad_buffers if grad_buffers is not None else (None, None)
+    if gfeat is None:
+        gfeat = [_dense_grad(p) if p.requires_grad else None for p in octree.feature_list()]
+    if grad_buffers is None:
+        train = [p.requires_grad for p in mlp]
+        if any(train) != all(train):
+            raise ValueError("the decoder's six tensors must all require grad or all be frozen")
+        gmlp = [_dense_grad(p) for p in mlp] if all(train) else None
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.numel() == 1):
+        raise ValueError("out must be a CUDA float32 tensor of one element")
+    if k == 0:  # (what the entry point does for n_pairs == 0; empty explicit tensors have no address to hand it)
+        out.zero_()
+        return out.view(())
+    ws = workspace if workspace is not None else autograd_ops.consistency_workspace(dev)
+    cfg = octree.step_config()
+    _lib.check(
+        _lib.lib().shine_consistency_train_step(
+            t.handle, C.byref(cfg), src.data_ptr(), stride, idx.data_ptr() if idx is not None else None, n,
+            near_index.data_ptr() if explicit else None, shift.data_ptr() if explicit else None, k,
+            float(shift_scale) if shift_scale is not None else 0.0, int(seed) & 0xFFFFFFFFFFFFFFFF,
+            draw_state.data_ptr() if (draw_state is not None and not explicit) else None,
+            ni_out.data_ptr() if ni_out is not None else None, sh_out.data_ptr() if sh_out is not None else None,
+            float(weight_c), octree.feature_ptrs(), octree.row_counts(),
+            _lib.ptr_array([g.data_ptr() if g is not None else None for g in gfeat]),
+            _lib.ptr_array([p.data_ptr() for p in mlp]),
+            _lib.ptr_array([g.data_ptr() for g in gmlp]) if gmlp is not None else None,
+            _lib.ptr_array([x.data_ptr() for x in touched]) if touched is not None else None,
+            out.data_ptr(), ws.data_ptr(), _stream(),
+        ),
+        "shine_consistency_train_step",
+    )
+    if not torch.cuda.is_current_stream_capturing():
+        octree._tables_read_done()
+    return out.view(())
+
+
 def octree_interp(octree, coord):
     """FeatureOctree.query_feature (model/feature_octree.py:237-244) -> [N,8]; also fills hierarchical_indices."""
     needs_grad = torch.is_grad_enabled() and (
