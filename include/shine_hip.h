@@ -421,6 +421,20 @@ int shine_mlp_backward(const float* feat, const float* grad_pred, int64_t n, con
 int shine_mlp_backward_backward(const float* feat, const float* grad_pred, const float* gg_feat, int64_t n,
                                 const float* const* mlp, float* grad_gpred_out, float* const* grad_mlp, void* stream);
 
+/* ---- Tier A: Decoder.time_conditionded_sdf (model/decoder.py:65-81; the 4D maps of config.time_conditioned,
+ *      shine_batch.py:41,127-130,248-264) as the same twice-differentiable trio.  ts [N] = the time input of every point
+ *      (no gradient); mlp[0] is nn.Linear(9, 32).weight read in place, [32][9] = [W1f | w_t], and grad_mlp[0] has its shape;
+ *      everything else as above (feat, grad_feat_out and gg_feat stay [N,8]).  W1f f + w_t ts + b1 makes the time input a
+ *      per-point shift of the first bias: _backward adds sum_i ts_i d1_i to grad_mlp[0][:,8]; _backward_backward sends
+ *      nothing to that column nor to the biases (the ReLU masks are piecewise constant).  No workspace. ------------ */
+int shine_time_mlp_forward(const float* feat, const float* ts, int64_t n, const float* const* mlp, float* pred_out,
+                           void* stream);
+int shine_time_mlp_backward(const float* feat, const float* ts, const float* grad_pred, int64_t n,
+                            const float* const* mlp, float* grad_feat_out, float* const* grad_mlp, void* stream);
+int shine_time_mlp_backward_backward(const float* feat, const float* ts, const float* grad_pred, const float* gg_feat,
+                                     int64_t n, const float* const* mlp, float* grad_gpred_out, float* const* grad_mlp,
+                                     void* stream);
+
 /* ---- Tier A, fused: backward of { FeatureOctree.query_feature (model/feature_octree.py:237-244) -> Decoder.sdf
  *      (model/decoder.py:49-63) } for a given grad_pred [N] = d loss / d pred — what autograd derives for
  *      cur_loss.backward() (shine_batch.py:208-209) through those two calls when the driver is unchanged: decoder

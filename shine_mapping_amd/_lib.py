@@ -168,6 +168,9 @@ _SIGNATURES = {
     "shine_mlp_forward": (C.c_int, [_P, C.c_int64, C.POINTER(_P), _P, _P]),
     "shine_mlp_backward": (C.c_int, [_P, _P, C.c_int64, C.POINTER(_P), _P, C.POINTER(_P), _P]),
     "shine_mlp_backward_backward": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(_P), _P, C.POINTER(_P), _P]),
+    "shine_time_mlp_forward": (C.c_int, [_P, _P, C.c_int64, C.POINTER(_P), _P, _P]),
+    "shine_time_mlp_backward": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(_P), _P, C.POINTER(_P), _P]),
+    "shine_time_mlp_backward_backward": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.POINTER(_P), _P, C.POINTER(_P), _P]),
     "shine_interp_backward": (
         C.c_int, [_P, C.POINTER(StepConfig), _P, C.c_int64, C.POINTER(_P), C.POINTER(C.c_int64), _P, _P,
                   C.POINTER(_P), _P]),

@@ -251,6 +251,102 @@ class FusedMLPBackward(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# Tier A: Decoder.time_conditionded_sdf (model/decoder.py:65-81) — the same three launches with one scalar per point
+# ----------------------------------------------------------------------------------------------------------------------
+
+
+class FusedTimeMLP(torch.autograd.Function):
+    """pred[N] = w3 . relu(W2 relu(W1f feat + w_t ts + b1) + b2) + b3   (shine_time_mlp_forward).  Inputs: feat [N,8], ts (N
+    elements, no gradient), then the six decoder tensors with W1 = [W1f | w_t] [32,9].  Backward is FusedTimeMLPBackward (itself
+    differentiable), as FusedMLP's."""
+
+    @staticmethod
+    def forward(ctx, feat, ts, *mlp):
+        f, t = _f32c(feat), _f32c(ts).reshape(-1)
+        w = [_f32c(p) for p in mlp]
+        n = f.shape[0]
+        pred = torch.empty(n, dtype=torch.float32, device=f.device)
+        _lib.check(
+            _lib.lib().shine_time_mlp_forward(f.data_ptr(), t.data_ptr(), n, _lib.ptr_array([p.data_ptr() for p in w]),
+                                              pred.data_ptr(), _stream()),
+            "shine_time_mlp_forward",
+        )
+        ctx.save_for_backward(feat, t, *mlp)
+        return pred
+
+    @staticmethod
+    def backward(ctx, g):
+        feat, ts, *mlp = ctx.saved_tensors
+        need_w = any(ctx.needs_input_grad[2:])
+        outs = FusedTimeMLPBackward.apply(g, feat, ts, ctx.needs_input_grad[0], need_w, *mlp)
+        grad_feat = outs[0] if ctx.needs_input_grad[0] else None
+        grads = tuple(o if need else None for o, need in zip(outs[1:], ctx.needs_input_grad[2:]))
+        return (grad_feat, None) + grads
+
+
+class FusedTimeMLPBackward(torch.autograd.Function):
+    """(grad_feat [N,8], gW1 [32,9], gb1, gW2, gb2, gw3, gb3) = backward of FusedTimeMLP (shine_time_mlp_backward), differentiable
+    wrt g and the weights through grad_feat (shine_time_mlp_backward_backward: nothing reaches gW1[:,8] or the biases there).
+    Second derivatives THROUGH the weight-grad outputs raise, as FusedMLPBackward's."""
+
+    @staticmethod
+    def forward(ctx, g, feat, ts, want_feat, want_w, *mlp):
+        f, gc = _f32c(feat), _f32c(g)
+        w = [_f32c(p) for p in mlp]
+        n = f.shape[0]
+        dev = f.device
+        grad_feat = torch.empty((n, 8), dtype=torch.float32, device=dev) if want_feat else None
+        gw = [torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format) for p in mlp] \
+            if want_w else None
+        _lib.check(
+            _lib.lib().shine_time_mlp_backward(
+                f.data_ptr(), ts.data_ptr(), gc.data_ptr(), n, _lib.ptr_array([p.data_ptr() for p in w]),
+                grad_feat.data_ptr() if want_feat else None,
+                _lib.ptr_array([t.data_ptr() for t in gw]) if want_w else None, _stream(),
+            ),
+            "shine_time_mlp_backward",
+        )
+        ctx.save_for_backward(g, feat, ts, *mlp)
+        ctx.set_materialize_grads(False)
+        if grad_feat is None:
+            grad_feat = torch.zeros((0, 8), dtype=torch.float32, device=dev)
+        if gw is None:
+            gw = [torch.zeros(0, dtype=torch.float32, device=dev) for _ in mlp]
+        return (grad_feat,) + tuple(gw)
+
+    @staticmethod
+    def backward(ctx, gg_feat, *gg_w):
+        if any(x is not None for x in gg_w):
+            raise NotImplementedError("second derivatives through the decoder's weight gradients are not implemented")
+        g, feat, ts, *mlp = ctx.saved_tensors
+        none = (None,) * (5 + len(mlp))
+        if gg_feat is None:
+            return none
+        need_g = ctx.needs_input_grad[0]
+        need_w = any(ctx.needs_input_grad[5:])
+        if not (need_g or need_w):
+            return none
+        f, gc, r = _f32c(feat), _f32c(g), _f32c(gg_feat)
+        w = [_f32c(p) for p in mlp]
+        n = f.shape[0]
+        grad_g = torch.empty(n, dtype=torch.float32, device=f.device) if need_g else None
+        gw = [torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format) for p in mlp] \
+            if need_w else None
+        _lib.check(
+            _lib.lib().shine_time_mlp_backward_backward(
+                f.data_ptr(), ts.data_ptr(), gc.data_ptr(), r.data_ptr(), n, _lib.ptr_array([p.data_ptr() for p in w]),
+                grad_g.data_ptr() if need_g else None,
+                _lib.ptr_array([t.data_ptr() for t in gw]) if need_w else None, _stream(),
+            ),
+            "shine_time_mlp_backward_backward",
+        )
+        grads = tuple(t if need else None for t, need in zip(gw, ctx.needs_input_grad[5:])) if need_w \
+            else (None,) * len(mlp)
+        # inputs: g, feat, ts, want_feat, want_w, *mlp   (relu masks are piecewise constant: nothing flows to feat or ts)
+        return (grad_g, None, None, None, None) + grads
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # Tier A, fused across the query_feature -> sdf boundary
 # ----------------------------------------------------------------------------------------------------------------------
 

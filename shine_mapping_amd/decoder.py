@@ -7,8 +7,10 @@ one launch each — get_gradient(create_graph=True), utils/tools.py:175-185, dif
 decoder shape every shipped config uses (8 -> 32 -> 32 -> 1 with bias) on CUDA float32 input; the benchmarked
 tier never calls it — the fused HIP step reads the six parameter tensors directly (ops.train_step).
 `sem_label_prob` / `sem_label` of the semantic decoder (semantic_on) are HIP launches for the same hidden shape with up to 32
-classes (csrc/shine_semantic.hip).  The time-conditioned head and other decoder shapes are plain torch composites, as in the
-reference.
+classes (csrc/shine_semantic.hip).  `time_conditionded_sdf` of the time-conditioned head (9 -> 32 -> 32 -> 1 with bias) is the
+same kind of twice-differentiable HIP op (autograd_ops.FusedTimeMLP, csrc/shine_time_mlp.hip: the time input is a per-point shift
+of the first bias), and `fused_params_at(ts)` folds one time stamp into that bias for the 8-wide query kernels the Mesher uses.
+Other decoder shapes are plain torch composites, as in the reference.
 """
 import weakref
 
@@ -17,7 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _ext, _lib, autograd_ops
-from .autograd_ops import FusedInterpSdf, FusedMLP
+from .autograd_ops import FusedInterpSdf, FusedMLP, FusedTimeMLP
 
 
 class Decoder(nn.Module):
@@ -36,6 +38,10 @@ class Decoder(nn.Module):
         self.fusable = (
             level == 2 and hidden == _lib.HIDDEN_DIM and in_dim == _lib.FEATURE_DIM and bias_on
             and not is_time_conditioned
+        )
+        self.time_fusable = (
+            level == 2 and hidden == _lib.HIDDEN_DIM and in_dim == _lib.FEATURE_DIM + 1 and bias_on
+            and is_time_conditioned
         )
         self.to(config.device)
 
@@ -78,6 +84,18 @@ class Decoder(nn.Module):
 
     # model/decoder.py:65-81
     def time_conditionded_sdf(self, sum_features, ts):
+        """The time-conditioned head 9 -> 32 -> 32 -> 1 with bias on CUDA float32 [N,8] features and a ts of N elements that asks
+        for no gradient (any shape; cast to float32) is a twice-differentiable HIP op (autograd_ops.FusedTimeMLP); anything else
+        is the reference's composite."""
+        if (self.time_fusable and sum_features.is_cuda and sum_features.dtype == torch.float32 and sum_features.dim() == 2
+                and sum_features.shape[1] == _lib.FEATURE_DIM and sum_features.shape[0] > 0
+                and ts.numel() == sum_features.shape[0] and ts.device == sum_features.device and not ts.requires_grad):
+            mlp = self._layer_params()
+            if self._params_on(sum_features.device, mlp):
+                return FusedTimeMLP.apply(sum_features, ts, *mlp)
+        return self._time_composite(sum_features, ts)
+
+    def _time_composite(self, sum_features, ts):
         h = torch.cat((sum_features, ts.view(-1, 1)), dim=1)
         for l in self.layers:
             h = F.relu(l(h))
@@ -145,9 +163,23 @@ class Decoder(nn.Module):
         """W1,b1,W2,b2,w3,b3 in the order libshine_hip expects."""
         if not self.fusable:
             raise NotImplementedError("fused HIP decoder supports 8 -> 32 -> 32 -> 1 with bias (every shipped config)")
+        return self._layer_params()
+
+    def _layer_params(self):
         # (plain dict lookups: nn.Module.__getattr__ / ModuleList.__getitem__ cost ~1 us per hop, and the small-batch loop asks
         # for these six tensors half a dozen times per iteration)
         m = self._modules
         hidden = m["layers"]._modules
         l0, l1, lo = hidden["0"]._parameters, hidden["1"]._parameters, m["lout"]._parameters
         return [l0["weight"], l0["bias"], l1["weight"], l1["bias"], lo["weight"], lo["bias"]]
+
+    def fused_params_at(self, ts):
+        """The time-conditioned head at ONE time stamp `ts` (a Python or 0-dim scalar) as a plain 8 -> 32 -> 32 -> 1 decoder, six
+        detached tensors in fused_params() order: W1 [32,9] = [W1f | w_t] and W1f f + w_t ts + b1 = W1f f + (b1 + w_t ts), so
+        W1f = W1[:, :8] (a contiguous copy), b1' = b1 + w_t ts and the other four as they are (utils/mesher.py:71-74,94-97 decode
+        every grid point at self.ts)."""
+        if not self.time_fusable:
+            raise NotImplementedError("fused_params_at needs the time-conditioned head 9 -> 32 -> 32 -> 1 with bias")
+        W1, b1, W2, b2, w3, b3 = [p.detach() for p in self._layer_params()]
+        nf = _lib.FEATURE_DIM
+        return [W1[:, :nf].contiguous(), b1 + W1[:, nf] * ts, W2, b2, w3, b3]

@@ -16,6 +16,9 @@ open3d TriangleMesh when open3d can be imported, else as this module's `Triangle
 A map whose dense grid does not fit the device is meshed from BRICKS instead (`marching_cubes_sparse`, csrc/shine_mc_sparse.hip):
 only the node blocks (octree route) or the tiles near existing nodes (box route) are queried and kept, and the mesh is the dense
 route's bit for bit.  `recon_octree_mesh` / `recon_bbx_mesh` pick the route with their `sparse` keyword.
+
+With `config.time_conditioned` (utils/mesher.py:29,71-74,94-97) the queries decode at `Mesher.ts`: the time stamp is folded into the
+decoder's first bias once per call (`Decoder.fused_params_at`) and the same kernels run.
 """
 from __future__ import annotations
 
@@ -29,8 +32,10 @@ from . import _lib
 from .ops import _stream
 
 
-def query_points_device(octree, decoder, coord, check_level=0, negate=True, query_sdf=True, query_mask=True):
-    """One launch over `coord [N,3]` (device, scaled to [-1,1]); returns device tensors (sdf f32 | None, mask bool | None)."""
+def query_points_device(octree, decoder, coord, check_level=0, negate=True, query_sdf=True, query_mask=True, mlp=None):
+    """One launch over `coord [N,3]` (device, scaled to [-1,1]); returns device tensors (sdf f32 | None, mask bool | None).
+    `mlp`: the six tensors to decode with instead of decoder.fused_params() — a time-conditioned head folded at one time stamp
+    (Decoder.fused_params_at), which this 8 -> 32 -> 32 -> 1 kernel then serves unchanged."""
     t = octree._require_tables()
     coord = octree._check_coord(coord.detach())
     n = coord.shape[0]
@@ -38,7 +43,10 @@ def query_points_device(octree, decoder, coord, check_level=0, negate=True, quer
     sdf = torch.empty(n, dtype=torch.float32, device=dev) if query_sdf else None
     mask = torch.empty(n, dtype=torch.uint8, device=dev) if query_mask else None
     cfg = octree.step_config()
-    mlp = [p.detach() for p in decoder.fused_params()] if query_sdf else None
+    if not query_sdf:
+        mlp = None
+    elif mlp is None:
+        mlp = [p.detach() for p in decoder.fused_params()]
     _lib.check(
         _lib.lib().shine_query_points(
             t.handle, C.byref(cfg), coord.data_ptr(), n, octree.feature_ptrs(), octree.row_counts(),
@@ -524,8 +532,7 @@ class Mesher:
 
     def query_points(self, coord, bs, query_sdf=True, query_sem=False, query_mask=True):
         """utils/mesher.py:33-108.  Returns (sdf_pred, sem_pred, mc_mask) as numpy arrays (None when not asked for)."""
-        if getattr(self.config, "time_conditioned", False):
-            raise NotImplementedError("time-conditioned decoding is outside the SDF hot path")
+        mlp = self._decoder_params() if query_sdf else None  # (folded once per call, not per chunk)
         sample_count = coord.shape[0]
         iter_n = math.ceil(sample_count / bs)
         check_level = min(self.octree.featured_level_num, self.config.mc_vis_level) - 1
@@ -540,7 +547,7 @@ class Mesher:
                     chunk = coord[head:tail].to(dev)
                     if query_sdf or query_mask:
                         sdf, mask = query_points_device(self.octree, self.geo_decoder, chunk, check_level, True, query_sdf,
-                                                        query_mask)
+                                                        query_mask, mlp)
                     if query_sdf:
                         sdf_pred[head:tail] = sdf.cpu().numpy()
                     if query_sem:
@@ -551,7 +558,7 @@ class Mesher:
                 sdf = mask = None
                 if query_sdf or query_mask:
                     sdf, mask = query_points_device(self.octree, self.geo_decoder, coord.to(dev), check_level, True,
-                                                    query_sdf, query_mask)
+                                                    query_sdf, query_mask, mlp)
                 sdf_pred = sdf.cpu().numpy() if query_sdf else None
                 # (the reference's unchunked branch returns the int64 array of .cpu().numpy(), :98)
                 sem_pred = query_labels_device(self.octree, self.sem_decoder, coord.to(dev)).cpu().numpy() if query_sem else None
@@ -677,11 +684,12 @@ class Mesher:
         dev = self.octree.hier_features[0].device
         sdf = torch.empty(n, dtype=torch.float32, device=dev)
         mask = torch.empty(n, dtype=torch.bool, device=dev) if query_mask else None
+        mlp = self._decoder_params()
         with torch.no_grad():
             for head in range(0, n, QUERY_CHUNK):
                 tail = min(head + QUERY_CHUNK, n)
                 s, m = query_points_device(self.octree, self.geo_decoder, coord[head:tail].to(dev), check_level, True, True,
-                                           query_mask)
+                                           query_mask, mlp)
                 sdf[head:tail] = s
                 if query_mask:
                     mask[head:tail] = m
@@ -689,6 +697,14 @@ class Mesher:
 
     def _check_level(self):
         return min(self.octree.featured_level_num, self.config.mc_vis_level) - 1
+
+    def _decoder_params(self):
+        """what query_points_device decodes with: None (the decoder's own six tensors) or, with config.time_conditioned, the head
+        at self.ts (utils/mesher.py:29,71-74,94-97) folded into an 8-wide decoder.  Asked for once per public call, before its
+        chunks: self.ts is read at call time and the fold is two small torch ops."""
+        if getattr(self.config, "time_conditioned", False):
+            return self.geo_decoder.fused_params_at(self.ts)
+        return None
 
     def _bbx_layout(self, bbx, voxel_size):
         """utils/mesher.py:113-121: the box grid, padded, one extra layer underground: (shape [3], voxel_origin [3] metres)"""
@@ -725,6 +741,7 @@ class Mesher:
         top = torch.as_tensor(np.asarray(shape, np.int64) - 1, device=dev)
         origin_t = torch.tensor(voxel_origin, dtype=self.dtype, device=dev)
         per = max(1, QUERY_CHUNK // (B ** 3))
+        mlp = self._decoder_params()
         with torch.no_grad():
             for h in range(0, n, per):
                 t = min(h + per, n)
@@ -734,7 +751,7 @@ class Mesher:
                 coord *= voxel_size
                 coord += origin_t
                 coord *= self.world_scale
-                s, m = query_points_device(self.octree, self.geo_decoder, coord, check_level, True, True, True)
+                s, m = query_points_device(self.octree, self.geo_decoder, coord, check_level, True, True, True, mlp)
                 values[h:t] = s.view(-1, B, B, B)
                 mask[h:t] = m.view(-1, B, B, B)
         return values, mask, origins, tuple(int(v) for v in shape), voxel_origin
@@ -743,8 +760,6 @@ class Mesher:
         """what recon_bbx_mesh and recon_octree_mesh share: the route (`sparse` None: bricks iff the dense grid of fits_shape(), a
         shape or None for "do not ask", does not fit), the route's marching cubes — dense_fn / brick_fn return (verts, faces,
         voxel size m, origin m) — and _finish with its remaining arguments `finish`."""
-        if getattr(self.config, "time_conditioned", False):
-            raise NotImplementedError("time-conditioned decoding is outside the SDF hot path")
         if sparse is None:
             shape = fits_shape()
             if shape is not None:
@@ -835,12 +850,13 @@ class Mesher:
         mask_on = bool(getattr(self.config, "mc_mask_on", True))
         check_level = self._check_level()
         per = max(1, QUERY_CHUNK // (k ** 3))
+        mlp = self._decoder_params()
         for h in range(0, len(nodes), per):
             t = min(h + per, len(nodes))
             # cur_coord += cur_origin (:329-330): a float32 tensor plus a float64 one, computed in double, stored as float32
             coord = (block64[None] + origins[h:t, None, :]).float().reshape(-1, 3)
             with torch.no_grad():
-                s, m = query_points_device(self.octree, self.geo_decoder, coord, check_level, True, True, mask_on)
+                s, m = query_points_device(self.octree, self.geo_decoder, coord, check_level, True, True, mask_on, mlp)
             yield h, t, s.half().float(), m
 
     def octree_grid_device(self, query_level, mc_res_m):
@@ -896,7 +912,8 @@ class Mesher:
         requeried_nodes, requeried_points, full, reason ("first" / "key" / "decoder" / "octree" when the cache was rebuilt from
         nothing, else None), and changed_rows per level, the count shine_rows_diff leaves next to them.  The cache costs the size of the feature tables plus 5 bytes per grid point."""
         if getattr(self.config, "time_conditioned", False):
-            raise NotImplementedError("time-conditioned decoding is outside the SDF hot path")
+            raise NotImplementedError("update_octree_mesh keeps one block cache, not one per time stamp: mesh a time-conditioned "
+                                      "map with recon_octree_mesh")
         try:
             return self._update_octree_mesh(query_level, mc_res_m, mesh_path, estimate_sem, estimate_normal, filter_isolated_mesh,
                                             filter_free_space_vertices)
