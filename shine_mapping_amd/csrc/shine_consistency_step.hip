@@ -22,6 +22,7 @@
 // TOUCHED-ROW FLAGS: the shifted points reach corner rows the batch's own points did not; with the exact active-row Adam the
 // tail neither steps nor clears a row whose flag is 0 (shine_finish.hip), so every live lane flags the rows it scatters to.
 #include "shine_gterm_body.hpp"
+#include "shine_term_host.hpp"
 
 namespace shine {
 namespace {
@@ -146,13 +147,6 @@ __global__ __launch_bounds__(kThreads) void k_consistency_step(const Consistency
   gterm_step<L, POLY, ConsistencyPolicy>(a, s_stage, s_loss, &s_flag);
 }
 
-template <int L>
-void launch_consistency_step(const ConsistencyArgs& a, bool poly, hipStream_t st) {
-  const dim3 grid(gterm_blocks((a.n_pairs + 31) / 32));
-  if (poly) hipLaunchKernelGGL((k_consistency_step<L, true>), grid, dim3(kThreads), 0, st, a);
-  else hipLaunchKernelGGL((k_consistency_step<L, false>), grid, dim3(kThreads), 0, st, a);
-}
-
 }  // namespace
 }  // namespace shine
 
@@ -165,45 +159,23 @@ extern "C" int shine_consistency_train_step(const shine_tables* t, const shine_s
                                             const float* const* feats, const int64_t* rows, float* const* grad_feats,
                                             const float* const* mlp, float* const* grad_mlp, unsigned char* const* touched,
                                             float* consistency_loss_out, void* workspace, void* stream) {
-  if (!t) return set_error(SHINE_E_INVALID, "shine_consistency_train_step: null table handle");
-  if (!cfg) return set_error(SHINE_E_INVALID, "shine_consistency_train_step: null config");
-  if (coord_stride != 3 && coord_stride != 8)
-    return set_error(SHINE_E_INVALID, "shine_consistency_train_step: coord_stride is 3 ([n,3] array) or 8 (32-byte pool records)");
-  if (n < 0) return set_error(SHINE_E_INVALID, "shine_consistency_train_step: n < 0");
-  if (n >= (1ll << 31)) return set_error(SHINE_E_INVALID, "shine_consistency_train_step: n exceeds 2^31 - 1 rows");
-  if (n_pairs < 0) return set_error(SHINE_E_INVALID, "shine_consistency_train_step: n_pairs < 0");
-  if ((near_index != nullptr) != (shift != nullptr))
-    return set_error(SHINE_E_INVALID, "shine_consistency_train_step: near_index and shift come together (both, or neither: drawn pairs)");
-  if (!near_index && !draw_state)
-    return set_error(SHINE_E_INVALID, "shine_consistency_train_step: drawn pairs need draw_state");
-  if (n_pairs > 0 && n == 0) return set_error(SHINE_E_INVALID, "shine_consistency_train_step: n_pairs > 0 with n == 0");
-  if (!feats || !rows || !mlp || !consistency_loss_out || (n_pairs > 0 && !coord))
-    return set_error(SHINE_E_INVALID, "shine_consistency_train_step: null argument");
-  if (!workspace || ((size_t)workspace & 255)) return set_error(SHINE_E_INVALID, "shine_consistency_train_step: workspace");
+  static const char* const kEntry = "shine_consistency_train_step";
   ConsistencyArgs a = {};
-  for (int k = 0; k < 6; ++k) {
-    if (!mlp[k]) return set_error(SHINE_E_INVALID, "shine_consistency_train_step: null decoder parameter");
-    a.mlp[k] = mlp[k];
-  }
-  if (grad_mlp) {
-    for (int k = 0; k < 6; ++k)
-      if (!grad_mlp[k]) return set_error(SHINE_E_INVALID, "shine_consistency_train_step: null weight-grad tensor");
-    a.gW1 = grad_mlp[0], a.gW2 = grad_mlp[2], a.gw3 = grad_mlp[4];  // (the three biases receive nothing)
-  }
-  if (cfg->n_levels > 4) return set_error(SHINE_E_INVALID, "shine_consistency_train_step: more than 4 featured levels");
-  int rc = make_level_set(t, cfg, feats, rows, grad_feats, &a.ls);
+  int rc = term_prologue(kEntry, t, cfg, coord_stride, n, feats, rows, consistency_loss_out, workspace);
+  if (rc == SHINE_OK) rc = term_decoder(kEntry, mlp, grad_mlp, &a);
   if (rc != SHINE_OK) return rc;
-  const int L = cfg->n_levels;
-  for (int s = 0; s < L; ++s) {
-    if (!feats[s]) return set_error(SHINE_E_INVALID, "shine_consistency_train_step: null feature level");
-    if (rows[s] >= (1ll << 29)) return set_error(SHINE_E_INVALID, "shine_consistency_train_step: level exceeds 2^29 rows");
-    a.touched[s] = touched ? touched[s] : nullptr;
-  }
+  if (n >= (1ll << 31)) return term_refuse(kEntry, "n exceeds 2^31 - 1 rows");
+  if (n_pairs < 0) return term_refuse(kEntry, "n_pairs < 0");
+  if ((near_index != nullptr) != (shift != nullptr))
+    return term_refuse(kEntry, "near_index and shift come together (both, or neither: drawn pairs)");
+  if (!near_index && !draw_state) return term_refuse(kEntry, "drawn pairs need draw_state");
+  if (n_pairs > 0 && n == 0) return term_refuse(kEntry, "n_pairs > 0 with n == 0");
+  if (n_pairs > 0 && !coord) return term_refuse(kEntry, "null argument");
+  rc = term_levels(kEntry, t, cfg, feats, rows, grad_feats, &a.ls);
+  if (rc != SHINE_OK) return rc;
+  for (int s = 0; s < cfg->n_levels; ++s) a.touched[s] = touched ? touched[s] : nullptr;
   hipStream_t st = (hipStream_t)stream;
-  if (n_pairs == 0) {
-    SHINE_HIP_CHECK(hipMemsetAsync(consistency_loss_out, 0, sizeof(float), st));
-    return SHINE_OK;
-  }
+  if (n_pairs == 0) return term_empty(consistency_loss_out, st);
   a.coord = coord;
   a.idx = idx;
   a.near_index = near_index;
@@ -217,16 +189,12 @@ extern "C" int shine_consistency_train_step(const shine_tables* t, const shine_s
   a.cstride = coord_stride;
   a.shift_scale = shift_scale;
   a.weight_c = weight_c;
-  a.want_wgrad = grad_mlp ? 1 : 0;
   a.loss_out = consistency_loss_out;
   a.ws = (unsigned char*)workspace;
-  const bool poly = cfg->poly_int_on != 0;
-  switch (L) {
-    case 1: launch_consistency_step<1>(a, poly, st); break;
-    case 2: launch_consistency_step<2>(a, poly, st); break;
-    case 3: launch_consistency_step<3>(a, poly, st); break;
-    default: launch_consistency_step<4>(a, poly, st); break;
-  }
+  const dim3 grid(gterm_blocks((n_pairs + 31) / 32));
+  dispatch_levels_poly(cfg->n_levels, cfg->poly_int_on != 0, [&](auto l, auto p) {
+    hipLaunchKernelGGL((k_consistency_step<decltype(l)::value, decltype(p)::value>), grid, dim3(kThreads), 0, st, a);
+  });
   SHINE_HIP_CHECK(hipGetLastError());
   return SHINE_OK;
 }

@@ -13,6 +13,7 @@
 // Rows with weight <= 0 sit out behind the weight test (they read no coordinate and no normal); a tile without a surface row
 // is skipped as a whole.  The loss is summed in fp64 from the lanes up and divided by n_surf in fp64.
 #include "shine_gterm_body.hpp"
+#include "shine_term_host.hpp"
 
 namespace shine {
 namespace {
@@ -103,17 +104,6 @@ __global__ __launch_bounds__(kThreads) void k_normal_step(const NormalArgs a) {
   gterm_step<L, POLY, NormalPolicy>(a, s_stage, s_loss, &s_flag);
 }
 
-template <int L, bool POLY>
-void launch_normal_step_p(const NormalArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL((k_normal_step<L, POLY>), dim3(gterm_blocks((a.n + 63) / 64)), dim3(kThreads), 0, st, a);
-}
-
-template <int L>
-void launch_normal_step(const NormalArgs& a, bool poly, hipStream_t st) {
-  if (poly) launch_normal_step_p<L, true>(a, st);
-  else launch_normal_step_p<L, false>(a, st);
-}
-
 }  // namespace
 }  // namespace shine
 
@@ -125,40 +115,19 @@ extern "C" int shine_normal_train_step(const shine_tables* t, const shine_step_c
                                        float weight_n, const float* const* feats, const int64_t* rows,
                                        float* const* grad_feats, const float* const* mlp, float* const* grad_mlp,
                                        float* normal_loss_out, void* workspace, void* stream) {
-  if (!t) return set_error(SHINE_E_INVALID, "shine_normal_train_step: null table handle");
-  if (!cfg) return set_error(SHINE_E_INVALID, "shine_normal_train_step: null config");
-  if (coord_stride != 3 && coord_stride != 8)
-    return set_error(SHINE_E_INVALID, "shine_normal_train_step: coord_stride is 3 ([n,3] array) or 8 (32-byte pool records)");
-  if (weight_stride != 1 && weight_stride != 8)
-    return set_error(SHINE_E_INVALID, "shine_normal_train_step: weight_stride is 1 (an array) or 8 (32-byte pool records)");
-  if (n < 0) return set_error(SHINE_E_INVALID, "shine_normal_train_step: n < 0");
-  if (n_surf_parts < 0) return set_error(SHINE_E_INVALID, "shine_normal_train_step: n_surf_parts < 0");
-  if (!feats || !rows || !mlp || !normal_loss_out || (n > 0 && (!coord || !weight || !normal || !n_surf)))
-    return set_error(SHINE_E_INVALID, "shine_normal_train_step: null argument");
-  if (!workspace || ((size_t)workspace & 255)) return set_error(SHINE_E_INVALID, "shine_normal_train_step: workspace");
+  static const char* const kEntry = "shine_normal_train_step";
   NormalArgs a = {};
-  for (int k = 0; k < 6; ++k) {
-    if (!mlp[k]) return set_error(SHINE_E_INVALID, "shine_normal_train_step: null decoder parameter");
-    a.mlp[k] = mlp[k];
-  }
-  if (grad_mlp) {
-    for (int k = 0; k < 6; ++k)
-      if (!grad_mlp[k]) return set_error(SHINE_E_INVALID, "shine_normal_train_step: null weight-grad tensor");
-    a.gW1 = grad_mlp[0], a.gW2 = grad_mlp[2], a.gw3 = grad_mlp[4];  // (the three biases receive nothing)
-  }
-  if (cfg->n_levels > 4) return set_error(SHINE_E_INVALID, "shine_normal_train_step: more than 4 featured levels");
-  int rc = make_level_set(t, cfg, feats, rows, grad_feats, &a.ls);
+  int rc = term_prologue(kEntry, t, cfg, coord_stride, n, feats, rows, normal_loss_out, workspace);
+  if (rc == SHINE_OK) rc = term_decoder(kEntry, mlp, grad_mlp, &a);
   if (rc != SHINE_OK) return rc;
-  const int L = cfg->n_levels;
-  for (int s = 0; s < L; ++s) {
-    if (!feats[s]) return set_error(SHINE_E_INVALID, "shine_normal_train_step: null feature level");
-    if (rows[s] >= (1ll << 29)) return set_error(SHINE_E_INVALID, "shine_normal_train_step: level exceeds 2^29 rows");
-  }
+  if (weight_stride != 1 && weight_stride != 8)
+    return term_refuse(kEntry, "weight_stride is 1 (an array) or 8 (32-byte pool records)");
+  if (n_surf_parts < 0) return term_refuse(kEntry, "n_surf_parts < 0");
+  if (n > 0 && (!coord || !weight || !normal || !n_surf)) return term_refuse(kEntry, "null argument");
+  rc = term_levels(kEntry, t, cfg, feats, rows, grad_feats, &a.ls);
+  if (rc != SHINE_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (n == 0) {
-    SHINE_HIP_CHECK(hipMemsetAsync(normal_loss_out, 0, sizeof(float), st));
-    return SHINE_OK;
-  }
+  if (n == 0) return term_empty(normal_loss_out, st);
   a.coord = coord;
   a.idx = idx;
   a.weight = weight;
@@ -169,16 +138,12 @@ extern "C" int shine_normal_train_step(const shine_tables* t, const shine_step_c
   a.cstride = coord_stride;
   a.wstride = weight_stride;
   a.weight_n = weight_n;
-  a.want_wgrad = grad_mlp ? 1 : 0;
   a.loss_out = normal_loss_out;
   a.ws = (unsigned char*)workspace;
-  const bool poly = cfg->poly_int_on != 0;
-  switch (L) {
-    case 1: launch_normal_step<1>(a, poly, st); break;
-    case 2: launch_normal_step<2>(a, poly, st); break;
-    case 3: launch_normal_step<3>(a, poly, st); break;
-    default: launch_normal_step<4>(a, poly, st); break;
-  }
+  const dim3 grid(gterm_blocks((n + 63) / 64));
+  dispatch_levels_poly(cfg->n_levels, cfg->poly_int_on != 0, [&](auto l, auto p) {
+    hipLaunchKernelGGL((k_normal_step<decltype(l)::value, decltype(p)::value>), grid, dim3(kThreads), 0, st, a);
+  });
   SHINE_HIP_CHECK(hipGetLastError());
   return SHINE_OK;
 }

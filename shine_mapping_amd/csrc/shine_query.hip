@@ -9,6 +9,7 @@
 // it is produced.
 // Bytes per query: 12 in, 5 out.
 #include "shine_internal.hpp"
+#include "shine_term_host.hpp"
 
 namespace shine {
 
@@ -78,16 +79,6 @@ __global__ __launch_bounds__(256) void k_query_points(QueryArgs a) {
   }
 }
 
-template <int L>
-static void launch_query(const QueryArgs& a, bool poly, hipStream_t st) {
-  long long blocks = (a.n + 255) / 256;
-  if (blocks > 256 * 16) blocks = 256 * 16;  // grid-stride beyond 16 workgroups per CU
-  if (poly)
-    hipLaunchKernelGGL((k_query_points<L, true>), dim3((unsigned)blocks), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((k_query_points<L, false>), dim3((unsigned)blocks), dim3(256), 0, st, a);
-}
-
 }  // namespace shine
 
 using namespace shine;
@@ -119,15 +110,13 @@ extern "C" int shine_query_points(const shine_tables* t, const shine_step_config
   a.n = n;
   a.check_slot = L - 1 - check_level;  // hierarchical_indices is bottom-up (mesher.py:78), slots are top-down
   a.sign = negate ? -1.f : 1.f;
-  const bool poly = cfg->poly_int_on != 0;
   hipStream_t st = (hipStream_t)stream;
-  switch (L) {
-    case 1: launch_query<1>(a, poly, st); break;
-    case 2: launch_query<2>(a, poly, st); break;
-    case 3: launch_query<3>(a, poly, st); break;
-    case 4: launch_query<4>(a, poly, st); break;
-    default: return set_error(SHINE_E_INVALID, "shine_query_points: more than 4 featured levels");
-  }
+  long long blocks = (n + 255) / 256;
+  if (blocks > 256 * 16) blocks = 256 * 16;  // grid-stride beyond 16 workgroups per CU
+  if (!dispatch_levels_poly(L, cfg->poly_int_on != 0, [&](auto l, auto p) {
+        hipLaunchKernelGGL((k_query_points<decltype(l)::value, decltype(p)::value>), dim3((unsigned)blocks), dim3(256), 0, st, a);
+      }))
+    return set_error(SHINE_E_INVALID, "shine_query_points: more than 4 featured levels");
   SHINE_HIP_CHECK(hipGetLastError());
   return SHINE_OK;
 }

@@ -17,6 +17,7 @@
 // writes the loss.  What bounds the launch at the reference's batch (4096 rows = 64 tiles) is the latency of ONE tile through
 // the head and back — the rolled weight-row loops are chains of scalar loads and FMAs — not throughput: 64 waves on 16 CUs.
 #include "shine_sem_head.hpp"
+#include "shine_term_host.hpp"
 
 namespace shine {
 using namespace sem;
@@ -275,17 +276,10 @@ SEM_ROW_LOOP(8)
 // depends on m alone, so equal batches sum in equal order.  (One wave per workgroup — a tile per CU up to 16 K rows — was
 // measured at N = 4096: 8 us less with the head frozen, 13 us MORE with it training, where 64 partial vectors instead of 16
 // meet in the ticket sums; not kept.  DESIGN.md 3.15.)
-template <int L, bool POLY>
-void launch_sem_step_p(const SemStepArgs& a, hipStream_t st) {
-  const long long tiles = (a.m + 63) / 64;
+unsigned sem_step_blocks(long long m) {
+  const long long tiles = (m + 63) / 64;
   const long long b = (tiles + kWaves - 1) / kWaves;
-  hipLaunchKernelGGL((k_sem_step<L, POLY>), dim3((unsigned)(b > kMaxBlocks ? kMaxBlocks : b)), dim3(kThreads), 0, st, a);
-}
-
-template <int L>
-void launch_sem_step(const SemStepArgs& a, bool poly, hipStream_t st) {
-  if (poly) launch_sem_step_p<L, true>(a, st);
-  else launch_sem_step_p<L, false>(a, st);
+  return (unsigned)(b > kMaxBlocks ? kMaxBlocks : b);
 }
 
 }  // namespace
@@ -298,34 +292,20 @@ extern "C" int shine_sem_train_step(const shine_tables* t, const shine_step_conf
                                     const float* const* feats, const int64_t* rows, float* const* grad_feats,
                                     const float* const* mlp, int32_t n_class, float* const* grad_mlp, float* sem_loss_out,
                                     void* workspace, void* stream) {
-  if (!t) return set_error(SHINE_E_INVALID, "shine_sem_train_step: null table handle");
-  if (coord_stride != 3 && coord_stride != 8)
-    return set_error(SHINE_E_INVALID, "shine_sem_train_step: coord_stride is 3 ([n,3] array) or 8 (32-byte pool records)");
-  if (decimation < 1) return set_error(SHINE_E_INVALID, "shine_sem_train_step: decimation < 1");
+  static const char* const kEntry = "shine_sem_train_step";
   SemStepArgs a = {};
-  int rc = fill_mlp(&a.p, mlp, n_class, "shine_sem_train_step: decoder parameters / n_class (1..32)");
+  int rc = term_prologue(kEntry, t, cfg, coord_stride, n, feats, rows, sem_loss_out, workspace);
   if (rc != SHINE_OK) return rc;
-  if (n < 0 || !feats || !rows || !sem_loss_out || (n > 0 && (!coord || !labels)))
-    return set_error(SHINE_E_INVALID, "shine_sem_train_step: null argument");
-  if (!workspace || ((size_t)workspace & 255)) return set_error(SHINE_E_INVALID, "shine_sem_train_step: workspace");
-  if (grad_mlp)
-    for (int k = 0; k < 6; ++k) {
-      if (!grad_mlp[k]) return set_error(SHINE_E_INVALID, "shine_sem_train_step: null weight-grad tensor");
-      a.gp.g[k] = grad_mlp[k];
-    }
-  rc = make_level_set(t, cfg, feats, rows, grad_feats, &a.ls);
+  if (decimation < 1) return term_refuse(kEntry, "decimation < 1");
+  rc = fill_mlp(&a.p, mlp, n_class, "shine_sem_train_step: decoder parameters / n_class (1..32)");
+  if (rc == SHINE_OK) rc = term_wgrads(kEntry, grad_mlp);
   if (rc != SHINE_OK) return rc;
-  const int L = cfg->n_levels;
-  if (L > 4) return set_error(SHINE_E_INVALID, "shine_sem_train_step: more than 4 featured levels");
-  for (int s = 0; s < L; ++s) {
-    if (!feats[s]) return set_error(SHINE_E_INVALID, "shine_sem_train_step: null feature level");
-    if (rows[s] >= (1ll << 29)) return set_error(SHINE_E_INVALID, "shine_sem_train_step: level exceeds 2^29 rows");
-  }
+  for (int k = 0; grad_mlp && k < 6; ++k) a.gp.g[k] = grad_mlp[k];
+  if (n > 0 && (!coord || !labels)) return term_refuse(kEntry, "null argument");
+  rc = term_levels(kEntry, t, cfg, feats, rows, grad_feats, &a.ls);
+  if (rc != SHINE_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (n == 0) {
-    SHINE_HIP_CHECK(hipMemsetAsync(sem_loss_out, 0, sizeof(float), st));
-    return SHINE_OK;
-  }
+  if (n == 0) return term_empty(sem_loss_out, st);
   const long long m = (n + decimation - 1) / decimation;
   a.coord = coord;
   a.idx = idx;
@@ -340,13 +320,10 @@ extern "C" int shine_sem_train_step(const shine_tables* t, const shine_step_conf
   a.want_wgrad = grad_mlp ? 1 : 0;
   a.loss_out = sem_loss_out;
   a.ws = (unsigned char*)workspace;
-  const bool poly = cfg->poly_int_on != 0;
-  switch (L) {
-    case 1: launch_sem_step<1>(a, poly, st); break;
-    case 2: launch_sem_step<2>(a, poly, st); break;
-    case 3: launch_sem_step<3>(a, poly, st); break;
-    default: launch_sem_step<4>(a, poly, st); break;
-  }
+  const dim3 grid(sem_step_blocks(m));
+  dispatch_levels_poly(cfg->n_levels, cfg->poly_int_on != 0, [&](auto l, auto p) {
+    hipLaunchKernelGGL((k_sem_step<decltype(l)::value, decltype(p)::value>), grid, dim3(kThreads), 0, st, a);
+  });
   SHINE_HIP_CHECK(hipGetLastError());
   return SHINE_OK;
 }

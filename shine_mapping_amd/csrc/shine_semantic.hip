@@ -13,6 +13,7 @@
 // Weight grads are repeat-bit-identical: every wave accumulates its tiles in a fixed order, the four waves of a workgroup are
 // summed in a fixed order, and the workgroups' partials meet in the two ticket levels of shine_sem_head.hpp's sem_grid_sum.
 #include "shine_sem_head.hpp"
+#include "shine_term_host.hpp"
 
 namespace shine {
 using namespace sem;
@@ -231,17 +232,6 @@ __global__ __launch_bounds__(kThreads) void k_sem_query(LevelSet ls, const float
   }
 }
 
-template <int L>
-void launch_sem_query(const LevelSet& ls, bool poly, const float* coord, long long n, const SemArgsPtrs& p, int C,
-                      long long* label, hipStream_t st) {
-  long long blocks = (n + kThreads - 1) / kThreads;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  if (poly)
-    hipLaunchKernelGGL((k_sem_query<L, true>), dim3((unsigned)blocks), dim3(kThreads), 0, st, ls, coord, n, p, C, label);
-  else
-    hipLaunchKernelGGL((k_sem_query<L, false>), dim3((unsigned)blocks), dim3(kThreads), 0, st, ls, coord, n, p, C, label);
-}
-
 unsigned fwd_grid(long long n) {
   const long long b = (n + kThreads - 1) / kThreads;
   return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
@@ -315,16 +305,15 @@ extern "C" int shine_sem_query_labels(const shine_tables* t, const shine_step_co
     if (rows[s] >= (1ll << 29)) return set_error(SHINE_E_INVALID, "shine_sem_query_labels: level exceeds 2^29 rows");
   }
   if (n == 0) return SHINE_OK;
-  const bool poly = cfg->poly_int_on != 0;
   hipStream_t st = (hipStream_t)stream;
   long long* lab = reinterpret_cast<long long*>(label_out);
-  switch (L) {
-    case 1: launch_sem_query<1>(ls, poly, coord, n, p, n_class, lab, st); break;
-    case 2: launch_sem_query<2>(ls, poly, coord, n, p, n_class, lab, st); break;
-    case 3: launch_sem_query<3>(ls, poly, coord, n, p, n_class, lab, st); break;
-    case 4: launch_sem_query<4>(ls, poly, coord, n, p, n_class, lab, st); break;
-    default: return set_error(SHINE_E_INVALID, "shine_sem_query_labels: more than 4 featured levels");
-  }
+  long long blocks = (n + kThreads - 1) / kThreads;
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  if (!dispatch_levels_poly(L, cfg->poly_int_on != 0, [&](auto l, auto pl) {
+        hipLaunchKernelGGL((k_sem_query<decltype(l)::value, decltype(pl)::value>), dim3((unsigned)blocks), dim3(kThreads), 0, st,
+                           ls, coord, (long long)n, p, (int)n_class, lab);
+      }))
+    return set_error(SHINE_E_INVALID, "shine_sem_query_labels: more than 4 featured levels");
   SHINE_HIP_CHECK(hipGetLastError());
   return SHINE_OK;
 }

@@ -273,6 +273,14 @@ class GraphedIteration(metaclass=_IterationTerms):
         self._out_1 = self._out_k = None
         self._native = {}  # unroll -> (IterationGraph, outputs, keep-alive) bound to this object's buffers
 
+    def _term_buffers(self, nbytes):
+        """(workspace, out, loss) of one term step: a zeroed workspace of its own (the captured graph holds the address), the
+        one-element tensor the step writes, and the 0-dim view of it that the loop hands out"""
+        dev = self.pool.coord.device
+        ws = _lib.zeroed_workspace(nbytes, dev)
+        out = torch.zeros(1, dtype=torch.float32, device=dev)
+        return ws, out, out[0]
+
     def _init_sem(self, can_fold):
         """the semantic term's buffers, all made here: a captured graph bakes their addresses in"""
         sem = self.sem
@@ -283,15 +291,12 @@ class GraphedIteration(metaclass=_IterationTerms):
         if int(sem.decimation) < 1:
             raise ValueError("sem_label_decimation must be >= 1")
         self.native = False  # (the library-built graph holds the two-launch iteration)
-        dev = self.pool.coord.device
         self._sem_params = list(sem.decoder.sem_params())
         train = [p.requires_grad for p in self._sem_params]
         if any(train) != all(train):
             raise ValueError("the semantic head's six tensors must all train or all be frozen")
         self._sem_train = all(train)
-        self._sem_ws = _lib.zeroed_workspace(SEM_WORKSPACE_BYTES, dev)  # (its own: the captured graph holds the address)
-        self._sem_out = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.sem_loss = self._sem_out[0]
+        self._sem_ws, self._sem_out, self.sem_loss = self._term_buffers(SEM_WORKSPACE_BYTES)
 
     def _init_normal(self, can_fold):
         """the normal term's buffers, all made here: a captured graph bakes their addresses in"""
@@ -300,10 +305,7 @@ class GraphedIteration(metaclass=_IterationTerms):
         if getattr(self.pool, "normal_label", None) is None:
             raise ValueError("GraphedIteration(normal=...) needs a SortedPool built with normal_label=")
         self.native = False  # (the library-built graph holds the two-launch iteration)
-        dev = self.pool.coord.device
-        self._normal_ws = _lib.zeroed_workspace(NORMAL_WORKSPACE_BYTES, dev)  # (its own: the captured graph holds the address)
-        self._normal_out = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.normal_loss = self._normal_out[0]
+        self._normal_ws, self._normal_out, self.normal_loss = self._term_buffers(NORMAL_WORKSPACE_BYTES)
 
     def _check_consistency(self, can_fold):
         term = self.consistency
@@ -321,11 +323,9 @@ class GraphedIteration(metaclass=_IterationTerms):
         self.native = False  # (the library-built graph holds the two-launch iteration)
         dev = self.pool.coord.device
         k = self._consistency_k = min(int(term.count), self.n)
-        self._consistency_ws = _lib.zeroed_workspace(CONSISTENCY_WORKSPACE_BYTES, dev)  # (its own: the graph holds the address)
-        self._consistency_out = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._consistency_ws, self._consistency_out, self.consistency_loss = self._term_buffers(CONSISTENCY_WORKSPACE_BYTES)
         self._consistency_state = torch.zeros(1, dtype=torch.int64, device=dev)  # the pairs' stream id, advanced by the kernel
         self.consistency_draws = (torch.zeros(k, dtype=torch.int32, device=dev), torch.zeros((k, 3), dtype=torch.float32, device=dev))
-        self.consistency_loss = self._consistency_out[0]
 
     def _graph_1(self):
         if self.graph is None:

@@ -155,10 +155,7 @@ def _fused_launch(octree, decoder, coord, sdf_label, weight, opts: StepOptions, 
     t = octree._require_tables(probe=(int(opts.kernel_variant) & 0xff) == 1)
     pool_mode = pool is not None
     if pool_mode:  # batch = pool[idx] with idx sorted (sampler.SortedPool.draw): read straight out of the pool
-        if idx is None or not (idx.is_cuda and idx.dtype == torch.int32):
-            raise ValueError("pool mode needs idx = SortedPool.draw(n) (CUDA int32)")
-        if pool.tables_epoch != octree._tables_epoch:
-            raise RuntimeError("the octree grew since the pool was planned: call SortedPool.rebuild()")
+        _check_pool_idx(octree, pool, idx)
         if eik_needs_count(opts) and n_surf is None:
             n_surf = (pool.weight[idx.long()] > 0).sum()
     variant = int(opts.kernel_variant) & 0xff
@@ -280,6 +277,78 @@ def _fused_launch(octree, decoder, coord, sdf_label, weight, opts: StepOptions, 
     return loss_parts[3], pred, gx  # 0-dim float64 view: BCE (+ weight_e * eikonal), no extra launch
 
 
+# ---- the term steps (fused_sem_step, fused_normal_step, fused_consistency_step) share their host side: where
+# the batch is read from, where the gradients go, the loss's tensor, and the call.  A step keeps its term's own checks and its
+# argument list.
+def _i32c(x):
+    return isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.int32 and x.is_contiguous()
+
+
+def _check_pool_idx(octree, pool, idx):
+    """pool mode: the batch is pool[idx], and the pool was planned on the octree's tables as they are now"""
+    if not _i32c(idx):
+        raise ValueError("pool mode needs idx = SortedPool.draw(n) (CUDA int32)")
+    if pool.tables_epoch != octree._tables_epoch:
+        raise RuntimeError("the octree grew since the pool was planned: call SortedPool.rebuild()")
+
+
+def _term_batch(octree, coord, pool, idx, pool_needs=None):
+    """(src, floats per row, n, device) of a term step's batch.  Array mode: coord [N,3], read through idx when given.  Pool
+    mode: pool[idx] straight out of the pool's 32-byte records, or of its SoA coordinates; `pool_needs` names the pool attribute
+    the term reads beside them."""
+    if pool is not None:
+        _check_pool_idx(octree, pool, idx)
+        if pool_needs is not None and getattr(pool, pool_needs, None) is None:
+            raise ValueError("pool mode needs a SortedPool built with %s=" % pool_needs)
+        rec = getattr(pool, "rec", None)
+        src, stride = (rec, 8) if rec is not None else (pool.soa()[0], 3)
+    else:
+        if not isinstance(coord, torch.Tensor):
+            raise ValueError("array mode needs coord [N,3] (or pool= and idx=)")
+        src, stride = octree._check_coord(coord.detach()), 3
+        if idx is not None and not _i32c(idx):
+            raise ValueError("idx must be a contiguous CUDA int32 tensor")
+    n = int(idx.numel()) if idx is not None else int(src.shape[0])
+    return src, stride, n, src.device
+
+
+def _term_targets(octree, mlp, grad_buffers, who):
+    """(L feature-grad tensors | None entries, 6 weight-grad tensors | None): `grad_buffers`, or the parameters' dense `.grad`"""
+    gfeat, gmlp = grad_buffers if grad_buffers is not None else (None, None)
+    if gfeat is None:
+        gfeat = [_dense_grad(p) if p.requires_grad else None for p in octree.feature_list()]
+    if grad_buffers is None:
+        train = [p.requires_grad for p in mlp]
+        if any(train) != all(train):
+            raise ValueError("%s six tensors must all require grad or all be frozen" % who)
+        gmlp = [_dense_grad(p) for p in mlp] if all(train) else None
+    return gfeat, gmlp
+
+
+def _term_out(out, dev):
+    if out is None:
+        return torch.empty(1, dtype=torch.float32, device=dev)
+    if not (out.is_cuda and out.dtype == torch.float32 and out.numel() == 1):
+        raise ValueError("out must be a CUDA float32 tensor of one element")
+    return out
+
+
+def _term_ptrs(octree, mlp, gfeat, gmlp):
+    """(feats, rows, grad_feats, mlp, grad_mlp | None) as the entry points take them"""
+    return (octree.feature_ptrs(), octree.row_counts(), _lib.ptr_array([g.data_ptr() if g is not None else None for g in gfeat]),
+            _lib.ptr_array([p.data_ptr() for p in mlp]),
+            _lib.ptr_array([g.data_ptr() for g in gmlp]) if gmlp is not None else None)
+
+
+def _term_call(name, octree, *args):
+    """the entry point `name` on the current stream (looked up at call time); the launch probed the hash tables"""
+    rc = getattr(_lib.lib(), name)(*args, _lib.current_stream_handle())
+    if rc != 0:
+        _lib.check(rc, name)
+    if not torch.cuda.is_current_stream_capturing():
+        octree._tables_read_done()
+
+
 def fused_sem_step(octree, sem_decoder, coord, sem_label, weight_s, decimation=1, pool=None, idx=None, grad_buffers=None,
                    out=None, workspace=None):
     """The semantic term of one training iteration (shine_batch.py:132-133,200-204) in ONE launch (shine_sem_train_step):
@@ -302,62 +371,24 @@ def fused_sem_step(octree, sem_decoder, coord, sem_label, weight_s, decimation=1
     decimation = int(decimation)
     if decimation < 1:
         raise ValueError("decimation must be >= 1")
-    if pool is not None:
-        if idx is None or not (idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous()):
-            raise ValueError("pool mode needs idx = SortedPool.draw(n) (CUDA int32)")
-        if pool.tables_epoch != octree._tables_epoch:
-            raise RuntimeError("the octree grew since the pool was planned: call SortedPool.rebuild()")
-        labels = getattr(pool, "sem_label", None)
-        if labels is None:
-            raise ValueError("pool mode needs a SortedPool built with sem_label=")
-        if getattr(pool, "rec", None) is not None:
-            src, stride = pool.rec, 8
-        else:
-            src, stride = pool.soa()[0], 3
-        n = int(idx.numel())
-    else:
-        src, stride = octree._check_coord(coord.detach()), 3
-        labels = sem_label
-        n = int(src.shape[0])
-        if idx is not None:
-            if not (idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous()):
-                raise ValueError("idx must be a contiguous CUDA int32 tensor")
-            n = int(idx.numel())
-        elif labels.numel() != n:
-            raise ValueError("sem_label must hold one label per coordinate")
-    if not (labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous()):
+    src, stride, n, dev = _term_batch(octree, coord, pool, idx, pool_needs="sem_label")
+    labels = pool.sem_label if pool is not None else sem_label
+    if pool is None and idx is None and labels.numel() != n:
+        raise ValueError("sem_label must hold one label per coordinate")
+    if not _i32c(labels):
         raise ValueError("sem_label must be a contiguous CUDA int32 tensor")
-    dev = src.device
     if not sem_decoder._params_on(dev, mlp):
         raise ValueError("the semantic decoder's parameters must be CUDA float32 contiguous on the batch's device")
-    gfeat, gmlp = grad_buffers if grad_buffers is not None else (None, None)
-    if gfeat is None:
-        gfeat = [_dense_grad(p) if p.requires_grad else None for p in octree.feature_list()]
-    if grad_buffers is None:
-        train = [p.requires_grad for p in mlp]
-        if any(train) != all(train):
-            raise ValueError("the semantic head's six tensors must all require grad or all be frozen")
-        gmlp = [_dense_grad(p) for p in mlp] if all(train) else None
-    if out is None:
-        out = torch.empty(1, dtype=torch.float32, device=dev)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.numel() == 1):
-        raise ValueError("out must be a CUDA float32 tensor of one element")
+    gfeat, gmlp = _term_targets(octree, mlp, grad_buffers, "the semantic head's")
+    out = _term_out(out, dev)
     ws = workspace if workspace is not None else autograd_ops.sem_workspace(dev)
     cfg = octree.step_config()
-    _lib.check(
-        _lib.lib().shine_sem_train_step(
-            t.handle, C.byref(cfg), src.data_ptr(), stride, idx.data_ptr() if idx is not None else None, labels.data_ptr(), n,
-            decimation, float(weight_s), octree.feature_ptrs(), octree.row_counts(),
-            _lib.ptr_array([g.data_ptr() if g is not None else None for g in gfeat]),
-            _lib.ptr_array([p.data_ptr() for p in mlp]), n_class,
-            _lib.ptr_array([g.data_ptr() for g in gmlp]) if gmlp is not None else None,
-            out.data_ptr(), ws.data_ptr(), _stream(),
-        ),
-        "shine_sem_train_step",
-    )
-    if not torch.cuda.is_current_stream_capturing():
-        octree._tables_read_done()
+    feats, rows, grad_feats, mlp_ptrs, grad_mlp = _term_ptrs(octree, mlp, gfeat, gmlp)
+    _term_call("shine_sem_train_step", octree, t.handle, C.byref(cfg), src.data_ptr(), stride,
+               idx.data_ptr() if idx is not None else None, labels.data_ptr(), n, decimation, float(weight_s), feats, rows,
+               grad_feats, mlp_ptrs, n_class, grad_mlp, out.data_ptr(), ws.data_ptr())
     return out.view(())
+
 
 
 def fused_normal_step(octree, decoder, coord, weight, normal_label, weight_n, n_surf=None, pool=None, idx=None,
@@ -387,45 +418,26 @@ def fused_normal_step(octree, decoder, coord, weight, normal_label, weight_n, n_
     mlp = decoder.fused_params()
     if n_surf is not None and not isinstance(n_surf, torch.Tensor):
         raise ValueError("n_surf must be a contiguous CUDA int64 tensor (one count, or the draw's partial counts)")
-
-    def _idx_ok(i):
-        return i.is_cuda and i.dtype == torch.int32 and i.is_contiguous()
-
+    if pool is None and not all(isinstance(x, torch.Tensor) for x in (coord, weight, normal_label)):
+        raise ValueError("array mode needs coord [N,3], weight [N] and normal_label [N,3] (or pool= and idx=)")
+    src, stride, n, dev = _term_batch(octree, coord, pool, idx, pool_needs="normal_label")
     if pool is not None:
-        if idx is None or not _idx_ok(idx):
-            raise ValueError("pool mode needs idx = SortedPool.draw(n) (CUDA int32)")
-        if pool.tables_epoch != octree._tables_epoch:
-            raise RuntimeError("the octree grew since the pool was planned: call SortedPool.rebuild()")
-        normal = getattr(pool, "normal_label", None)
-        if normal is None:
-            raise ValueError("pool mode needs a SortedPool built with normal_label=")
-        if getattr(pool, "rec", None) is not None:
-            src, stride = pool.rec, 8
-            if pool._weight_sep is None:  # word 4 of the 32-byte records
-                w_ptr, w_stride, w_keep = pool.rec.data_ptr() + 16, 8, pool.rec
-            else:
-                w_ptr, w_stride, w_keep = pool._weight_sep.data_ptr(), 1, pool._weight_sep
+        normal = pool.normal_label
+        if stride == 3:
+            w_keep, w_stride = pool.soa()[2], 1
+            w_ptr = w_keep.data_ptr()
+        elif pool._weight_sep is None:  # word 4 of the 32-byte records
+            w_ptr, w_stride, w_keep = pool.rec.data_ptr() + 16, 8, pool.rec
         else:
-            soa = pool.soa()
-            src, stride = soa[0], 3
-            w_ptr, w_stride, w_keep = soa[2].data_ptr(), 1, soa[2]
-        n = int(idx.numel())
+            w_ptr, w_stride, w_keep = pool._weight_sep.data_ptr(), 1, pool._weight_sep
         if n_surf is None:
             n_surf = (pool.weight[idx.long()] > 0).sum()
     else:
-        if not all(isinstance(x, torch.Tensor) for x in (coord, weight, normal_label)):
-            raise ValueError("array mode needs coord [N,3], weight [N] and normal_label [N,3] (or pool= and idx=)")
-        src, stride = octree._check_coord(coord.detach()), 3
         normal = normal_label
         w_keep = _f32(weight, "weight")
         w_ptr, w_stride = w_keep.data_ptr(), 1
-        n = int(src.shape[0])
-        if w_keep.dim() != 1 or w_keep.numel() != n:
+        if w_keep.dim() != 1 or w_keep.numel() != src.shape[0]:
             raise ValueError("weight must hold one value per coordinate")
-        if idx is not None:
-            if not _idx_ok(idx):
-                raise ValueError("idx must be a contiguous CUDA int32 tensor")
-            n = int(idx.numel())
         if n_surf is None:
             n_surf = ((w_keep[idx.long()] if idx is not None else w_keep) > 0).sum()
     if not (isinstance(normal, torch.Tensor) and normal.is_cuda and normal.dtype == torch.float32 and normal.is_contiguous()
@@ -433,41 +445,20 @@ def fused_normal_step(octree, decoder, coord, weight, normal_label, weight_n, n_
         raise ValueError("normal_label must be a contiguous CUDA float32 [N,3] tensor")
     if pool is None and normal.shape[0] != src.shape[0]:
         raise ValueError("normal_label must hold one normal per coordinate")
-    dev = src.device
     if not (n_surf.is_cuda and n_surf.dtype == torch.int64 and n_surf.is_contiguous() and n_surf.numel() >= 1):
         raise ValueError("n_surf must be a contiguous CUDA int64 tensor (one count, or the draw's partial counts)")
     if not decoder._params_on(dev, mlp):
         raise ValueError("the decoder's parameters must be CUDA float32 contiguous on the batch's device")
-    gfeat, gmlp = grad_buffers if grad_buffers is not None else (None, None)
-    if gfeat is None:
-        gfeat = [_dense_grad(p) if p.requires_grad else None for p in octree.feature_list()]
-    if grad_buffers is None:
-        train = [p.requires_grad for p in mlp]
-        if any(train) != all(train):
-            raise ValueError("the decoder's six tensors must all require grad or all be frozen")
-        gmlp = [_dense_grad(p) for p in mlp] if all(train) else None
-    if out is None:
-        out = torch.empty(1, dtype=torch.float32, device=dev)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.numel() == 1):
-        raise ValueError("out must be a CUDA float32 tensor of one element")
+    gfeat, gmlp = _term_targets(octree, mlp, grad_buffers, "the decoder's")
+    out = _term_out(out, dev)
     ws = workspace if workspace is not None else autograd_ops.normal_workspace(dev)
     cfg = octree.step_config()
-    _lib.check(
-        _lib.lib().shine_normal_train_step(
-            t.handle, C.byref(cfg), src.data_ptr(), stride, idx.data_ptr() if idx is not None else None, w_ptr, w_stride,
-            normal.data_ptr(), n_surf.data_ptr(), int(n_surf.numel()), n, float(weight_n),
-            octree.feature_ptrs(), octree.row_counts(),
-            _lib.ptr_array([g.data_ptr() if g is not None else None for g in gfeat]),
-            _lib.ptr_array([p.data_ptr() for p in mlp]),
-            _lib.ptr_array([g.data_ptr() for g in gmlp]) if gmlp is not None else None,
-            out.data_ptr(), ws.data_ptr(), _stream(),
-        ),
-        "shine_normal_train_step",
-    )
-    del w_keep
-    if not torch.cuda.is_current_stream_capturing():
-        octree._tables_read_done()
+    _term_call("shine_normal_train_step", octree, t.handle, C.byref(cfg), src.data_ptr(), stride,
+               idx.data_ptr() if idx is not None else None, w_ptr, w_stride, normal.data_ptr(), n_surf.data_ptr(),
+               int(n_surf.numel()), n, float(weight_n), *_term_ptrs(octree, mlp, gfeat, gmlp), out.data_ptr(), ws.data_ptr())
+    del w_keep  # (the weights outlive the call)
     return out.view(())
+
 
 
 def fused_consistency_step(octree, decoder, coord, weight_c, near_index=None, shift=None, n_pairs=None, shift_scale=None, seed=0,
@@ -501,37 +492,16 @@ def fused_consistency_step(octree, decoder, coord, weight_c, near_index=None, sh
     t = octree._require_tables()  # (the kernel probes the hash tables from the coordinates)
     mlp = decoder.fused_params()
 
-    def _i32(x):
-        return isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.int32 and x.is_contiguous()
-
     def _f32k3(x):
         return (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 2
                 and x.shape[1] == 3)
 
-    if pool is not None:
-        if idx is None or not _i32(idx):
-            raise ValueError("pool mode needs idx = SortedPool.draw(n) (CUDA int32)")
-        if pool.tables_epoch != octree._tables_epoch:
-            raise RuntimeError("the octree grew since the pool was planned: call SortedPool.rebuild()")
-        if getattr(pool, "rec", None) is not None:
-            src, stride = pool.rec, 8
-        else:
-            src, stride = pool.soa()[0], 3
-        n = int(idx.numel())
-    else:
-        if not isinstance(coord, torch.Tensor):
-            raise ValueError("array mode needs coord [N,3] (or pool= and idx=)")
-        src, stride = octree._check_coord(coord.detach()), 3
-        n = int(src.shape[0])
-        if idx is not None:
-            if not _i32(idx):
-                raise ValueError("idx must be a contiguous CUDA int32 tensor")
-            n = int(idx.numel())
+    src, stride, n, dev = _term_batch(octree, coord, pool, idx)
     if (near_index is None) != (shift is None):
         raise ValueError("near_index and shift come together (both: explicit pairs; neither: drawn pairs)")
     explicit = near_index is not None
     if explicit:
-        if not (_i32(near_index) and near_index.dim() == 1):
+        if not (_i32c(near_index) and near_index.dim() == 1):
             raise ValueError("near_index must be a contiguous CUDA int32 [K] tensor")
         k = int(near_index.numel())
         if not (_f32k3(shift) and shift.shape[0] == k):
@@ -549,53 +519,34 @@ def fused_consistency_step(octree, decoder, coord, weight_c, near_index=None, sh
             raise ValueError("drawn pairs need draw_state: a CUDA int64 tensor of one element")
     if k > 0 and n == 0:
         raise ValueError("pairs need a batch: n_pairs > 0 with no batch row")
-    dev = src.device
     ni_out = sh_out = None
     if draws_out is not None:
         ni_out, sh_out = draws_out
-        if not (_i32(ni_out) and ni_out.numel() >= k and _f32k3(sh_out) and sh_out.shape[0] >= k):
+        if not (_i32c(ni_out) and ni_out.numel() >= k and _f32k3(sh_out) and sh_out.shape[0] >= k):
             raise ValueError("draws_out = (CUDA int32 [K], CUDA float32 [K,3])")
     if touched is not None and not (len(touched) == octree.featured_level_num
                                     and all(x.is_cuda and x.dtype == torch.uint8 for x in touched)):
         raise ValueError("touched = ops.touched_flags(octree): one CUDA uint8 tensor per featured level")
     if not decoder._params_on(dev, mlp):
         raise ValueError("the decoder's parameters must be CUDA float32 contiguous on the batch's device")
-    gfeat, gmlp = grad_buffers if grad_buffers is not None else (None, None)
-    if gfeat is None:
-        gfeat = [_dense_grad(p) if p.requires_grad else None for p in octree.feature_list()]
-    if grad_buffers is None:
-        train = [p.requires_grad for p in mlp]
-        if any(train) != all(train):
-            raise ValueError("the decoder's six tensors must all require grad or all be frozen")
-        gmlp = [_dense_grad(p) for p in mlp] if all(train) else None
-    if out is None:
-        out = torch.empty(1, dtype=torch.float32, device=dev)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.numel() == 1):
-        raise ValueError("out must be a CUDA float32 tensor of one element")
+    gfeat, gmlp = _term_targets(octree, mlp, grad_buffers, "the decoder's")
+    out = _term_out(out, dev)
     if k == 0:  # (what the entry point does for n_pairs == 0; empty explicit tensors have no address to hand it)
         out.zero_()
         return out.view(())
     ws = workspace if workspace is not None else autograd_ops.consistency_workspace(dev)
     cfg = octree.step_config()
-    _lib.check(
-        _lib.lib().shine_consistency_train_step(
-            t.handle, C.byref(cfg), src.data_ptr(), stride, idx.data_ptr() if idx is not None else None, n,
-            near_index.data_ptr() if explicit else None, shift.data_ptr() if explicit else None, k,
-            float(shift_scale) if shift_scale is not None else 0.0, int(seed) & 0xFFFFFFFFFFFFFFFF,
-            draw_state.data_ptr() if (draw_state is not None and not explicit) else None,
-            ni_out.data_ptr() if ni_out is not None else None, sh_out.data_ptr() if sh_out is not None else None,
-            float(weight_c), octree.feature_ptrs(), octree.row_counts(),
-            _lib.ptr_array([g.data_ptr() if g is not None else None for g in gfeat]),
-            _lib.ptr_array([p.data_ptr() for p in mlp]),
-            _lib.ptr_array([g.data_ptr() for g in gmlp]) if gmlp is not None else None,
-            _lib.ptr_array([x.data_ptr() for x in touched]) if touched is not None else None,
-            out.data_ptr(), ws.data_ptr(), _stream(),
-        ),
-        "shine_consistency_train_step",
-    )
-    if not torch.cuda.is_current_stream_capturing():
-        octree._tables_read_done()
+    _term_call("shine_consistency_train_step", octree, t.handle, C.byref(cfg), src.data_ptr(), stride,
+               idx.data_ptr() if idx is not None else None, n,
+               near_index.data_ptr() if explicit else None, shift.data_ptr() if explicit else None, k,
+               float(shift_scale) if shift_scale is not None else 0.0, int(seed) & 0xFFFFFFFFFFFFFFFF,
+               draw_state.data_ptr() if (draw_state is not None and not explicit) else None,
+               ni_out.data_ptr() if ni_out is not None else None, sh_out.data_ptr() if sh_out is not None else None,
+               float(weight_c), *_term_ptrs(octree, mlp, gfeat, gmlp),
+               _lib.ptr_array([x.data_ptr() for x in touched]) if touched is not None else None,
+               out.data_ptr(), ws.data_ptr())
     return out.view(())
+
 
 
 def octree_interp(octree, coord):

@@ -34,7 +34,7 @@ def test_argument_errors_come_back_without_touching_the_gpu():
     try:
         for kw, word in ((dict(stride=4), b"coord_stride"), (dict(stride=0), b"coord_stride"), (dict(d=0), b"decimation"),
                          (dict(d=-3), b"decimation"), (dict(n_class=0), b"n_class"), (dict(n_class=33), b"n_class"),
-                         (dict(mlp=False), b"n_class"), (dict(loss=False), b"null argument"), (dict(n=-1), b"null argument"),
+                         (dict(mlp=False), b"n_class"), (dict(loss=False), b"null argument"), (dict(n=-1), b"n < 0"),
                          (dict(ws=0), b"workspace"), (dict(ws=8), b"workspace")):
             rc = _call(lib, table, cfg, **kw)
             assert rc == -1 and word in lib.shine_error_string(rc), (kw, lib.shine_error_string(rc))
