@@ -393,6 +393,40 @@ int shine_consistency_train_step(const shine_tables* t, const shine_step_config*
                                  float* const* grad_feats, const float* const* mlp, float* const* grad_mlp,
                                  unsigned char* const* touched, float* consistency_loss_out, void* workspace, void* stream);
 
+/* ---- Tier B with time_conditioned: one training iteration's forward + backward of a 4D map (shine_batch.py:119-130,141-142,
+ *      172-185,208-209 with Decoder.time_conditionded_sdf, model/decoder.py:65-81) in ONE launch — the step the graphed loop
+ *      runs instead of shine_train_step when the decoder is the 9 -> 32 -> 32 -> 1 head.  For the n batch rows:
+ *        f = query_feature(x);  pred = w3 . relu(W2 relu(W1f f + (b1 + w_t ts)) + b2) + b3   with mlp[0] = nn.Linear(9, 32).weight
+ *        read in place, [32][9] = [W1f | w_t] (the bias identity of the shine_time_mlp_* trio above);
+ *        bce = BCEWithLogits(pred, sigmoid(label / cfg->sigma)), 'mean' (times cfg->inv_n) or 'sum' (cfg->reduction_sum);
+ *        with cfg->eikonal_on: g = cfg->sigma d pred / d x, eik = mean over weight > 0 of (1 - |g|)^2 — 0 without such a row; a
+ *        row with |g| == 0 contributes 1 and gets no gradient through g (shine_train_step's guard);
+ *        *loss_out = bce + cfg->weight_e * eik (float; both sums in fp64 from the lanes up).
+ *      Gradients: grad_feats[s] [rows_s+1,8] is ACCUMULATED INTO with fp32 atomics, trash row included (NULL array / NULL entries:
+ *      no gradient for that level).  grad_mlp: NULL (a frozen decoder) or 6 tensors shaped like mlp, grad_mlp[0] [32][9]; the sums
+ *      are ADDED to all six by the workgroup that finishes them (the eikonal term's second-order part reaches W1[:, :8], W2 and w3
+ *      only).  ts gets no gradient.  Those sums and the loss are bit-identical from call to call.  Like shine_train_step the
+ *      launch re-zeroes the trash row of every feature table (FeatureOctree.set_zero, model/feature_octree.py:78-81).
+ *      coord / coord_stride / idx as for shine_normal_train_step (3: a plain [.,3] array; 8: 32-byte pool records).  label: float32
+ *      [.] for coord_stride 3; with coord_stride 8 it is not read — the label is dword 3 of the record.  weight / weight_stride as
+ *      for shine_normal_train_step, read with cfg->eikonal_on only.  ts: float32 [.], the time input of every row.  Batch
+ *      position i reads row idx[i] (without idx: row i) of coord, label, weight and ts.  n_surf / n_surf_parts as for
+ *      shine_normal_train_step (cfg->eikonal_on only; at most 64 parts).  pred_out: NULL or float32 [n], written at the batch
+ *      position.  Of cfg: n_levels, max_level, poly_int_on, reduction_sum, eikonal_on, sigma, weight_e, inv_n are read;
+ *      loss_weight_on is refused.
+ *      workspace: see the convention (the query answers one size for every batch) — and a ticket workspace: 256-byte aligned, zero
+ *      before the first call, left ALL zero by every call, never cleared by a call, so the launch can be captured into a HIP graph.
+ *      n == 0 launches nothing and writes a loss of 0.
+ *      SHINE_E_INVALID, worded "shine_time_step: <defect>", before anything touches the device: a null table handle / cfg / feats /
+ *      rows / loss_out / workspace_bytes / decoder tensor, a misaligned or short workspace, n < 0 or >= 2^31, coord_stride other
+ *      than 3 or 8, loss_weight_on, a null coord / ts / label (stride 3) / weight / n_surf (eikonal) with n > 0, more than 4
+ *      featured levels. */
+int shine_time_step(const shine_tables* t, const shine_step_config* cfg, const float* coord, int32_t coord_stride,
+                    const int32_t* idx, const float* label, const float* weight, int32_t weight_stride, const float* ts,
+                    const int64_t* n_surf, int32_t n_surf_parts, int64_t n, const float* const* feats, const int64_t* rows,
+                    float* const* grad_feats, const float* const* mlp, float* const* grad_mlp, float* pred_out, float* loss_out,
+                    void* workspace, size_t* workspace_bytes, void* stream);
+
 /* ---- Tier A (strict drop-in): the backward of FeatureOctree.query_feature as autograd derives it from
  *      model/feature_octree.py:222-234, and its own backward (needed by get_gradient(create_graph=True),
  *      utils/tools.py:175-185, when the eikonal term is differentiated, shine_batch.py:182-185).

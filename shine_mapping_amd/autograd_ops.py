@@ -699,6 +699,25 @@ def normal_workspace(device):
     return _lib.ticket_workspace(device, NORMAL_WORKSPACE_BYTES)
 
 
+_TIME_STEP_WORKSPACE_BYTES = None
+
+
+def time_step_workspace_bytes():
+    """what shine_time_step's size query answers (one size for every batch; asked once)"""
+    global _TIME_STEP_WORKSPACE_BYTES
+    if _TIME_STEP_WORKSPACE_BYTES is None:
+        need = C.c_size_t(0)
+        _lib.check(_lib.lib().shine_time_step(None, None, None, 3, None, None, None, 1, None, None, 0, 0, None, None, None, None,
+                                              None, None, None, None, C.byref(need), None), "shine_time_step")
+        _TIME_STEP_WORKSPACE_BYTES = int(need.value)
+    return _TIME_STEP_WORKSPACE_BYTES
+
+
+def time_step_workspace(device):
+    """the workspace of shine_time_step for the current stream of `device`"""
+    return _lib.ticket_workspace(device, time_step_workspace_bytes())
+
+
 CONSISTENCY_WORKSPACE_BYTES = 1429888  # SHINE_CONSISTENCY_WORKSPACE_BYTES
 
 

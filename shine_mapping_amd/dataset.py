@@ -844,6 +844,8 @@ class LiDARDataset:
             extra = dict(sem_label=self.sem_label_pool, n_class=int(self.config.sem_class_count) + 1) if self.semantic else {}
             if self.estimate_normal:  # (the normals travel with the pool: loop.GraphedIteration(normal=...) reads them)
                 extra["normal_label"] = self.normal_label_pool
+            if getattr(self.config, "time_conditioned", False):  # (the time stamps too: the loop's time route reads pool.ts)
+                extra["ts"] = self.time_pool
             if self._sorted is None:
                 sp = SortedPool(self.octree, self.coord_pool, self.sdf_label_pool, self.weight_pool, seed=self.seed, **extra)
             else:

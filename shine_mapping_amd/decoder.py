@@ -165,6 +165,13 @@ class Decoder(nn.Module):
             raise NotImplementedError("fused HIP decoder supports 8 -> 32 -> 32 -> 1 with bias (every shipped config)")
         return self._layer_params()
 
+    def time_params(self):
+        """W1 [32,9] = [W1f | w_t], b1, W2, b2, w3, b3 of the time-conditioned head, in place, in the order shine_time_step and the
+        shine_time_mlp_* trio expect (fused_params() is the plain decoder's and refuses this head)."""
+        if not self.time_fusable:
+            raise NotImplementedError("the fused HIP time head supports 9 -> 32 -> 32 -> 1 with bias (is_time_conditioned=True)")
+        return self._layer_params()
+
     def _layer_params(self):
         # (plain dict lookups: nn.Module.__getattr__ / ModuleList.__getitem__ cost ~1 us per hop, and the small-batch loop asks
         # for these six tensors half a dozen times per iteration)

@@ -28,6 +28,12 @@ own K = min(count, n) pairs on the device from a draw state this object owns (ad
 and flags the rows its shifted points reach, so the active-row Adam steps and clears them.  Not served with the regulariser
 (lambda_forget != 0): the reference then regularises the rows of its LAST query_feature call, coord_near's, an accident of call
 order (shine_incre.py:144,156).
+
+With a TIME-CONDITIONED decoder (config.time_conditioned: Decoder(config, is_time_conditioned=True) in the fusable shape,
+decoder.time_fusable) the iteration takes the time route: {draw, ops.fused_time_step on pool / idx (one launch: BCE [+ eikonal]
+through the 9-wide head and the whole backward), the optimiser's graph-safe step with zero_grad}, captured as a stream graph —
+the non-folded form, `native` off.  The pool carries the time stamps (SortedPool(ts=...)).  Not served on that route yet:
+lambda_forget != 0, sem=, normal=, consistency= (their kernels decode with the plain head).
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -37,8 +43,8 @@ import torch
 from . import _lib
 from .autograd_ops import bump_param_epoch
 from .autograd_ops import CONSISTENCY_WORKSPACE_BYTES, NORMAL_WORKSPACE_BYTES, SEM_WORKSPACE_BYTES
-from .ops import (StepOptions, fused_consistency_step, fused_normal_step, fused_regularization, fused_sem_step, fused_train_step,
-                  touched_flags)
+from .ops import (StepOptions, fused_consistency_step, fused_normal_step, fused_regularization, fused_sem_step, fused_time_step,
+                  fused_train_step, touched_flags)
 
 
 @dataclass
@@ -191,7 +197,9 @@ class GraphedIteration(metaclass=_IterationTerms):
     `consistency=ConsistencyTerm(...)` (a keyword of the call too): the gradient-consistency term as the last launch before the
     tail (ops.fused_consistency_step, pairs drawn on the device); `consistency_loss` is its 0-dim device tensor and
     `consistency_draws` = (near_index [K], shift [K,3]) holds the last iteration's pairs.  Raises ValueError with
-    lambda_forget != 0."""
+    lambda_forget != 0.
+    `decoder` time-conditioned (decoder.time_fusable): the time route of the module docstring — `time` is True, `pool` must carry
+    `ts`, and lambda_forget != 0 / sem= / normal= / consistency= raise ValueError before anything is allocated."""
 
     def __init__(self, octree, decoder, pool, opt, opts: StepOptions, n: int, lambda_forget: float = 0.0, unroll: int = 1,
                  fold: bool = True, eager_first: bool = True, active_rows: bool = True, native: bool = True, graph_slot: int = 0,
@@ -199,6 +207,11 @@ class GraphedIteration(metaclass=_IterationTerms):
         self.octree, self.decoder, self.pool, self.opt, self.opts, self.n = octree, decoder, pool, opt, opts, int(n)
         self.lambda_forget = float(lambda_forget)
         self.graph_slot = int(graph_slot)
+        # the time route (a time-conditioned decoder): {draw, fused_time_step, graph-safe Adam} — the non-folded form
+        self.time = bool(getattr(decoder, "time_fusable", False))
+        if self.time:  # (argument errors before anything is allocated)
+            self._check_time(sem)
+            fold = native = False
         self.fold = bool(fold)  # the iteration's tail as one launch (False: reduction, regulariser and Adam as three)
         self.regularize = self.lambda_forget != 0.0
         can_fold = self.fold and hasattr(opt, "finish_iteration") and hasattr(opt, "prepare_graph_safe")
@@ -241,6 +254,10 @@ class GraphedIteration(metaclass=_IterationTerms):
         self.consistency_loss = self.consistency_draws = None
         if self.consistency is not None:
             self._init_consistency(can_fold)
+        if self.time:  # the time step's buffers, made here: a captured graph bakes their addresses in
+            from .autograd_ops import time_step_workspace_bytes
+
+            self._time_ws, self._time_out, self._time_loss = self._term_buffers(time_step_workspace_bytes())
         self.ran_eager = (not self.native) and (bool(eager_first) or dev_key not in _WARMED or not can_fold)
         if can_fold:
             # the optimiser's device-side step state up front: the eager warm-up iteration then runs the SAME two launches the
@@ -307,6 +324,17 @@ class GraphedIteration(metaclass=_IterationTerms):
         self.native = False  # (the library-built graph holds the two-launch iteration)
         self._normal_ws, self._normal_out, self.normal_loss = self._term_buffers(NORMAL_WORKSPACE_BYTES)
 
+    def _check_time(self, sem):
+        if getattr(self.pool, "ts", None) is None:
+            raise ValueError("GraphedIteration with a time-conditioned decoder needs a SortedPool built with ts=")
+        if self.lambda_forget != 0.0:
+            raise ValueError("GraphedIteration with a time-conditioned decoder does not serve lambda_forget != 0 yet")
+        for name, term in (("sem", sem), ("normal", getattr(self, "normal", None)),
+                           ("consistency", getattr(self, "consistency", None))):
+            if term is not None:
+                raise ValueError("GraphedIteration with a time-conditioned decoder does not serve %s= yet: its kernel decodes "
+                                 "with the plain head" % name)
+
     def _check_consistency(self, can_fold):
         term = self.consistency
         if not can_fold:
@@ -356,7 +384,18 @@ class GraphedIteration(metaclass=_IterationTerms):
             ent = self._native[unroll] = (g, out, keep)
         return ent
 
+    def _time_body(self):
+        """the time route's iteration: draw, the one-launch step on pool / idx, the optimiser's graph-safe step"""
+        idx = self.pool.draw(self.n, out=self._idx, graph_safe=True, surf_parts=self._surf)
+        fused_time_step(self.octree, self.decoder, None, None, None, None, self.opts,
+                        n_surf=self._surf if self.opts.ekional_loss_on else None, pool=self.pool, idx=idx, out=self._time_out,
+                        workspace=self._time_ws)
+        self.opt.step(zero_grad=True, graph_safe=True)
+        return self._time_loss, None
+
     def _body(self, graph=None, keep=None):
+        if self.time:
+            return self._time_body()
         idx = self._idx if self._ahead else self.pool.draw(self.n, out=self._idx, graph_safe=True, surf_parts=self._surf)
         n_surf = self._surf if self.opts.ekional_loss_on else None
         # Iteration hooks: the step's reduction launch also counts the optimiser step (+ bias corrections) and clears the

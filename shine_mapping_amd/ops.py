@@ -549,6 +549,99 @@ def fused_consistency_step(octree, decoder, coord, weight_c, near_index=None, sh
 
 
 
+def fused_time_step(octree, decoder, coord, sdf_label, weight, ts, opts: StepOptions, n_surf=None, pool=None, idx=None,
+                    grad_buffers=None, out=None, workspace=None, pred_out=None):
+    """One training iteration's forward + backward of a TIME-CONDITIONED map (config.time_conditioned; shine_batch.py:119-130,
+    141-142,172-185,208-209) in ONE launch (shine_time_step), no optimiser:
+
+        pred = decoder.time_conditionded_sdf(octree.query_feature(coord), ts)
+        loss = sdf_bce_loss(pred, sdf_label, opts.sigma, None, False, opts.loss_reduction)
+        [+ opts.weight_e * ((1 - (get_gradient(coord, pred) * opts.sigma)[weight > 0].norm(2, dim=-1)) ** 2).mean()]
+        loss.backward()
+
+    with fused_train_step's conventions: the eikonal mean is 0 without a surface row, a row with |g| == 0 contributes 1 and gets no
+    gradient through g, 'mean' divides by opts.n_global or N.  `decoder`: Decoder(config, is_time_conditioned=True) in the fusable
+    shape (decoder.time_fusable).  `opts.loss_weight_on` is not served.
+    Array mode: coord [N,3], sdf_label [N], ts [N] float32, weight [N] float32 (read with the eikonal term only; may be None
+    without it), optionally idx (CUDA int32: batch position i reads row idx[i] of all four).  Pool mode: pool = a SortedPool built
+    with ts= and idx = pool.draw(n): the batch is read straight out of the pool's records (the four arrays are ignored).
+    `n_surf` (eikonal): the number of surface rows as an int64 device tensor of one element, or the draw's partial counts
+    (pool.surf_parts_buffer()); default (weight > 0).sum() on the device.
+    Returns the loss as a 0-dim float32 device tensor (no host sync, no grad_fn — the gradients are already in place; `out`: a
+    float32 tensor of one element to write it to).  Accumulates into ``.grad`` of octree.hier_features[*] (dense, trash row
+    included) and of the head's six tensors — W1 [32,9] with its time column —, or into `grad_buffers` = (L feature-grad tensors, 6
+    decoder-grad tensors | None) instead.  A decoder whose parameters do not require grad gets no gradient.  ts gets none.
+    `pred_out`: a CUDA float32 [N] tensor that receives pred at the batch position.
+    `workspace`: zeroed device memory of autograd_ops.time_step_workspace_bytes() bytes the caller owns (default: the current
+    stream's, autograd_ops.time_step_workspace)."""
+    t = octree._require_tables()  # (the kernel probes the hash tables from the coordinates)
+    if not getattr(decoder, "time_fusable", False):
+        raise NotImplementedError("fused_time_step needs the time-conditioned head 9 -> 32 -> 32 -> 1 with bias (decoder.time_fusable)")
+    mlp = decoder.time_params()
+    if bool(opts.loss_weight_on):
+        raise NotImplementedError("fused_time_step does not serve loss_weight_on (False in every shipped config)")
+    if opts.loss_reduction not in ("mean", "sum"):
+        raise ValueError("loss_reduction must be 'mean' or 'sum'")
+    eik = bool(opts.ekional_loss_on)
+    if n_surf is not None and not isinstance(n_surf, torch.Tensor):
+        raise ValueError("n_surf must be a contiguous CUDA int64 tensor (one count, or the draw's partial counts)")
+    if pool is None and not all(isinstance(x, torch.Tensor) for x in (coord, sdf_label, ts) + ((weight,) if eik else ())):
+        raise ValueError("array mode needs coord [N,3], sdf_label [N], ts [N] and, with the eikonal term, weight [N] (or pool= and "
+                         "idx=)")
+    src, stride, n, dev = _term_batch(octree, coord, pool, idx, pool_needs="ts")
+    label = w_keep = None
+    w_ptr, w_stride = None, 1
+    if pool is not None:
+        ts_arr = pool.ts
+        if stride == 3:
+            label, w_keep = pool.soa()[1], pool.soa()[2]
+            w_ptr = w_keep.data_ptr()
+        elif pool._weight_sep is None:  # word 4 of the 32-byte records
+            w_ptr, w_stride, w_keep = pool.rec.data_ptr() + 16, 8, pool.rec
+        else:
+            w_ptr, w_keep = pool._weight_sep.data_ptr(), pool._weight_sep
+        if eik and n_surf is None:
+            n_surf = (pool.weight[idx.long()] > 0).sum()
+    else:
+        rows_n = int(src.shape[0])
+        label = _f32(sdf_label, "sdf_label")
+        ts_arr = ts
+        if label.dim() != 1 or label.numel() != rows_n:
+            raise ValueError("sdf_label must hold one value per coordinate")
+        if eik:
+            w_keep = _f32(weight, "weight")
+            if w_keep.dim() != 1 or w_keep.numel() != rows_n:
+                raise ValueError("weight must hold one value per coordinate")
+            w_ptr = w_keep.data_ptr()
+            if n_surf is None:
+                n_surf = ((w_keep[idx.long()] if idx is not None else w_keep) > 0).sum()
+    if not (isinstance(ts_arr, torch.Tensor) and ts_arr.is_cuda and ts_arr.dtype == torch.float32 and ts_arr.is_contiguous()
+            and ts_arr.numel() == (pool.size if pool is not None else int(src.shape[0]))):
+        raise ValueError("ts must be a contiguous CUDA float32 tensor, one time stamp per coordinate")
+    if eik and not (n_surf.is_cuda and n_surf.dtype == torch.int64 and n_surf.is_contiguous() and 1 <= n_surf.numel() <= 64):
+        raise ValueError("n_surf must be a contiguous CUDA int64 tensor (one count, or the draw's partial counts)")
+    if pred_out is not None and not (isinstance(pred_out, torch.Tensor) and pred_out.is_cuda and pred_out.dtype == torch.float32
+                                     and pred_out.is_contiguous() and pred_out.numel() == n):
+        raise ValueError("pred_out must be a contiguous CUDA float32 tensor of N elements")
+    if not decoder._params_on(dev, mlp):
+        raise ValueError("the decoder's parameters must be CUDA float32 contiguous on the batch's device")
+    gfeat, gmlp = _term_targets(octree, mlp, grad_buffers, "the decoder's")
+    out = _term_out(out, dev)
+    ws = workspace if workspace is not None else autograd_ops.time_step_workspace(dev)
+    n_global = int(opts.n_global) if opts.n_global else n
+    cfg = octree.step_config(sigma=float(opts.sigma), weight_e=float(opts.weight_e), eikonal_on=1 if eik else 0,
+                             reduction_sum=1 if opts.loss_reduction == "sum" else 0, n_global=n_global,
+                             inv_n=(1.0 if opts.loss_reduction == "sum" else 1.0 / max(n_global, 1)))
+    ws_bytes = C.c_size_t(int(ws.numel()) * int(ws.element_size()))
+    _term_call("shine_time_step", octree, t.handle, C.byref(cfg), src.data_ptr(), stride,
+               idx.data_ptr() if idx is not None else None, label.data_ptr() if label is not None else None,
+               w_ptr if eik else None, w_stride, ts_arr.data_ptr(), n_surf.data_ptr() if eik else None,
+               int(n_surf.numel()) if eik else 0, n, *_term_ptrs(octree, mlp, gfeat, gmlp),
+               pred_out.data_ptr() if pred_out is not None else None, out.data_ptr(), ws.data_ptr(), C.byref(ws_bytes))
+    del w_keep  # (the weights outlive the call)
+    return out.view(())
+
+
 def octree_interp(octree, coord):
     """FeatureOctree.query_feature (model/feature_octree.py:237-244) -> [N,8]; also fills hierarchical_indices."""
     needs_grad = torch.is_grad_enabled() and (

@@ -110,7 +110,7 @@ class DrawChain:
 
 class SortedPool:
     def __init__(self, octree, coord, sdf_label, weight, seed=42, canonical=False, sem_label=None, n_class=None,
-                 normal_label=None):
+                 normal_label=None, ts=None):
         """`canonical`: order the samples of one node by their original pool index.  The plan's counting sort places the
         samples of a node in whatever order its atomics retire, so two processes (or two runs) hold the same pool in
         different within-node orders: still a valid pool — draws stay i.i.d. uniform — but not the SAME draw.  Data-parallel
@@ -121,7 +121,9 @@ class SortedPool:
         and raises ValueError otherwise (one min / max, outside the iteration).
         `normal_label` (normal_loss_on): the samples' normals [P,3]; kept in pool order as a contiguous float32 [P,3]
         `self.normal_label` for ops.fused_normal_step(pool=...) — 12 B per sample, paid only when it is given.  Like `sem_label`,
-        a rebuild without it deletes the attribute."""
+        a rebuild without it deletes the attribute.
+        `ts` (time_conditioned): the samples' time stamps [P]; kept in pool order as a contiguous float32 `self.ts` for
+        ops.fused_time_step(pool=...) — 4 B per sample, paid only when it is given; checked and dropped the same way."""
         self.octree = octree
         self.canonical = bool(canonical)
         self.seed = int(seed)
@@ -130,11 +132,13 @@ class SortedPool:
         self._stream_state = None  # device uint64[4] for graph-replayable draws (loop.GraphedIteration)
         self._rider_for = None     # size of the draw whose first pass the last fused step carried (StepOptions.next_draw)
         self.n_class = None if n_class is None else int(n_class)
-        self.rebuild(coord, sdf_label, weight, sem_label=sem_label, normal_label=normal_label)
+        self.rebuild(coord, sdf_label, weight, sem_label=sem_label, normal_label=normal_label, ts=ts)
 
-    def rebuild(self, coord, sdf_label, weight, sem_label=None, n_class=None, normal_label=None):
+    def rebuild(self, coord, sdf_label, weight, sem_label=None, n_class=None, normal_label=None, ts=None):
         if n_class is not None:
             self.n_class = int(n_class)
+        if ts is not None and ts.numel() != coord.shape[0]:
+            raise ValueError("ts must hold one time stamp per pool sample")
         if normal_label is not None and (normal_label.dim() != 2 or tuple(normal_label.shape) != (coord.shape[0], 3)):
             raise ValueError("normal_label must hold one [3] normal per pool sample")
         if sem_label is not None:
@@ -192,6 +196,10 @@ class SortedPool:
             self.normal_label = normal_label[p].to(torch.float32).contiguous()
         elif hasattr(self, "normal_label"):
             del self.normal_label
+        if ts is not None:
+            self.ts = ts.reshape(-1)[p].to(torch.float32).contiguous()
+        elif hasattr(self, "ts"):
+            del self.ts
         self.tables_epoch = self.octree._tables_epoch
         # sampler scratch of other pool sizes is dead weight (a graph captured for the old pool is invalid anyway: the
         # tables epoch moved); without this an object rebuilt every frame pins one buffer per distinct frame size
