@@ -427,6 +427,43 @@ int shine_time_step(const shine_tables* t, const shine_step_config* cfg, const f
                     float* const* grad_feats, const float* const* mlp, float* const* grad_mlp, float* pred_out, float* loss_out,
                     void* workspace, size_t* workspace_bytes, void* stream);
 
+/* ---- Tier B with ray_loss: one training iteration's forward + backward of a map trained by ray rendering (shine_batch.py:
+ *      119-130,160-170,172-185,208-209, main_loss_type dr / dr_neus) in ONE launch — the step the graphed loop's ray route runs.
+ *      The pool is ray-major: ray i owns rows i * samples .. i * samples + samples - 1 of coord [., 3], weight [.] and
+ *      sample_depth [.], and entry i of ray_depth.  Batch ray i is pool ray idx[i] (without idx: ray i); batch row r = i * samples + s.
+ *        f = query_feature(x);  pred = w3 . relu(W2 relu(W1 f + b1) + b2) + b3   the plain 8 -> 32 -> 32 -> 1 head, mlp as for
+ *        shine_normal_train_step;  y = sigmoid(pred / *sigma_size) — sigma_size: ONE float in device memory, read by the launch;
+ *        render = batch_ray_rendering_loss(sample_depth, y, ray_depth, neus_on) over the n_rays rays: per ray the samples in
+ *        depth order (ties by column), alphas y (dr) or clamp((y[i+1] - y[i]) / (1 - y[i] + 1e-10), 0, 1) (dr_neus),
+ *        o = 1 - a + 1e-10, d = sum(cumprod(o) / o * a * depth), render = mean |d - ray_depth| — the arithmetic of
+ *        shine_ray_render_loss, rounding for rounding;
+ *        with cfg->eikonal_on: g = cfg->sigma d pred / d x, eik = mean over weight > 0 of (1 - |g|)^2 — 0 without such a row; a
+ *        row with |g| == 0 contributes 1 and gets no gradient through g;
+ *        *loss_out = render + cfg->weight_e * eik (float; the sums in fp64 from the lanes up).
+ *      Gradients: grad_feats as for shine_time_step (ACCUMULATED INTO, trash row included).  grad_mlp: NULL (a frozen decoder) or 6
+ *      tensors shaped like mlp, ADDED to.  sigma_grad: NULL (a frozen sigma_size) or one float that
+ *      d loss / d sigma_size = sum dL/dy . y (1 - y) . (-pred / sigma_size^2) is ADDED to.  All of these sums and the loss are
+ *      bit-identical from call to call.  The launch re-zeroes the trash row of every feature table.
+ *      pred_out / dpred_out: NULL or float32 [n_rays * samples], written at the batch position: pred and d render / d pred.
+ *      n_surf / n_surf_parts as for shine_normal_train_step (cfg->eikonal_on only): the batch's rows with weight > 0.
+ *      samples: 1 .. SHINE_RAY_MAX_SAMPLES; a tile of the launch holds 64 / samples whole rays.  samples == 1 with neus_on has no
+ *      alpha: the loss is mean |ray_depth| and nothing receives a gradient.
+ *      Of cfg: n_levels, max_level, poly_int_on, eikonal_on, sigma, weight_e are read.
+ *      workspace: as for shine_time_step (size query, 256-byte aligned ticket workspace, zero before, left ALL zero).
+ *      n_rays == 0 launches nothing and writes a loss of 0.
+ *      SHINE_E_INVALID, worded "shine_ray_step: <defect>", before anything touches the device: a null table handle / cfg / feats /
+ *      rows / loss_out / workspace_bytes / decoder tensor, a misaligned or short workspace, n_rays < 0, samples < 1 or
+ *      > SHINE_RAY_MAX_SAMPLES, n_rays * samples >= 2^31, a null coord / sample_depth / ray_depth / sigma_size / weight / n_surf
+ *      (eikonal) with n_rays > 0, more than 4 featured levels.
+ *      shine_ray_surf_count: *count_out = sum over the n batch rays of surf_per_ray[idx[i]] (int32 counts of a ray's samples with
+ *      weight > 0; idx NULL: ray i) — the n_surf of a drawn batch, one small launch. */
+int shine_ray_step(const shine_tables* t, const shine_step_config* cfg, const float* coord, const int32_t* idx, const float* weight,
+                   const float* sample_depth, const float* ray_depth, const float* sigma_size, int32_t samples, int32_t neus_on,
+                   const int64_t* n_surf, int32_t n_surf_parts, int64_t n_rays, const float* const* feats, const int64_t* rows,
+                   float* const* grad_feats, const float* const* mlp, float* const* grad_mlp, float* sigma_grad, float* pred_out,
+                   float* dpred_out, float* loss_out, void* workspace, size_t* workspace_bytes, void* stream);
+int shine_ray_surf_count(const int32_t* idx, const int32_t* surf_per_ray, int64_t n, int64_t* count_out, void* stream);
+
 /* ---- Tier A (strict drop-in): the backward of FeatureOctree.query_feature as autograd derives it from
  *      model/feature_octree.py:222-234, and its own backward (needed by get_gradient(create_graph=True),
  *      utils/tools.py:175-185, when the eikonal term is differentiated, shine_batch.py:182-185).

@@ -197,6 +197,10 @@ _SIGNATURES = {
     "shine_time_step": (C.c_int, [_P, C.POINTER(StepConfig), _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int64,
                                   C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P, _P,
                                   C.POINTER(C.c_size_t), _P]),
+    "shine_ray_step": (C.c_int, [_P, C.POINTER(StepConfig), _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int64,
+                                 C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P, _P, _P,
+                                 _P, C.POINTER(C.c_size_t), _P]),
+    "shine_ray_surf_count": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
     # meshing (csrc/shine_mc.hip, csrc/shine_mesh.hip)
     "shine_mc_count": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_float, _P, C.POINTER(C.c_size_t),
                                  C.POINTER(C.c_int64), _P]),

@@ -718,6 +718,25 @@ def time_step_workspace(device):
     return _lib.ticket_workspace(device, time_step_workspace_bytes())
 
 
+_RAY_STEP_WORKSPACE_BYTES = None
+
+
+def ray_step_workspace_bytes():
+    """what shine_ray_step's size query answers (one size for every batch; asked once)"""
+    global _RAY_STEP_WORKSPACE_BYTES
+    if _RAY_STEP_WORKSPACE_BYTES is None:
+        need = C.c_size_t(0)
+        _lib.check(_lib.lib().shine_ray_step(None, None, None, None, None, None, None, None, 1, 0, None, 0, 0, None, None, None, None,
+                                             None, None, None, None, None, None, C.byref(need), None), "shine_ray_step")
+        _RAY_STEP_WORKSPACE_BYTES = int(need.value)
+    return _RAY_STEP_WORKSPACE_BYTES
+
+
+def ray_step_workspace(device):
+    """the workspace of shine_ray_step for the current stream of `device`"""
+    return _lib.ticket_workspace(device, ray_step_workspace_bytes())
+
+
 CONSISTENCY_WORKSPACE_BYTES = 1429888  # SHINE_CONSISTENCY_WORKSPACE_BYTES
 
 

@@ -9,6 +9,7 @@
 // Repeated calls give the same bits.
 #include "shine_arrive.hpp"
 #include "shine_internal.hpp"
+#include "shine_ray_render.hpp"
 
 // The composite rounds every product and sum on its own; so do these kernels (no a * b + c contracted into one rounding).
 // Saturated rays (a probability of exactly 0 or 1) make the autograd form of the gradient a difference of ~1e10-sized terms:
@@ -92,19 +93,9 @@ __global__ __launch_bounds__(kDiffThreads) void k_sdf_diff_loss(const float* __r
 // of their own rows hit 32 different banks), the row kept in registers of a fully unrolled S_MAX-element network.
 constexpr int kRayThreads = 128;
 
-// sort key: padding columns (>= S) last, then x with NaN after every number (torch.sort's order), then the column — ties are
-// broken by the column, so any network gives the stable order, and the S real columns always fill positions 0..S-1
-__device__ __forceinline__ bool key_gt(float xa, int ia, float xb, int ib, int S) {
-  const bool pa = ia >= S, pb = ib >= S;
-  if (pa != pb) return pa;
-  const bool na = xa != xa, nb = xb != xb;
-  if (na != nb) return na;
-  if (!na && xa != xb) return xa > xb;
-  return ia > ib;
-}
-
+// (the sort key ray_key_gt and the per-sample arithmetic: shine_ray_render.hpp, shared with the ray step)
 __device__ __forceinline__ void cmpx(float& xa, float& ya, int& ia, float& xb, float& yb, int& ib, bool up, int S) {
-  const bool a_gt = key_gt(xa, ia, xb, ib, S);
+  const bool a_gt = ray_key_gt(xa, ia, xb, ib, S);
   const bool swap = up ? a_gt : !a_gt;
   const float tx = xa, ty = ya;
   const int ti = ia;
@@ -171,17 +162,11 @@ __global__ __launch_bounds__(kRayThreads) void k_ray_render_loss(const float* __
         a[k] = 0.f, o[k] = 1.f, c[k] = 1.f;
         if (k < A) {
           if (NEUS) {
-            if (k + 1 < SM) {
-              const float q = (vy[k + 1] - vy[k]) / ((1.0f - vy[k]) + 1e-10f);
-              a[k] = fminf(fmaxf(q, 0.f), 1.f);
-            }
+            if (k + 1 < SM) a[k] = ray_neus_alpha(vy[k], vy[k + 1]);
           } else {
             a[k] = vy[k];
           }
-          o[k] = (1.0f - a[k]) + 1e-10f;
-          cp *= (double)o[k];
-          c[k] = (float)cp;
-          d += ((c[k] / o[k]) * a[k]) * vx[k];
+          ray_forward(a[k], vx[k], cp, o[k], c[k], d);
         }
       }
       const float dm = d_meas[r0 + lr];
@@ -189,32 +174,19 @@ __global__ __launch_bounds__(kRayThreads) void k_ray_render_loss(const float* __
       acc += (double)fabsf(err);
       // backward for an upstream gradient of 1: mean -> abs -> sum -> w x -> (c / o) a -> cumprod -> (1 - a) + 1e-10
       // [-> clamp -> the neus quotient], walking the samples from the far end (the reversed cumsum of cumprod's backward)
-      const float gd = inv_r * (err > 0.f ? 1.f : (err < 0.f ? -1.f : 0.f));
+      const float gd = ray_err_grad(err, inv_r);
       float gy[SM];
       double rc = 0.0;
 #pragma unroll
       for (int k = SM - 1; k >= 0; --k) {
         gy[k] = 0.f;
         if (k < A) {
-          const float gw = gd * vx[k];
-          const float qq = c[k] / o[k];
-          const float gqq = gw * a[k];
-          const float ga = gw * qq;
-          const float gc = gqq / o[k];
-          const float go_div = -gqq * (qq / o[k]);
-          rc += (double)(gc * c[k]);
-          const float go_cum = A == 1 ? gc : (float)rc / o[k];  // (torch returns the gradient itself for a length-1 cumprod)
-          const float ga_t = ga + -(go_cum + go_div);
+          const float ga_t = ray_backward(gd, vx[k], a[k], o[k], c[k], rc, A == 1);
           if (NEUS) {
             if (k + 1 < SM) {
-              const float num = vy[k + 1] - vy[k];
-              const float den = (1.0f - vy[k]) + 1e-10f;
-              const float q = num / den;
-              const float gq = (q >= 0.f && q <= 1.f) ? ga_t : 0.f;
-              const float gnum = gq / den;
-              const float gden = -gq * (q / den);
+              float gnum;
+              ray_neus_backward(vy[k], vy[k + 1], ga_t, gnum, gy[k]);
               gy[k + 1] += gnum;
-              gy[k] = -gnum + -gden;
             }
           } else {
             gy[k] = ga_t;

@@ -855,6 +855,27 @@ class LiDARDataset:
             self._sorted_perm = sp.perm.long()
         return self._sorted[0]
 
+    def ray_pool(self):
+        """the pools of ray mode (config.ray_loss) as a sampler.RayPool, planned when the pools or the octree changed: what
+        loop.GraphedIteration(ray=RayTerm(...)) / ops.fused_ray_step(pool=...) take"""
+        from .sampler import RayPool
+
+        if not self.config.ray_loss:
+            raise ValueError("LiDARDataset.ray_pool serves ray mode (config.ray_loss); the point-sample pools are sorted_pool()'s")
+        if self.octree is None or self.to_cpu:
+            raise ValueError("LiDARDataset.ray_pool needs the octree the dataset was built with and the pools on the device")
+        key = (self._pool_version, self.octree._tables_epoch)
+        cached = getattr(self, "_ray_pool", None)
+        if cached is None or cached[1] != key:
+            pools = (self.coord_pool, self.weight_pool, self.sample_depth_pool, self.ray_depth_pool)
+            if cached is None:
+                rp = RayPool(self.octree, *pools, samples=self.ray_sample_count, seed=self.seed)
+            else:
+                rp = cached[0]
+                rp.rebuild(*pools, samples=self.ray_sample_count)
+            self._ray_pool = (rp, key)
+        return self._ray_pool[0]
+
     def get_batch(self):
         cfg = self.config
         if cfg.ray_loss:

@@ -34,6 +34,13 @@ decoder.time_fusable) the iteration takes the time route: {draw, ops.fused_time_
 through the 9-wide head and the whole backward), the optimiser's graph-safe step with zero_grad}, captured as a stream graph —
 the non-folded form, `native` off.  The pool carries the time stamps (SortedPool(ts=...)).  Not served on that route yet:
 lambda_forget != 0, sem=, normal=, consistency= (their kernels decode with the plain head).
+
+With `ray=RayTerm(sigma_size, neus_on)` (config.ray_loss, main_loss_type dr / dr_neus) and a sampler.RayPool the iteration takes
+the ray route: {ray_pool.draw of n RAYS (+ the batch's surface count with the eikonal term), ops.fused_ray_step on pool / idx (one
+launch: the head, the per-ray render, [the eikonal term] and the whole backward, sigma_size's gradient included), the optimiser's
+graph-safe step with zero_grad}, captured as a stream graph — the non-folded form, `native` off.  The optimiser is
+setup_optimizer(config, feats, geo_params, None, sigma_size) with config.ray_loss: its step moves sigma_size with the tables and
+the decoder.  Not served on that route: a time-conditioned decoder, lambda_forget != 0, sem=, normal=, consistency=.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -43,8 +50,8 @@ import torch
 from . import _lib
 from .autograd_ops import bump_param_epoch
 from .autograd_ops import CONSISTENCY_WORKSPACE_BYTES, NORMAL_WORKSPACE_BYTES, SEM_WORKSPACE_BYTES
-from .ops import (StepOptions, fused_consistency_step, fused_normal_step, fused_regularization, fused_sem_step, fused_time_step,
-                  fused_train_step, touched_flags)
+from .ops import (StepOptions, fused_consistency_step, fused_normal_step, fused_ray_step, fused_regularization, fused_sem_step,
+                  fused_time_step, fused_train_step, touched_flags)
 
 
 @dataclass
@@ -77,6 +84,16 @@ class ConsistencyTerm:
     seed: int = 0
 
 
+@dataclass
+class RayTerm:
+    """The ray route of GraphedIteration(ray=...): the learnable sigma_size of the rendering loss (a CUDA float32 tensor of one
+    element, in the optimiser's last group: setup_optimizer(config, feats, geo_params, None, sigma_size) with config.ray_loss) and
+    main_loss_type dr (False) / dr_neus (True) (shine_batch.py:160-170); the pool is a sampler.RayPool."""
+
+    sigma_size: object
+    neus_on: bool = False
+
+
 class _IterationTerms(type):
     """GraphedIteration(..., normal=NormalTerm(...)): loss terms added after `sem` are keyword arguments of the CALL, set on the
     object before its constructor runs — the constructor's own parameter list is what existing callers (and the suite) spell out
@@ -87,10 +104,11 @@ class _IterationTerms(type):
     move `normal` into the constructor and delete this class.  A third term now hangs on the hook: `consistency`
     (ConsistencyTerm) rides the same way, under the same constraint."""
 
-    def __call__(cls, *args, normal=None, consistency=None, **kw):
+    def __call__(cls, *args, normal=None, consistency=None, ray=None, **kw):
         self = cls.__new__(cls)
         self.normal = normal
         self.consistency = consistency
+        self.ray = ray  # (the ray route's RayTerm: a fourth keyword on the same hook)
         self.__init__(*args, **kw)
         return self
 
@@ -207,6 +225,11 @@ class GraphedIteration(metaclass=_IterationTerms):
         self.octree, self.decoder, self.pool, self.opt, self.opts, self.n = octree, decoder, pool, opt, opts, int(n)
         self.lambda_forget = float(lambda_forget)
         self.graph_slot = int(graph_slot)
+        # the ray route (ray=RayTerm(...) and a RayPool): {draw, fused_ray_step, graph-safe Adam} — the non-folded form
+        self.ray = getattr(self, "ray", None)
+        if self.ray is not None or hasattr(pool, "surf_per_ray"):  # (argument errors before anything is allocated)
+            self._check_ray(sem)
+            fold = native = False
         # the time route (a time-conditioned decoder): {draw, fused_time_step, graph-safe Adam} — the non-folded form
         self.time = bool(getattr(decoder, "time_fusable", False))
         if self.time:  # (argument errors before anything is allocated)
@@ -233,7 +256,10 @@ class GraphedIteration(metaclass=_IterationTerms):
         # the eikonal term's surface count: per-block partial counts written by the draw itself, summed by the step's kernels
         self.normal = getattr(self, "normal", None)
         # (... and the normal term's: both divide by the batch's surface count)
-        self._surf = pool.surf_parts_buffer(self.n) if (opts.ekional_loss_on or self.normal is not None) else None
+        if self.ray is not None:
+            self._surf = pool.surf_buffer() if opts.ekional_loss_on else None
+        else:
+            self._surf = pool.surf_parts_buffer(self.n) if (opts.ekional_loss_on or self.normal is not None) else None
         self.loss = self.reg = None
         self._reg_out = torch.zeros(1, dtype=torch.float64, device=pool.coord.device) if self.regularize else None
         self._hooked = None  # StepOptions with the iteration hooks (made once the optimiser has its device state)
@@ -258,6 +284,10 @@ class GraphedIteration(metaclass=_IterationTerms):
             from .autograd_ops import time_step_workspace_bytes
 
             self._time_ws, self._time_out, self._time_loss = self._term_buffers(time_step_workspace_bytes())
+        if self.ray is not None:  # the ray step's buffers, made here too
+            from .autograd_ops import ray_step_workspace_bytes
+
+            self._ray_ws, self._ray_out, self._ray_loss = self._term_buffers(ray_step_workspace_bytes())
         self.ran_eager = (not self.native) and (bool(eager_first) or dev_key not in _WARMED or not can_fold)
         if can_fold:
             # the optimiser's device-side step state up front: the eager warm-up iteration then runs the SAME two launches the
@@ -335,6 +365,22 @@ class GraphedIteration(metaclass=_IterationTerms):
                 raise ValueError("GraphedIteration with a time-conditioned decoder does not serve %s= yet: its kernel decodes "
                                  "with the plain head" % name)
 
+    def _check_ray(self, sem):
+        if self.ray is None:
+            raise ValueError("GraphedIteration with a RayPool needs ray=RayTerm(sigma_size, neus_on)")
+        if not hasattr(self.pool, "surf_per_ray"):
+            raise ValueError("GraphedIteration(ray=...) needs a sampler.RayPool (LiDARDataset.ray_pool())")
+        if getattr(self.decoder, "time_fusable", False) or getattr(self.decoder, "is_time_conditioned", False):
+            raise ValueError("GraphedIteration(ray=...) does not serve a time-conditioned decoder: the ray step decodes with the "
+                             "plain head")
+        if self.lambda_forget != 0.0:
+            raise ValueError("GraphedIteration(ray=...) does not serve lambda_forget != 0")
+        for name, term in (("sem", sem), ("normal", getattr(self, "normal", None)),
+                           ("consistency", getattr(self, "consistency", None))):
+            if term is not None:
+                raise ValueError("GraphedIteration(ray=...) does not serve %s=: ray mode combined with the other terms is out of "
+                                 "scope" % name)
+
     def _check_consistency(self, can_fold):
         term = self.consistency
         if not can_fold:
@@ -393,7 +439,18 @@ class GraphedIteration(metaclass=_IterationTerms):
         self.opt.step(zero_grad=True, graph_safe=True)
         return self._time_loss, None
 
+    def _ray_body(self):
+        """the ray route's iteration: draw n rays, the one-launch step on pool / idx, the optimiser's graph-safe step"""
+        idx = self.pool.draw(self.n, out=self._idx, graph_safe=True, surf_out=self._surf)
+        fused_ray_step(self.octree, self.decoder, None, None, None, None, self.ray.sigma_size, self.opts, None,
+                       neus_on=bool(self.ray.neus_on), n_surf=self._surf, pool=self.pool, idx=idx, out=self._ray_out,
+                       workspace=self._ray_ws)
+        self.opt.step(zero_grad=True, graph_safe=True)
+        return self._ray_loss, None
+
     def _body(self, graph=None, keep=None):
+        if self.ray is not None:
+            return self._ray_body()
         if self.time:
             return self._time_body()
         idx = self._idx if self._ahead else self.pool.draw(self.n, out=self._idx, graph_safe=True, surf_parts=self._surf)

@@ -642,6 +642,104 @@ def fused_time_step(octree, decoder, coord, sdf_label, weight, ts, opts: StepOpt
     return out.view(())
 
 
+RAY_MAX_SAMPLES = 32  # include/shine_hip.h SHINE_RAY_MAX_SAMPLES
+
+
+def _f32_n(x, numel, what):
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() == numel):
+        raise ValueError("%s must be a contiguous CUDA float32 tensor of %d elements" % (what, numel))
+    return x
+
+
+def fused_ray_step(octree, decoder, coord, weight, sample_depth, ray_depth, sigma_size, opts: StepOptions, samples, neus_on=False,
+                   n_surf=None, pool=None, idx=None, grad_buffers=None, sigma_grad=None, out=None, workspace=None, pred_out=None,
+                   dpred_out=None):
+    """One training iteration's forward + backward of a map trained by RAY RENDERING (config.ray_loss with main_loss_type dr /
+    dr_neus; shine_batch.py:119-130,160-170,172-185,208-209) in ONE launch (shine_ray_step), no optimiser:
+
+        pred = decoder.sdf(octree.query_feature(coord))
+        loss = losses.batch_ray_rendering_loss(sample_depth.view(-1, S), torch.sigmoid(pred / sigma_size).view(-1, S), ray_depth,
+                                               neus_on)
+        [+ opts.weight_e * ((1 - (get_gradient(coord, pred) * opts.sigma)[weight > 0].norm(2, dim=-1)) ** 2).mean()]
+        loss.backward()
+
+    with fused_train_step's conventions for the eikonal term: 0 without a surface row, a row with |g| == 0 contributes 1 and gets
+    no gradient through g.  `decoder`: the plain 8 -> 32 -> 32 -> 1 geometry head.  `samples` = S = surface_sample_n +
+    free_sample_n (1 .. 32).  `sigma_size`: the learnable CUDA float32 tensor of one element; the launch reads it on the device.
+    Array mode: ray-major coord [m*S,3], weight [m*S] (read with the eikonal term only; may be None without it), sample_depth
+    [m*S], ray_depth [m]; optionally idx (CUDA int32: batch ray i is ray idx[i]).  Pool mode: pool = a sampler.RayPool and idx =
+    pool.draw(n) (the four arrays and `samples` are the pool's).
+    `n_surf` (eikonal): the batch's rows with weight > 0 as an int64 device tensor (one count, e.g. RayPool.draw(surf_out=...), or
+    up to 64 partial counts); default: counted here on the device.
+    Returns the loss as a 0-dim float32 device tensor (no host sync, no grad_fn — the gradients are already in place; `out`: a
+    float32 tensor of one element to write it to).  Accumulates into ``.grad`` of octree.hier_features[*] (dense, trash row
+    included), of the head's six tensors and of sigma_size — or into `grad_buffers` = (L feature-grad tensors, 6 decoder-grad
+    tensors | None) and `sigma_grad` (a CUDA float32 tensor of one element) instead.  A decoder whose parameters do not require
+    grad gets no gradient (a half-frozen one is refused); a sigma_size that does not require grad gets none either.
+    `pred_out` / `dpred_out`: CUDA float32 [n*S] tensors that receive pred and d (render term) / d pred at the batch position.
+    `workspace`: zeroed device memory of autograd_ops.ray_step_workspace_bytes() bytes the caller owns (default: the current
+    stream's, autograd_ops.ray_step_workspace)."""
+    t = octree._require_tables()  # (the kernel probes the hash tables from the coordinates)
+    if getattr(decoder, "time_fusable", False) or not hasattr(decoder, "fused_params"):
+        raise NotImplementedError("fused_ray_step needs the plain geometry head 8 -> 32 -> 32 -> 1 (not a time-conditioned decoder)")
+    mlp = decoder.fused_params()
+    eik = bool(opts.ekional_loss_on)
+    if n_surf is not None and not isinstance(n_surf, torch.Tensor):
+        raise ValueError("n_surf must be a contiguous CUDA int64 tensor (one count, or partial counts)")
+    if pool is not None:
+        _check_pool_idx(octree, pool, idx)
+        if not hasattr(pool, "surf_per_ray"):
+            raise ValueError("pool mode needs a sampler.RayPool")
+        coord, weight, sample_depth, ray_depth, S = pool.coord, pool.weight, pool.sample_depth, pool.ray_depth, int(pool.samples)
+    else:
+        S = int(samples)
+        if not all(isinstance(x, torch.Tensor) for x in (coord, sample_depth, ray_depth) + ((weight,) if eik else ())):
+            raise ValueError("array mode needs coord [m*S,3], sample_depth [m*S], ray_depth [m] and, with the eikonal term, weight "
+                             "[m*S] (or pool= and idx=)")
+        if idx is not None and not _i32c(idx):
+            raise ValueError("idx must be a contiguous CUDA int32 tensor")
+    if not 1 <= S <= RAY_MAX_SAMPLES:
+        raise ValueError("samples must be 1 .. %d (SHINE_RAY_MAX_SAMPLES)" % RAY_MAX_SAMPLES)
+    src = octree._check_coord(coord.detach())
+    dev = src.device
+    m = int(ray_depth.numel()) if isinstance(ray_depth, torch.Tensor) else -1
+    if int(src.shape[0]) != m * S:
+        raise ValueError("coord must hold samples rows per entry of ray_depth (ray-major)")
+    _f32_n(sample_depth, m * S, "sample_depth")
+    _f32_n(ray_depth, m, "ray_depth")
+    if eik:
+        _f32_n(weight, m * S, "weight")
+    _f32_n(sigma_size, 1, "sigma_size")
+    n = int(idx.numel()) if idx is not None else m
+    if eik:
+        if n_surf is None:
+            w2 = weight.view(m, S)
+            n_surf = ((w2[idx.long()] if idx is not None else w2) > 0).sum()
+        if not (n_surf.is_cuda and n_surf.dtype == torch.int64 and n_surf.is_contiguous() and 1 <= n_surf.numel() <= 64):
+            raise ValueError("n_surf must be a contiguous CUDA int64 tensor (one count, or partial counts)")
+    for name, o in (("pred_out", pred_out), ("dpred_out", dpred_out)):
+        if o is not None:
+            _f32_n(o, n * S, name)
+    if not decoder._params_on(dev, mlp):
+        raise ValueError("the decoder's parameters must be CUDA float32 contiguous on the batch's device")
+    gfeat, gmlp = _term_targets(octree, mlp, grad_buffers, "the decoder's")
+    if sigma_grad is not None:
+        _f32_n(sigma_grad, 1, "sigma_grad")
+    elif sigma_size.requires_grad:
+        sigma_grad = _dense_grad(sigma_size)
+    out = _term_out(out, dev)
+    ws = workspace if workspace is not None else autograd_ops.ray_step_workspace(dev)
+    cfg = octree.step_config(sigma=float(opts.sigma), weight_e=float(opts.weight_e), eikonal_on=1 if eik else 0)
+    ws_bytes = C.c_size_t(int(ws.numel()) * int(ws.element_size()))
+    _term_call("shine_ray_step", octree, t.handle, C.byref(cfg), src.data_ptr(), idx.data_ptr() if idx is not None else None,
+               weight.data_ptr() if eik else None, sample_depth.data_ptr(), ray_depth.data_ptr(), sigma_size.data_ptr(), S,
+               1 if neus_on else 0, n_surf.data_ptr() if eik else None, int(n_surf.numel()) if eik else 0, n,
+               *_term_ptrs(octree, mlp, gfeat, gmlp), sigma_grad.data_ptr() if sigma_grad is not None else None,
+               pred_out.data_ptr() if pred_out is not None else None, dpred_out.data_ptr() if dpred_out is not None else None,
+               out.data_ptr(), ws.data_ptr(), C.byref(ws_bytes))
+    return out.view(())
+
+
 def octree_interp(octree, coord):
     """FeatureOctree.query_feature (model/feature_octree.py:237-244) -> [N,8]; also fills hierarchical_indices."""
     needs_grad = torch.is_grad_enabled() and (

@@ -352,3 +352,108 @@ class SortedPool:
             return self.coord[i], self.sdf_label[i], self.weight[i]
         r = self.rec[i].view(torch.float32)  # (one gather of the drawn records)
         return r[:, 0:3].contiguous(), r[:, 3].contiguous(), (r[:, 4].contiguous() if self._weight_sep is None else self._weight_sep[i])
+
+
+RAY_MAX_SAMPLES = 32  # include/shine_hip.h SHINE_RAY_MAX_SAMPLES
+
+
+class RayPool:
+    """The pools of ray mode (config.ray_loss: main_loss_type dr / dr_neus) as what the loop's ray route draws from.  A batch is
+    not a bag of points there: RAYS are drawn, each brings its S = surface_sample_n + free_sample_n samples, and the loss couples
+    the samples of a ray.  coord [m*S,3], weight [m*S], sample_depth [m*S] and ray_depth [m] are kept ray-major (ray i owns rows
+    i*S .. i*S+S-1), contiguous float32 on the device, the rays in the octree-node order of their FIRST sample (`perm`: pool ray j
+    is source ray perm[j]) so that a sorted draw walks the tables in order.  `surf_per_ray` (int32 [m]) counts every ray's samples
+    with weight > 0, whatever the sign pattern, for the eikonal term's surface count.
+
+    draw(n) returns n ray indices in ascending order, i.i.d. uniform with replacement: the sorted sampler of SortedPool over m
+    items, with its device-side stream state under graph_safe — a captured draw yields a fresh batch at every replay.
+    ops.fused_ray_step(pool=self, idx=idx) reads the batch straight out of the pool."""
+
+    def __init__(self, octree, coord, weight, sample_depth, ray_depth, samples, seed=42):
+        self.octree = octree
+        self.seed = int(seed)
+        self.draws = 0
+        self._ws = {}  # per batch size, never replaced: captured HIP graphs bake the address in
+        self._stream_state = None
+        self.rebuild(coord, weight, sample_depth, ray_depth, samples)
+
+    def rebuild(self, coord, weight, sample_depth, ray_depth, samples=None):
+        S = int(samples) if samples is not None else self.samples
+        if S < 1 or S > RAY_MAX_SAMPLES:
+            raise ValueError("RayPool: samples must be 1 .. %d (SHINE_RAY_MAX_SAMPLES)" % RAY_MAX_SAMPLES)
+        for name, x in (("coord", coord), ("weight", weight), ("sample_depth", sample_depth), ("ray_depth", ray_depth)):
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+                raise ValueError("RayPool: %s must be a float32 tensor" % name)
+        m = int(ray_depth.numel())
+        if (ray_depth.dim() != 1 or coord.dim() != 2 or tuple(coord.shape) != (m * S, 3) or tuple(weight.shape) != (m * S,)
+                or tuple(sample_depth.shape) != (m * S,)):
+            raise ValueError("RayPool: coord [m*S,3], weight [m*S] and sample_depth [m*S] must hold samples = %d rows per entry of "
+                             "ray_depth [m] (m = %d)" % (S, m))
+        if not (coord.is_cuda and weight.device == coord.device and sample_depth.device == coord.device
+                and ray_depth.device == coord.device):
+            raise ValueError("RayPool: the pools must be on one CUDA device")
+        self.samples, self.size, self.device = S, m, coord.device
+        if m > 1:
+            # node order of the rays' first samples; the rays of one node by their source index (canonical_order), so that two
+            # builds of the same pool hold the same order and the same seed gives the same batches
+            perm, slots = plan_batch(self.octree, coord[::S].contiguous(), sort=True)
+            perm = perm[canonical_order(perm, slots)].contiguous()
+        else:
+            perm = torch.arange(m, dtype=torch.int32, device=coord.device)
+        p = perm.long()
+        self.perm = perm
+        self.coord = coord.view(m, S, 3)[p].reshape(m * S, 3).contiguous()
+        self.weight = weight.view(m, S)[p].reshape(m * S).contiguous()
+        self.sample_depth = sample_depth.view(m, S)[p].reshape(m * S).contiguous()
+        self.ray_depth = ray_depth[p].contiguous()
+        self.surf_per_ray = (self.weight.view(m, S) > 0).sum(dim=1).to(torch.int32).contiguous()
+        self.tables_epoch = self.octree._tables_epoch
+        for k in [k for k in self._ws if k[1] != self.size]:
+            del self._ws[k]
+
+    def surf_buffer(self):
+        """int64[1] buffer for draw(n, surf_out=...): the surface-sample count of a batch, where the step reads it (n_surf)"""
+        return torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def draw(self, n, out=None, graph_safe=False, surf_out=None):
+        """n sorted i.i.d. uniform RAY indices (int32, device).  `graph_safe`: the stream id is read from (and advanced in) device
+        memory, so a captured HIP graph of this call draws a fresh batch at every replay.  `surf_out` (surf_buffer()): one more
+        small launch writes the number of the batch's samples with weight > 0 into it — pass it to fused_ray_step as n_surf."""
+        n = int(n)
+        dev = self.device
+        lib = _lib.lib()
+        stream = _lib.current_stream_handle()
+        if self.size < 1:
+            raise ValueError("RayPool.draw: the pool holds no ray")
+        ws = self._ws.get((n, self.size))
+        if ws is None:
+            need = _lib.workspace_bytes(lib.shine_sample_sorted, self.size, n, self.seed, 0, None, None, 0, None, None, _lib.WS,
+                                        _lib.WS_BYTES, stream)
+            ws = self._ws[(n, self.size)] = (_lib.workspace(need, dev), n, need)
+        idx = out if out is not None else torch.empty(n, dtype=torch.int32, device=dev)
+        if not (idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == n):
+            raise ValueError("RayPool.draw: out must be a contiguous CUDA int32 tensor of n entries")
+        if surf_out is not None and not (surf_out.is_cuda and surf_out.dtype == torch.int64 and surf_out.is_contiguous()
+                                         and surf_out.numel() == 1):
+            raise ValueError("RayPool.draw: surf_out must be a CUDA int64 tensor of one element (surf_buffer())")
+        need = C.c_size_t(ws[2])
+        if graph_safe:
+            if self._stream_state is None:
+                self._stream_state = _lib.device_constants([self.draws, 0, self.draws, 0], torch.int64, dev)
+            _lib.check(lib.shine_sample_sorted_dev(self.size, n, self.seed, self._stream_state.data_ptr(), idx.data_ptr(), None, 0,
+                                                   None, None, ws[0].data_ptr(), C.byref(need), stream), "shine_sample_sorted_dev")
+        else:
+            _lib.check(lib.shine_sample_sorted(self.size, n, self.seed, self.draws, idx.data_ptr(), None, 0, None, None,
+                                               ws[0].data_ptr(), C.byref(need), stream), "shine_sample_sorted")
+            self.draws += 1
+        if surf_out is not None:
+            _lib.check(lib.shine_ray_surf_count(idx.data_ptr(), self.surf_per_ray.data_ptr(), n, surf_out.data_ptr(), stream),
+                       "shine_ray_surf_count")
+        return idx
+
+    def get_batch(self, idx):
+        """(coord [n*S,3], sample_depth [n*S], ray_depth [n], weight [n*S]) of a drawn batch, for code that wants the tensors
+        (Tier A / debugging)."""
+        i, S = idx.long(), self.samples
+        return (self.coord.view(-1, S, 3)[i].reshape(-1, 3), self.sample_depth.view(-1, S)[i].reshape(-1), self.ray_depth[i],
+                self.weight.view(-1, S)[i].reshape(-1))
