@@ -93,6 +93,8 @@ __global__ __launch_bounds__(256) void k_finish(const FinArgs a, int fb, int db)
               g[q] += kk * w[q] * d;
             }
           }
+        } else if (tv[k] != 0 && !a.active) {
+          a.touched[s][r] = 0;  // dense: every flag is cleared, "touched earlier" (2) too (include/shine_hip.h)
         }
         const float lr = s_lr[s];
 #pragma unroll
