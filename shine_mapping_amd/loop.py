@@ -16,38 +16,40 @@ replay draws a fresh batch and applies the right bias correction.  Learning-rate
 (`opt.sync_lr()` after changing `param_groups`).  Re-create after `octree.update()` (parameters are re-allocated, like
 the optimiser itself, shine_incre.py:108-109).
 
-With `sem=SemTerm(...)` (semantic_on) the iteration is {fused step, semantic step, tail} on the same batch: the semantic step
-(ops.fused_sem_step, one launch) adds weight_s * d NLL / d {features, head} to the grads the tail's Adam consumes, and while the
-head trains its six tensors get one more graph-safe Adam launch of their own (the tail keeps its feature-table + decoder set).
-With `normal=NormalTerm(...)` (normal_loss_on) the normal step (ops.fused_normal_step, one launch) joins the same way: its
-feature and decoder grads land in the tensors the tail steps, so it needs no Adam launch of its own; with both terms the iteration
-is {fused step, semantic step, normal step, tail, the head's Adam}.
-With `consistency=ConsistencyTerm(...)` (consistency_loss_on) the consistency step (ops.fused_consistency_step, one launch) goes
-after the fused step and the other terms and before the tail: {fused, [sem], [normal], consistency, tail, [head Adam]}.  It draws its
-own K = min(count, n) pairs on the device from a draw state this object owns (advanced by the kernel: a replay draws fresh pairs)
-and flags the rows its shifted points reach, so the active-row Adam steps and clears them.  Not served with the regulariser
-(lambda_forget != 0): the reference then regularises the rows of its LAST query_feature call, coord_near's, an accident of call
-order (shine_incre.py:144,156).
+The routes, chosen by the constructor's arguments (a term or a combination outside this table is refused with a ValueError before
+anything is allocated):
 
-With a TIME-CONDITIONED decoder (config.time_conditioned: Decoder(config, is_time_conditioned=True) in the fusable shape,
-decoder.time_fusable) the iteration takes the time route: {draw, ops.fused_time_step on pool / idx (one launch: BCE [+ eikonal]
-through the 9-wide head and the whole backward), the optimiser's graph-safe step with zero_grad}, captured as a stream graph —
-the non-folded form, `native` off.  The pool carries the time stamps (SortedPool(ts=...)).  Not served on that route yet:
-lambda_forget != 0, sem=, normal=, consistency= (their kernels decode with the plain head).
+    route            launches per iteration                           needs                                    refuses
+    ---------------  -----------------------------------------------  ---------------------------------------  ----------------------
+    plain            fused step, tail — the library-built graph       a SortedPool; FusedAdam for the fold     —
+                     (`native`) while n + 1 <= 16 K; not folded:      (else {step, [regulariser], Adam} as a
+                     step, [regulariser], Adam                        captured stream graph)
+    + sem=           + ops.fused_sem_step after the fused step;       the fold; SortedPool(sem_label=);        —
+      SemTerm        + the head's own Adam launch after the tail      the head's six tensors all trained or
+                     while the head trains                            all frozen
+    + normal=        + ops.fused_normal_step after sem's; its grads   the fold; SortedPool(normal_label=)      —
+      NormalTerm     land in the tensors the tail steps
+    + consistency=   + ops.fused_consistency_step, last before the    the fold                                 lambda_forget != 0 (the
+      Consistency-   tail: it draws K = min(count, n) pairs from a                                             reference regularises
+      Term           draw state this object owns and flags the rows                                            coord_near's rows, an
+                     its shifted points reach for the active-row Adam                                          accident of call order)
+    time             draw, ops.fused_time_step, the optimiser's       a time-conditioned decoder in the        lambda_forget != 0,
+                     graph-safe step with zero_grad (a captured       fusable shape (decoder.time_fusable);    sem=, normal=,
+                     stream graph: not folded, `native` off)          SortedPool(ts=)                          consistency=
+    ray=RayTerm      draw of n RAYS (+ the batch's surface count      a sampler.RayPool; the optimiser of      a time-conditioned
+                     with the eikonal term), ops.fused_ray_step,      setup_optimizer(..., sigma_size) with    decoder, lambda_forget
+                     the optimiser's graph-safe step with zero_grad   config.ray_loss: its step moves          != 0, sem=, normal=,
+                     (as the time route)                              sigma_size too                           consistency=
 
-With `ray=RayTerm(sigma_size, neus_on)` (config.ray_loss, main_loss_type dr / dr_neus) and a sampler.RayPool the iteration takes
-the ray route: {ray_pool.draw of n RAYS (+ the batch's surface count with the eikonal term), ops.fused_ray_step on pool / idx (one
-launch: the head, the per-ray render, [the eikonal term] and the whole backward, sigma_size's gradient included), the optimiser's
-graph-safe step with zero_grad}, captured as a stream graph — the non-folded form, `native` off.  The optimiser is
-setup_optimizer(config, feats, geo_params, None, sigma_size) with config.ray_loss: its step moves sigma_size with the tables and
-the decoder.  Not served on that route: a time-conditioned decoder, lambda_forget != 0, sem=, normal=, consistency=.
+The terms join one iteration in the order {fused, [sem], [normal], [consistency], tail, [head Adam]} on the batch the fused step read.
 """
 import ctypes as C
 from dataclasses import dataclass
+from functools import partial
 
 import torch
 
-from . import _lib
+from . import _lib, autograd_ops
 from .autograd_ops import bump_param_epoch
 from .autograd_ops import CONSISTENCY_WORKSPACE_BYTES, NORMAL_WORKSPACE_BYTES, SEM_WORKSPACE_BYTES
 from .ops import (StepOptions, fused_consistency_step, fused_normal_step, fused_ray_step, fused_regularization, fused_sem_step,
@@ -92,25 +94,6 @@ class RayTerm:
 
     sigma_size: object
     neus_on: bool = False
-
-
-class _IterationTerms(type):
-    """GraphedIteration(..., normal=NormalTerm(...)): loss terms added after `sem` are keyword arguments of the CALL, set on the
-    object before its constructor runs — the constructor's own parameter list is what existing callers (and the suite) spell out
-    position by position, and it stays as it is.
-    A stopgap with known costs: inspect.signature, a subclass that overrides __init__ / __new__ and a direct __init__ call do not
-    see the keyword.  tests/test_sem_step.py::test_public_surface pins the constructor's exact parameter list and a change that adds
-    a loss term may not edit existing tests; a later change should relax that pin to "the leading parameters and their defaults",
-    move `normal` into the constructor and delete this class.  A third term now hangs on the hook: `consistency`
-    (ConsistencyTerm) rides the same way, under the same constraint."""
-
-    def __call__(cls, *args, normal=None, consistency=None, ray=None, **kw):
-        self = cls.__new__(cls)
-        self.normal = normal
-        self.consistency = consistency
-        self.ray = ray  # (the ray route's RayTerm: a fourth keyword on the same hook)
-        self.__init__(*args, **kw)
-        return self
 
 
 _CAPTURE_STREAM = {}
@@ -204,43 +187,32 @@ class IterationGraph:
             pass
 
 
-class GraphedIteration(metaclass=_IterationTerms):
+class GraphedIteration:
     """`eager_first` (default True): the constructor runs iteration 1 eagerly (it allocates the optimiser state and loads the
     kernels outside the capture), so a frame of K iterations is the constructor + run(K - 1).  False: nothing runs in the
     constructor — the optimiser's device state is created explicitly and the graph is captured straight away, so a frame is
     run(K); honoured only once an eager iteration has run on the device in this process (incremental mapping re-creates this
     object every frame: the eager iteration costs ~0.1 ms of launches that a replay does in a third of the time).
-    `normal=NormalTerm(...)` (a keyword of the call, see _IterationTerms): the surface-normal term of the same batch as one more
-    launch between the fused step and the tail (ops.fused_normal_step); `normal_loss` is its 0-dim device tensor.
-    `consistency=ConsistencyTerm(...)` (a keyword of the call too): the gradient-consistency term as the last launch before the
-    tail (ops.fused_consistency_step, pairs drawn on the device); `consistency_loss` is its 0-dim device tensor and
-    `consistency_draws` = (near_index [K], shift [K,3]) holds the last iteration's pairs.  Raises ValueError with
-    lambda_forget != 0.
-    `decoder` time-conditioned (decoder.time_fusable): the time route of the module docstring — `time` is True, `pool` must carry
-    `ts`, and lambda_forget != 0 / sem= / normal= / consistency= raise ValueError before anything is allocated."""
+    `sem`, `normal`, `consistency`, `ray`: the terms and routes of the module docstring's table.  `sem_loss`, `normal_loss` and
+    `consistency_loss` are the terms' 0-dim device tensors (None without the term) and `consistency_draws` = (near_index [K],
+    shift [K,3]) holds the last iteration's pairs; on the time and ray routes (`time` is True / `ray` is the RayTerm) `loss` is the
+    route's step's."""
 
     def __init__(self, octree, decoder, pool, opt, opts: StepOptions, n: int, lambda_forget: float = 0.0, unroll: int = 1,
                  fold: bool = True, eager_first: bool = True, active_rows: bool = True, native: bool = True, graph_slot: int = 0,
-                 sem: SemTerm = None):
+                 sem: SemTerm = None, *, normal: NormalTerm = None, consistency: ConsistencyTerm = None, ray: RayTerm = None):
         self.octree, self.decoder, self.pool, self.opt, self.opts, self.n = octree, decoder, pool, opt, opts, int(n)
         self.lambda_forget = float(lambda_forget)
         self.graph_slot = int(graph_slot)
-        # the ray route (ray=RayTerm(...) and a RayPool): {draw, fused_ray_step, graph-safe Adam} — the non-folded form
-        self.ray = getattr(self, "ray", None)
-        if self.ray is not None or hasattr(pool, "surf_per_ray"):  # (argument errors before anything is allocated)
-            self._check_ray(sem)
-            fold = native = False
-        # the time route (a time-conditioned decoder): {draw, fused_time_step, graph-safe Adam} — the non-folded form
+        self.sem, self.normal, self.consistency, self.ray = sem, normal, consistency, ray
         self.time = bool(getattr(decoder, "time_fusable", False))
-        if self.time:  # (argument errors before anything is allocated)
-            self._check_time(sem)
+        # the single-launch routes (ray, time): {draw, the route's step, graph-safe Adam} — the non-folded form
+        if self.ray is not None or hasattr(pool, "surf_per_ray") or self.time:
             fold = native = False
         self.fold = bool(fold)  # the iteration's tail as one launch (False: reduction, regulariser and Adam as three)
         self.regularize = self.lambda_forget != 0.0
         can_fold = self.fold and hasattr(opt, "finish_iteration") and hasattr(opt, "prepare_graph_safe")
-        self.consistency = getattr(self, "consistency", None)
-        if self.consistency is not None:  # (argument errors before anything is allocated)
-            self._check_consistency(can_fold)
+        self._check_arguments(can_fold)  # (before anything is allocated)
         # EXACT active-row Adam (FusedAdam.finish_iteration(active_flags=...)): rows that have had no gradient since `opt` was
         # created are not read.  Valid for an optimiser that is new (this object creates the flags cleared, so it must be built
         # together with the optimiser, as shine_incre.py:107-109 does every frame) and whose feature groups carry no weight decay
@@ -254,7 +226,6 @@ class GraphedIteration(metaclass=_IterationTerms):
         self._epoch = octree._tables_epoch
         self._idx = torch.empty(self.n, dtype=torch.int32, device=pool.coord.device)
         # the eikonal term's surface count: per-block partial counts written by the draw itself, summed by the step's kernels
-        self.normal = getattr(self, "normal", None)
         # (... and the normal term's: both divide by the batch's surface count)
         if self.ray is not None:
             self._surf = pool.surf_buffer() if opts.ekional_loss_on else None
@@ -268,26 +239,10 @@ class GraphedIteration(metaclass=_IterationTerms):
         # `native`: the graph is BUILT by the library from the two launches of an iteration and re-bound in place for this
         # object's buffers (IterationGraph) instead of being captured from the stream — nothing to warm up, nothing to capture:
         # the constructor runs no iteration whatever `eager_first` says.  Needs the two-launch iteration (fold, the next draw
-        # inside the tail: n < 16 K).
-        self.native = bool(native and can_fold and self.n + 1 <= 16 * 1024)
-        self.sem = sem
-        self.sem_loss = None
-        if sem is not None:
-            self._init_sem(can_fold)
-        self.normal_loss = None
-        if self.normal is not None:
-            self._init_normal(can_fold)
-        self.consistency_loss = self.consistency_draws = None
-        if self.consistency is not None:
-            self._init_consistency(can_fold)
-        if self.time:  # the time step's buffers, made here: a captured graph bakes their addresses in
-            from .autograd_ops import time_step_workspace_bytes
-
-            self._time_ws, self._time_out, self._time_loss = self._term_buffers(time_step_workspace_bytes())
-        if self.ray is not None:  # the ray step's buffers, made here too
-            from .autograd_ops import ray_step_workspace_bytes
-
-            self._ray_ws, self._ray_out, self._ray_loss = self._term_buffers(ray_step_workspace_bytes())
+        # inside the tail: n < 16 K) without a term: the library-built graph holds exactly those two launches.
+        terms = sem is not None or normal is not None or consistency is not None
+        self.native = bool(native and can_fold and self.n + 1 <= 16 * 1024 and not terms)
+        self._init_buffers()
         self.ran_eager = (not self.native) and (bool(eager_first) or dev_key not in _WARMED or not can_fold)
         if can_fold:
             # the optimiser's device-side step state up front: the eager warm-up iteration then runs the SAME two launches the
@@ -328,78 +283,83 @@ class GraphedIteration(metaclass=_IterationTerms):
         out = torch.zeros(1, dtype=torch.float32, device=dev)
         return ws, out, out[0]
 
-    def _init_sem(self, can_fold):
-        """the semantic term's buffers, all made here: a captured graph bakes their addresses in"""
-        sem = self.sem
-        if not can_fold:
-            raise ValueError("GraphedIteration(sem=...) needs the folded iteration (fold=True, a FusedAdam optimiser)")
-        if getattr(self.pool, "sem_label", None) is None:
-            raise ValueError("GraphedIteration(sem=...) needs a SortedPool built with sem_label=")
-        if int(sem.decimation) < 1:
-            raise ValueError("sem_label_decimation must be >= 1")
-        self.native = False  # (the library-built graph holds the two-launch iteration)
-        self._sem_params = list(sem.decoder.sem_params())
-        train = [p.requires_grad for p in self._sem_params]
-        if any(train) != all(train):
-            raise ValueError("the semantic head's six tensors must all train or all be frozen")
-        self._sem_train = all(train)
-        self._sem_ws, self._sem_out, self.sem_loss = self._term_buffers(SEM_WORKSPACE_BYTES)
-
-    def _init_normal(self, can_fold):
-        """the normal term's buffers, all made here: a captured graph bakes their addresses in"""
-        if not can_fold:
-            raise ValueError("GraphedIteration(normal=...) needs the folded iteration (fold=True, a FusedAdam optimiser)")
-        if getattr(self.pool, "normal_label", None) is None:
-            raise ValueError("GraphedIteration(normal=...) needs a SortedPool built with normal_label=")
-        self.native = False  # (the library-built graph holds the two-launch iteration)
-        self._normal_ws, self._normal_out, self.normal_loss = self._term_buffers(NORMAL_WORKSPACE_BYTES)
-
-    def _check_time(self, sem):
-        if getattr(self.pool, "ts", None) is None:
-            raise ValueError("GraphedIteration with a time-conditioned decoder needs a SortedPool built with ts=")
-        if self.lambda_forget != 0.0:
-            raise ValueError("GraphedIteration with a time-conditioned decoder does not serve lambda_forget != 0 yet")
-        for name, term in (("sem", sem), ("normal", getattr(self, "normal", None)),
-                           ("consistency", getattr(self, "consistency", None))):
-            if term is not None:
-                raise ValueError("GraphedIteration with a time-conditioned decoder does not serve %s= yet: its kernel decodes "
-                                 "with the plain head" % name)
-
-    def _check_ray(self, sem):
-        if self.ray is None:
-            raise ValueError("GraphedIteration with a RayPool needs ray=RayTerm(sigma_size, neus_on)")
-        if not hasattr(self.pool, "surf_per_ray"):
-            raise ValueError("GraphedIteration(ray=...) needs a sampler.RayPool (LiDARDataset.ray_pool())")
-        if getattr(self.decoder, "time_fusable", False) or getattr(self.decoder, "is_time_conditioned", False):
-            raise ValueError("GraphedIteration(ray=...) does not serve a time-conditioned decoder: the ray step decodes with the "
-                             "plain head")
-        if self.lambda_forget != 0.0:
-            raise ValueError("GraphedIteration(ray=...) does not serve lambda_forget != 0")
-        for name, term in (("sem", sem), ("normal", getattr(self, "normal", None)),
-                           ("consistency", getattr(self, "consistency", None))):
-            if term is not None:
-                raise ValueError("GraphedIteration(ray=...) does not serve %s=: ray mode combined with the other terms is out of "
-                                 "scope" % name)
-
-    def _check_consistency(self, can_fold):
-        term = self.consistency
-        if not can_fold:
-            raise ValueError("GraphedIteration(consistency=...) needs the folded iteration (fold=True, a FusedAdam optimiser)")
-        if self.regularize:
-            raise ValueError("GraphedIteration(consistency=...) is not served with lambda_forget != 0: the reference regularises "
-                             "the rows of its last query_feature call (coord_near's), an accident of call order")
-        if int(term.count) < 0 or not float(term.shift_scale) >= 0.0:
-            raise ValueError("ConsistencyTerm: count >= 0 and shift_scale >= 0 (consistency_range * scale)")
-
-    def _init_consistency(self, can_fold):
-        """the consistency term's buffers, all made here: a captured graph bakes their addresses in"""
-        term = self.consistency
-        self.native = False  # (the library-built graph holds the two-launch iteration)
+    def _init_buffers(self):
+        """the buffers of the terms and of a single-launch route's step, all made here: a captured graph bakes their addresses in"""
         dev = self.pool.coord.device
-        k = self._consistency_k = min(int(term.count), self.n)
-        self._consistency_ws, self._consistency_out, self.consistency_loss = self._term_buffers(CONSISTENCY_WORKSPACE_BYTES)
-        self._consistency_state = torch.zeros(1, dtype=torch.int64, device=dev)  # the pairs' stream id, advanced by the kernel
-        self.consistency_draws = (torch.zeros(k, dtype=torch.int32, device=dev), torch.zeros((k, 3), dtype=torch.float32, device=dev))
+        self.sem_loss = self.normal_loss = self.consistency_loss = self.consistency_draws = self._route = None
+        if self.sem is not None:
+            head = list(self.sem.decoder.sem_params())
+            self._sem_head = head if head[0].requires_grad else []  # (the tensors of the head's own Adam launch)
+            self._sem_ws, self._sem_out, self.sem_loss = self._term_buffers(SEM_WORKSPACE_BYTES)
+        if self.normal is not None:
+            self._normal_ws, self._normal_out, self.normal_loss = self._term_buffers(NORMAL_WORKSPACE_BYTES)
+        if self.consistency is not None:
+            k = self._consistency_k = min(int(self.consistency.count), self.n)
+            self._consistency_ws, self._consistency_out, self.consistency_loss = self._term_buffers(CONSISTENCY_WORKSPACE_BYTES)
+            self._consistency_state = torch.zeros(1, dtype=torch.int64, device=dev)  # the pairs' stream id, advanced by the kernel
+            self.consistency_draws = (torch.zeros(k, dtype=torch.int32, device=dev), torch.zeros((k, 3), dtype=torch.float32, device=dev))
+        # a single-launch route: (the draw's surface-count keyword, the step but for its idx=, the loss the step writes); `_surf`
+        # exists with the eikonal term only
+        if self.ray is not None or self.time:
+            nbytes = autograd_ops.ray_step_workspace_bytes() if self.ray is not None else autograd_ops.time_step_workspace_bytes()
+            ws, out, loss = self._term_buffers(nbytes)
+            batch = dict(n_surf=self._surf, pool=self.pool, out=out, workspace=ws)
+            if self.ray is not None:
+                self._route = ("surf_out", partial(fused_ray_step, self.octree, self.decoder, None, None, None, None,
+                                                   self.ray.sigma_size, self.opts, None, neus_on=bool(self.ray.neus_on), **batch), loss)
+            else:
+                self._route = ("surf_parts", partial(fused_time_step, self.octree, self.decoder, None, None, None, None, self.opts,
+                                                     **batch), loss)
+
+    def _refuse_terms(self, wording):
+        for name, term in (("sem", self.sem), ("normal", self.normal), ("consistency", self.consistency)):
+            if term is not None:
+                raise ValueError(wording % name)
+
+    def _check_arguments(self, can_fold):
+        """every argument error of the constructor, in the order ray, time, consistency, sem, normal"""
+        pool, sem, term = self.pool, self.sem, self.consistency
+        if self.ray is not None or hasattr(pool, "surf_per_ray"):
+            if self.ray is None:
+                raise ValueError("GraphedIteration with a RayPool needs ray=RayTerm(sigma_size, neus_on)")
+            if not hasattr(pool, "surf_per_ray"):
+                raise ValueError("GraphedIteration(ray=...) needs a sampler.RayPool (LiDARDataset.ray_pool())")
+            if self.time or getattr(self.decoder, "is_time_conditioned", False):
+                raise ValueError("GraphedIteration(ray=...) does not serve a time-conditioned decoder: the ray step decodes with the "
+                                 "plain head")
+            if self.regularize:
+                raise ValueError("GraphedIteration(ray=...) does not serve lambda_forget != 0")
+            self._refuse_terms("GraphedIteration(ray=...) does not serve %s=: ray mode combined with the other terms is out of scope")
+        if self.time:
+            if getattr(pool, "ts", None) is None:
+                raise ValueError("GraphedIteration with a time-conditioned decoder needs a SortedPool built with ts=")
+            if self.regularize:
+                raise ValueError("GraphedIteration with a time-conditioned decoder does not serve lambda_forget != 0 yet")
+            self._refuse_terms("GraphedIteration with a time-conditioned decoder does not serve %s= yet: its kernel decodes with the "
+                               "plain head")
+        if term is not None:
+            if not can_fold:
+                raise ValueError("GraphedIteration(consistency=...) needs the folded iteration (fold=True, a FusedAdam optimiser)")
+            if self.regularize:
+                raise ValueError("GraphedIteration(consistency=...) is not served with lambda_forget != 0: the reference regularises "
+                                 "the rows of its last query_feature call (coord_near's), an accident of call order")
+            if int(term.count) < 0 or not float(term.shift_scale) >= 0.0:
+                raise ValueError("ConsistencyTerm: count >= 0 and shift_scale >= 0 (consistency_range * scale)")
+        if sem is not None:
+            if not can_fold:
+                raise ValueError("GraphedIteration(sem=...) needs the folded iteration (fold=True, a FusedAdam optimiser)")
+            if getattr(pool, "sem_label", None) is None:
+                raise ValueError("GraphedIteration(sem=...) needs a SortedPool built with sem_label=")
+            if int(sem.decimation) < 1:
+                raise ValueError("sem_label_decimation must be >= 1")
+            train = [p.requires_grad for p in sem.decoder.sem_params()]
+            if any(train) != all(train):
+                raise ValueError("the semantic head's six tensors must all train or all be frozen")
+        if self.normal is not None:
+            if not can_fold:
+                raise ValueError("GraphedIteration(normal=...) needs the folded iteration (fold=True, a FusedAdam optimiser)")
+            if getattr(pool, "normal_label", None) is None:
+                raise ValueError("GraphedIteration(normal=...) needs a SortedPool built with normal_label=")
 
     def _graph_1(self):
         if self.graph is None:
@@ -430,29 +390,17 @@ class GraphedIteration(metaclass=_IterationTerms):
             ent = self._native[unroll] = (g, out, keep)
         return ent
 
-    def _time_body(self):
-        """the time route's iteration: draw, the one-launch step on pool / idx, the optimiser's graph-safe step"""
-        idx = self.pool.draw(self.n, out=self._idx, graph_safe=True, surf_parts=self._surf)
-        fused_time_step(self.octree, self.decoder, None, None, None, None, self.opts,
-                        n_surf=self._surf if self.opts.ekional_loss_on else None, pool=self.pool, idx=idx, out=self._time_out,
-                        workspace=self._time_ws)
+    def _route_body(self):
+        """a single-launch route's iteration: draw (n rays on the ray route), the one-launch step on pool / idx, the optimiser's
+        graph-safe step"""
+        count_kw, step, loss = self._route
+        step(idx=self.pool.draw(self.n, out=self._idx, graph_safe=True, **{count_kw: self._surf}))
         self.opt.step(zero_grad=True, graph_safe=True)
-        return self._time_loss, None
-
-    def _ray_body(self):
-        """the ray route's iteration: draw n rays, the one-launch step on pool / idx, the optimiser's graph-safe step"""
-        idx = self.pool.draw(self.n, out=self._idx, graph_safe=True, surf_out=self._surf)
-        fused_ray_step(self.octree, self.decoder, None, None, None, None, self.ray.sigma_size, self.opts, None,
-                       neus_on=bool(self.ray.neus_on), n_surf=self._surf, pool=self.pool, idx=idx, out=self._ray_out,
-                       workspace=self._ray_ws)
-        self.opt.step(zero_grad=True, graph_safe=True)
-        return self._ray_loss, None
+        return loss, None
 
     def _body(self, graph=None, keep=None):
-        if self.ray is not None:
-            return self._ray_body()
-        if self.time:
-            return self._time_body()
+        if self._route is not None:
+            return self._route_body()
         idx = self._idx if self._ahead else self.pool.draw(self.n, out=self._idx, graph_safe=True, surf_parts=self._surf)
         n_surf = self._surf if self.opts.ekional_loss_on else None
         # Iteration hooks: the step's reduction launch also counts the optimiser step (+ bias corrections) and clears the
@@ -478,38 +426,29 @@ class GraphedIteration(metaclass=_IterationTerms):
                                       idx=idx, touched=self.touched, pending=pending, graph=graph)
         if keep is not None:
             keep["pending"] = pending  # (every device buffer the nodes name stays alive with this object)
-        if self.sem is not None or self.normal is not None or self.consistency is not None:
-            return self._terms_tail(idx, fold, pending, loss)
-        if fold:
-            self.opt.finish_iteration(pending, dict(lambda_forget=self.lambda_forget, touched=self.touched,
-                                                    out=self._reg_out) if self.regularize else None,
-                                      next_draw=self.pool.next_draw(self.n, self._idx, self._surf) if self._ahead else None,
-                                      active_flags=self.touched if self.active_rows else None, graph=graph)
-            return loss, (self._reg_out[0] if self.regularize else None)
-        reg = None
-        if self.regularize:
-            reg = fused_regularization(self.octree, self.lambda_forget, self.touched, out=self._reg_out, out_zeroed=hooked)
-        self.opt.step(zero_grad=True, graph_safe=True, advanced=hooked)
-        return loss, reg
-
-    def _terms_tail(self, idx, fold, pending, loss):
-        """semantic_on / normal_loss_on / consistency_loss_on: each term's step on the batch the fused step just read (the fused
-        step's touched flags cover the rows of the first two; the consistency step flags the rows its shifted points add), the tail
-        on the feature tables + decoder — the normal and consistency terms' decoder grads are in the six tensors it steps —, and,
-        while the semantic head trains, the head's own Adam launch"""
+        sem, term = self.sem, self.consistency
         if not fold:
-            raise RuntimeError("GraphedIteration(sem=... / normal=... / consistency=...): the optimiser has no device-side step "
-                               "state")
-        sem, head = self.sem, []
+            if sem is not None or self.normal is not None or term is not None:
+                raise RuntimeError("GraphedIteration(sem=... / normal=... / consistency=...): the optimiser has no device-side step "
+                                   "state")
+            reg = None
+            if self.regularize:
+                reg = fused_regularization(self.octree, self.lambda_forget, self.touched, out=self._reg_out, out_zeroed=hooked)
+            self.opt.step(zero_grad=True, graph_safe=True, advanced=hooked)
+            return loss, reg
+        # semantic_on / normal_loss_on / consistency_loss_on: each term's step on the batch the fused step just read (the fused step's
+        # touched flags cover the rows of the first two; the consistency step flags the rows its shifted points add), the tail on the
+        # feature tables + decoder — the normal and consistency terms' decoder grads are in the six tensors it steps —, and, while
+        # the semantic head trains, the head's own Adam launch
+        head = []
         if sem is not None:
             fused_sem_step(self.octree, sem.decoder, None, None, float(sem.weight_s), int(sem.decimation), pool=self.pool, idx=idx,
                            out=self._sem_out, workspace=self._sem_ws)
-            head = self._sem_params if self._sem_train else []
+            head = self._sem_head
         if self.normal is not None:
             fused_normal_step(self.octree, self.decoder, None, None, None, float(self.normal.weight_n), n_surf=self._surf,
                               pool=self.pool, idx=idx, out=self._normal_out, workspace=self._normal_ws)
-        if self.consistency is not None:  # (last: its flags join the fused step's before the tail reads them)
-            term = self.consistency
+        if term is not None:  # (last: its flags join the fused step's before the tail reads them)
             fused_consistency_step(self.octree, self.decoder, None, float(term.weight_c), n_pairs=self._consistency_k,
                                    shift_scale=float(term.shift_scale), seed=int(term.seed), draw_state=self._consistency_state,
                                    pool=self.pool, idx=idx, touched=self.touched, out=self._consistency_out,
@@ -517,24 +456,14 @@ class GraphedIteration(metaclass=_IterationTerms):
         self.opt.finish_iteration(pending, dict(lambda_forget=self.lambda_forget, touched=self.touched,
                                                 out=self._reg_out) if self.regularize else None,
                                   next_draw=self.pool.next_draw(self.n, self._idx, self._surf) if self._ahead else None,
-                                  active_flags=self.touched if self.active_rows else None, others=head)
+                                  active_flags=self.touched if self.active_rows else None, graph=graph, others=head)
         if head:
             self.opt.step_tensors_dev(head)
         return loss, (self._reg_out[0] if self.regularize else None)
 
     def __call__(self):
         """Run one iteration; returns the loss of the fused terms as a 0-dim device tensor (no host sync)."""
-        if self.octree._tables_epoch != self._epoch:
-            raise RuntimeError("the octree grew since this iteration was captured: build a new GraphedIteration")
-        bump_param_epoch()
-        if self.native:
-            g, out, _ = self._bound(1)
-            g.launch(1)
-            self.loss, self.reg = out
-            return self.loss
-        self._graph_1().replay()
-        self.loss, self.reg = self._out_1
-        return self.loss
+        return self.run(1)
 
     def run(self, n_iters: int):
         """n_iters iterations: replays of the `unroll`-iteration graph, the remainder one by one.  Returns the last loss."""

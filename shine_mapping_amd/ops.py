@@ -189,19 +189,15 @@ def _fused_launch(octree, decoder, coord, sdf_label, weight, opts: StepOptions, 
         weight = _f32(weight, "weight")
     if opts.loss_reduction not in ("mean", "sum"):
         raise ValueError("loss_reduction must be 'mean' or 'sum'")
-    n_global = int(opts.n_global) if opts.n_global else n
     params = decoder.fused_params()
     if dec_grad is None:
         dec_grad = opts.decoder_grad_on
     if dec_grad is None:
         dec_grad = any(p.requires_grad for p in params)
     cfg = octree.step_config(
-        sigma=float(opts.sigma), weight_e=float(opts.weight_e), eikonal_on=1 if eik else 0,
-        reduction_sum=1 if opts.loss_reduction == "sum" else 0, decoder_grad_on=1 if dec_grad else 0,
-        sorted_input=(3 if rec_mode else 2) if pool_mode else (0 if perm is None else 1), n_global=n_global,
+        decoder_grad_on=1 if dec_grad else 0, sorted_input=(3 if rec_mode else 2) if pool_mode else (0 if perm is None else 1),
         kernel_variant=int(opts.kernel_variant) | (0x4000 if getattr(opts, "deterministic", False) else 0),
-        loss_weight_on=1 if opts.loss_weight_on else 0,
-        inv_n=(1.0 if opts.loss_reduction == "sum" else 1.0 / max(n_global, 1)),
+        loss_weight_on=1 if opts.loss_weight_on else 0, **_loss_scalars(opts, n),
     )
     if opts.adam_state is not None:
         cfg.adam_state = opts.adam_state.data_ptr()
@@ -277,11 +273,52 @@ def _fused_launch(octree, decoder, coord, sdf_label, weight, opts: StepOptions, 
     return loss_parts[3], pred, gx  # 0-dim float64 view: BCE (+ weight_e * eikonal), no extra launch
 
 
-# ---- the term steps (fused_sem_step, fused_normal_step, fused_consistency_step) share their host side: where
-# the batch is read from, where the gradients go, the loss's tensor, and the call.  A step keeps its term's own checks and its
-# argument list.
+# ---- the five steps beside the fused one (fused_sem_step, fused_normal_step, fused_consistency_step, fused_time_step,
+# fused_ray_step) share their host side: where the batch and its weights are read from, the surface count, the
+# loss's scalars, where the gradients go, the loss's tensor, and the call.  A step keeps its own checks and its argument list.
 def _i32c(x):
     return isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.int32 and x.is_contiguous()
+
+
+def _loss_scalars(opts, n=None):
+    """the loss's scalars of step_config; with `n`, the batch's rows, also those of a loss that is a mean over rows or a sum"""
+    kw = dict(sigma=float(opts.sigma), weight_e=float(opts.weight_e), eikonal_on=1 if opts.ekional_loss_on else 0)
+    if n is not None:
+        n_global = int(opts.n_global) if opts.n_global else n
+        total = opts.loss_reduction == "sum"
+        kw.update(reduction_sum=1 if total else 0, n_global=n_global, inv_n=1.0 if total else 1.0 / max(n_global, 1))
+    return kw
+
+
+def _term_weights(pool, stride, weight, rows_n):
+    """(ptr, stride in floats, the tensor to keep alive) of the batch's sample weights: the pool's SoA array, word 4 of its 32-byte
+    records or its separate array (4-level trees); array mode: weight [rows_n] float32"""
+    if pool is None:
+        keep = _f32(weight, "weight")
+        if keep.dim() != 1 or keep.numel() != rows_n:
+            raise ValueError("weight must hold one value per coordinate")
+    elif stride == 3:
+        keep = pool.soa()[2]
+    elif pool._weight_sep is None:
+        return pool.rec.data_ptr() + 16, 8, pool.rec
+    else:
+        keep = pool._weight_sep
+    return keep.data_ptr(), 1, keep
+
+
+def _n_surf(n_surf, w=None, idx=None, max_parts=None, parts="the draw's partial counts"):
+    """the surface count a step divides by, checked: one count or up to `max_parts` partial counts.  Without `w` only its type (the
+    check that comes ahead of the batch's own); with `w`, the weights the batch reads through idx, everything, and the default:
+    the rows with weight > 0, counted on the device"""
+    ok = n_surf is None or isinstance(n_surf, torch.Tensor)
+    if ok and w is not None:
+        if n_surf is None:
+            n_surf = ((w[idx.long()] if idx is not None else w) > 0).sum()
+        ok = (n_surf.is_cuda and n_surf.dtype == torch.int64 and n_surf.is_contiguous()
+              and 1 <= n_surf.numel() <= (max_parts or n_surf.numel()))
+    if not ok:
+        raise ValueError("n_surf must be a contiguous CUDA int64 tensor (one count, or %s)" % parts)
+    return n_surf
 
 
 def _check_pool_idx(octree, pool, idx):
@@ -390,7 +427,6 @@ def fused_sem_step(octree, sem_decoder, coord, sem_label, weight_s, decimation=1
     return out.view(())
 
 
-
 def fused_normal_step(octree, decoder, coord, weight, normal_label, weight_n, n_surf=None, pool=None, idx=None,
                       grad_buffers=None, out=None, workspace=None):
     """The surface-normal term of one training iteration (shine_batch.py:192-197) in ONE launch (shine_normal_train_step):
@@ -416,37 +452,18 @@ def fused_normal_step(octree, decoder, coord, weight, normal_label, weight_n, n_
     autograd_ops.normal_workspace)."""
     t = octree._require_tables()  # (the kernel probes the hash tables from the coordinates)
     mlp = decoder.fused_params()
-    if n_surf is not None and not isinstance(n_surf, torch.Tensor):
-        raise ValueError("n_surf must be a contiguous CUDA int64 tensor (one count, or the draw's partial counts)")
+    _n_surf(n_surf)
     if pool is None and not all(isinstance(x, torch.Tensor) for x in (coord, weight, normal_label)):
         raise ValueError("array mode needs coord [N,3], weight [N] and normal_label [N,3] (or pool= and idx=)")
     src, stride, n, dev = _term_batch(octree, coord, pool, idx, pool_needs="normal_label")
-    if pool is not None:
-        normal = pool.normal_label
-        if stride == 3:
-            w_keep, w_stride = pool.soa()[2], 1
-            w_ptr = w_keep.data_ptr()
-        elif pool._weight_sep is None:  # word 4 of the 32-byte records
-            w_ptr, w_stride, w_keep = pool.rec.data_ptr() + 16, 8, pool.rec
-        else:
-            w_ptr, w_stride, w_keep = pool._weight_sep.data_ptr(), 1, pool._weight_sep
-        if n_surf is None:
-            n_surf = (pool.weight[idx.long()] > 0).sum()
-    else:
-        normal = normal_label
-        w_keep = _f32(weight, "weight")
-        w_ptr, w_stride = w_keep.data_ptr(), 1
-        if w_keep.dim() != 1 or w_keep.numel() != src.shape[0]:
-            raise ValueError("weight must hold one value per coordinate")
-        if n_surf is None:
-            n_surf = ((w_keep[idx.long()] if idx is not None else w_keep) > 0).sum()
+    normal = pool.normal_label if pool is not None else normal_label
+    w_ptr, w_stride, w_keep = _term_weights(pool, stride, weight, src.shape[0])
     if not (isinstance(normal, torch.Tensor) and normal.is_cuda and normal.dtype == torch.float32 and normal.is_contiguous()
             and normal.dim() == 2 and normal.shape[1] == 3):
         raise ValueError("normal_label must be a contiguous CUDA float32 [N,3] tensor")
     if pool is None and normal.shape[0] != src.shape[0]:
         raise ValueError("normal_label must hold one normal per coordinate")
-    if not (n_surf.is_cuda and n_surf.dtype == torch.int64 and n_surf.is_contiguous() and n_surf.numel() >= 1):
-        raise ValueError("n_surf must be a contiguous CUDA int64 tensor (one count, or the draw's partial counts)")
+    n_surf = _n_surf(n_surf, pool.weight if pool is not None else w_keep, idx)
     if not decoder._params_on(dev, mlp):
         raise ValueError("the decoder's parameters must be CUDA float32 contiguous on the batch's device")
     gfeat, gmlp = _term_targets(octree, mlp, grad_buffers, "the decoder's")
@@ -458,7 +475,6 @@ def fused_normal_step(octree, decoder, coord, weight, normal_label, weight_n, n_
                int(n_surf.numel()), n, float(weight_n), *_term_ptrs(octree, mlp, gfeat, gmlp), out.data_ptr(), ws.data_ptr())
     del w_keep  # (the weights outlive the call)
     return out.view(())
-
 
 
 def fused_consistency_step(octree, decoder, coord, weight_c, near_index=None, shift=None, n_pairs=None, shift_scale=None, seed=0,
@@ -548,7 +564,6 @@ def fused_consistency_step(octree, decoder, coord, weight_c, near_index=None, sh
     return out.view(())
 
 
-
 def fused_time_step(octree, decoder, coord, sdf_label, weight, ts, opts: StepOptions, n_surf=None, pool=None, idx=None,
                     grad_buffers=None, out=None, workspace=None, pred_out=None):
     """One training iteration's forward + backward of a TIME-CONDITIONED map (config.time_conditioned; shine_batch.py:119-130,
@@ -583,43 +598,26 @@ def fused_time_step(octree, decoder, coord, sdf_label, weight, ts, opts: StepOpt
     if opts.loss_reduction not in ("mean", "sum"):
         raise ValueError("loss_reduction must be 'mean' or 'sum'")
     eik = bool(opts.ekional_loss_on)
-    if n_surf is not None and not isinstance(n_surf, torch.Tensor):
-        raise ValueError("n_surf must be a contiguous CUDA int64 tensor (one count, or the draw's partial counts)")
+    _n_surf(n_surf)
     if pool is None and not all(isinstance(x, torch.Tensor) for x in (coord, sdf_label, ts) + ((weight,) if eik else ())):
         raise ValueError("array mode needs coord [N,3], sdf_label [N], ts [N] and, with the eikonal term, weight [N] (or pool= and "
                          "idx=)")
     src, stride, n, dev = _term_batch(octree, coord, pool, idx, pool_needs="ts")
-    label = w_keep = None
-    w_ptr, w_stride = None, 1
     if pool is not None:
-        ts_arr = pool.ts
-        if stride == 3:
-            label, w_keep = pool.soa()[1], pool.soa()[2]
-            w_ptr = w_keep.data_ptr()
-        elif pool._weight_sep is None:  # word 4 of the 32-byte records
-            w_ptr, w_stride, w_keep = pool.rec.data_ptr() + 16, 8, pool.rec
-        else:
-            w_ptr, w_keep = pool._weight_sep.data_ptr(), pool._weight_sep
-        if eik and n_surf is None:
-            n_surf = (pool.weight[idx.long()] > 0).sum()
+        ts_arr, label = pool.ts, (pool.soa()[1] if stride == 3 else None)  # (the records carry their labels)
     else:
-        rows_n = int(src.shape[0])
-        label = _f32(sdf_label, "sdf_label")
-        ts_arr = ts
-        if label.dim() != 1 or label.numel() != rows_n:
+        ts_arr, label = ts, _f32(sdf_label, "sdf_label")
+        if label.dim() != 1 or label.numel() != int(src.shape[0]):
             raise ValueError("sdf_label must hold one value per coordinate")
-        if eik:
-            w_keep = _f32(weight, "weight")
-            if w_keep.dim() != 1 or w_keep.numel() != rows_n:
-                raise ValueError("weight must hold one value per coordinate")
-            w_ptr = w_keep.data_ptr()
-            if n_surf is None:
-                n_surf = ((w_keep[idx.long()] if idx is not None else w_keep) > 0).sum()
+    # (array mode reads the weights with the eikonal term only: they may be None without it)
+    w_ptr, w_stride, w_keep = None, 1, None
+    if pool is not None or eik:
+        w_ptr, w_stride, w_keep = _term_weights(pool, stride, weight, int(src.shape[0]))
     if not (isinstance(ts_arr, torch.Tensor) and ts_arr.is_cuda and ts_arr.dtype == torch.float32 and ts_arr.is_contiguous()
             and ts_arr.numel() == (pool.size if pool is not None else int(src.shape[0]))):
         raise ValueError("ts must be a contiguous CUDA float32 tensor, one time stamp per coordinate")
-    if eik and not (n_surf.is_cuda and n_surf.dtype == torch.int64 and n_surf.is_contiguous() and 1 <= n_surf.numel() <= 64):
-        raise ValueError("n_surf must be a contiguous CUDA int64 tensor (one count, or the draw's partial counts)")
+    if eik:
+        n_surf = _n_surf(n_surf, pool.weight if pool is not None else w_keep, idx, max_parts=64)
     if pred_out is not None and not (isinstance(pred_out, torch.Tensor) and pred_out.is_cuda and pred_out.dtype == torch.float32
                                      and pred_out.is_contiguous() and pred_out.numel() == n):
         raise ValueError("pred_out must be a contiguous CUDA float32 tensor of N elements")
@@ -628,10 +626,7 @@ def fused_time_step(octree, decoder, coord, sdf_label, weight, ts, opts: StepOpt
     gfeat, gmlp = _term_targets(octree, mlp, grad_buffers, "the decoder's")
     out = _term_out(out, dev)
     ws = workspace if workspace is not None else autograd_ops.time_step_workspace(dev)
-    n_global = int(opts.n_global) if opts.n_global else n
-    cfg = octree.step_config(sigma=float(opts.sigma), weight_e=float(opts.weight_e), eikonal_on=1 if eik else 0,
-                             reduction_sum=1 if opts.loss_reduction == "sum" else 0, n_global=n_global,
-                             inv_n=(1.0 if opts.loss_reduction == "sum" else 1.0 / max(n_global, 1)))
+    cfg = octree.step_config(**_loss_scalars(opts, n))
     ws_bytes = C.c_size_t(int(ws.numel()) * int(ws.element_size()))
     _term_call("shine_time_step", octree, t.handle, C.byref(cfg), src.data_ptr(), stride,
                idx.data_ptr() if idx is not None else None, label.data_ptr() if label is not None else None,
@@ -684,8 +679,7 @@ def fused_ray_step(octree, decoder, coord, weight, sample_depth, ray_depth, sigm
         raise NotImplementedError("fused_ray_step needs the plain geometry head 8 -> 32 -> 32 -> 1 (not a time-conditioned decoder)")
     mlp = decoder.fused_params()
     eik = bool(opts.ekional_loss_on)
-    if n_surf is not None and not isinstance(n_surf, torch.Tensor):
-        raise ValueError("n_surf must be a contiguous CUDA int64 tensor (one count, or partial counts)")
+    _n_surf(n_surf, parts="partial counts")
     if pool is not None:
         _check_pool_idx(octree, pool, idx)
         if not hasattr(pool, "surf_per_ray"):
@@ -712,11 +706,7 @@ def fused_ray_step(octree, decoder, coord, weight, sample_depth, ray_depth, sigm
     _f32_n(sigma_size, 1, "sigma_size")
     n = int(idx.numel()) if idx is not None else m
     if eik:
-        if n_surf is None:
-            w2 = weight.view(m, S)
-            n_surf = ((w2[idx.long()] if idx is not None else w2) > 0).sum()
-        if not (n_surf.is_cuda and n_surf.dtype == torch.int64 and n_surf.is_contiguous() and 1 <= n_surf.numel() <= 64):
-            raise ValueError("n_surf must be a contiguous CUDA int64 tensor (one count, or partial counts)")
+        n_surf = _n_surf(n_surf, weight.view(m, S), idx, max_parts=64, parts="partial counts")
     for name, o in (("pred_out", pred_out), ("dpred_out", dpred_out)):
         if o is not None:
             _f32_n(o, n * S, name)
@@ -729,7 +719,7 @@ def fused_ray_step(octree, decoder, coord, weight, sample_depth, ray_depth, sigm
         sigma_grad = _dense_grad(sigma_size)
     out = _term_out(out, dev)
     ws = workspace if workspace is not None else autograd_ops.ray_step_workspace(dev)
-    cfg = octree.step_config(sigma=float(opts.sigma), weight_e=float(opts.weight_e), eikonal_on=1 if eik else 0)
+    cfg = octree.step_config(**_loss_scalars(opts))
     ws_bytes = C.c_size_t(int(ws.numel()) * int(ws.element_size()))
     _term_call("shine_ray_step", octree, t.handle, C.byref(cfg), src.data_ptr(), idx.data_ptr() if idx is not None else None,
                weight.data_ptr() if eik else None, sample_depth.data_ptr(), ray_depth.data_ptr(), sigma_size.data_ptr(), S,

@@ -199,7 +199,9 @@ def test_public_surface_and_the_loop_s_argument_errors():
     term = loop.ConsistencyTerm()
     assert (term.weight_c, term.count, term.seed) == (1.0, 1000, 0) and term.shift_scale > 0
     assert loop.ConsistencyTerm(0.5, 10, 0.01, 3) == loop.ConsistencyTerm(weight_c=0.5, count=10, shift_scale=0.01, seed=3)
-    assert "third term" in loop._IterationTerms.__doc__
+    assert not hasattr(loop, "_IterationTerms")
+    p = inspect.signature(loop.GraphedIteration).parameters["consistency"]
+    assert p.kind is inspect.Parameter.KEYWORD_ONLY and p.default is None
 
     class Opt:  # has the folded iteration's hooks; nothing is called before the argument checks
         param_groups = []

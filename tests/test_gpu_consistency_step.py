@@ -613,6 +613,83 @@ def test_normal_and_consistency_terms_together(workload, loop_start):
     _loop_parts(wl, start)
 
 
+def test_all_three_terms_in_one_iteration(workload, loop_start):
+    """{fused, sem, normal, consistency, tail, the head's Adam}: the recorded launches in that order, then losses and parameters
+    against the eager replay of the loop's own batches and pairs"""
+    from shine_mapping_amd import StepOptions, _lib, autograd_ops, ops
+    from shine_mapping_amd.loop import GraphedIteration, NormalTerm, SemTerm
+    from shine_mapping_amd.sampler import SortedPool
+    from test_gpu_normal_step import _composite as normal_composite, _safe_labels
+    from test_gpu_sem_step import C_LOOP, WEIGHT_S, _head, _labels, _make_opt as sem_opt
+
+    wl, d, iters = workload, 3, 6
+    _loop_parts(wl, loop_start)
+    sem = _head(C_LOOP, seed=4)
+    params = list(wl.octree.hier_features) + list(wl.decoder.parameters()) + list(sem.parameters())
+    start = [p.detach().clone() for p in params]
+    pl = wl.pool
+    _, gpool = normal_composite(wl.octree, wl.decoder, pl.coord.contiguous(), pl.weight.contiguous(), torch.zeros_like(pl.coord))
+    cfg = copy.copy(wl.cfg)
+    cfg.lr, cfg.adam_eps, cfg.opt_adam, cfg.semantic_on, cfg.ray_loss, cfg.lr_level_reduce_ratio = 0.01, 1e-15, True, True, False, 1.0
+    pool = SortedPool(wl.octree, pl.coord, pl.sdf_label, pl.weight, seed=11, canonical=True, normal_label=_safe_labels(gpool, pl.weight, 31),
+                      sem_label=_labels(pl.coord, pl.weight, C_LOOP), n_class=C_LOOP)
+    opts = StepOptions(sigma=cfg.sigma_sigmoid)
+    g = GraphedIteration(wl.octree, wl.decoder, pool, sem_opt(cfg, wl, sem, True), opts, N, eager_first=False,
+                         sem=SemTerm(sem, WEIGHT_S, d), normal=NormalTerm(0.05), consistency=_term(wl))
+    assert not g.ran_eager and not g.native and g.active_rows
+    lib, extra = _lib.lib(), ("shine_normal_train_step", "shine_consistency_train_step")  # (beside counted_launches()' own)
+    saved = {name: getattr(lib, name) for name in extra}
+    batches, draws, hip = [], [], []
+    leftover = torch.zeros((), dtype=torch.int64, device="cuda")
+    for it in range(iters):
+        batches.append(g._idx.clone())
+        with counted_launches() as calls:
+            try:
+                for name, fn in saved.items():
+                    setattr(lib, name, lambda *a, _fn=fn, _name=name: (calls.append((_name, a)), _fn(*a))[1])
+                out = g()
+            finally:
+                for name, fn in saved.items():
+                    setattr(lib, name, fn)
+        names = [c[0] for c in calls]  # this object's first call records the iteration; a replay goes through no entry point
+        assert names == (["shine_train_step", "shine_sem_train_step", "shine_normal_train_step", "shine_consistency_train_step",
+                          "shine_finish_iteration", "shine_adam_step_dev"] if it == 0 else []), names
+        draws.append((g.consistency_draws[0].clone(), g.consistency_draws[1].clone()))
+        hip.append([x.clone() for x in (out, g.sem_loss, g.normal_loss, g.consistency_loss)])
+        for p in wl.octree.hier_features:
+            leftover += p.grad.ne(0).sum()
+    torch.cuda.synchronize()
+    assert int(leftover) == 0 and int(g._consistency_state) == iters
+    hip = [[float(x) for x in row] for row in hip]
+    hip_params = [p.detach().clone() for p in params]
+
+    with torch.no_grad():
+        for p, s in zip(params, start):
+            p.copy_(s)
+            p.grad = None
+    autograd_ops.bump_param_epoch()
+    opt = sem_opt(cfg, wl, sem, False)
+    ref = []
+    for idx, (near, shift) in zip(batches, draws):
+        coord, sdf_label, weight = pool.get_batch(idx)
+        coord, i = coord.contiguous(), idx.long()
+        opt.zero_grad(set_to_none=True)
+        loss, _, _ = ops.fused_train_step(wl.octree, wl.decoder, coord, sdf_label, weight, opts)
+        sem_loss = ops.fused_sem_step(wl.octree, sem, coord, pool.sem_label[i].contiguous(), WEIGHT_S, d)
+        normal_loss = ops.fused_normal_step(wl.octree, wl.decoder, coord, weight, pool.normal_label[i].contiguous(), 0.05)
+        cons = ops.fused_consistency_step(wl.octree, wl.decoder, coord, W_LOOP, near, shift)
+        ref.append([float(x) for x in (loss, sem_loss, normal_loss, cons)])
+        opt.step()
+    torch.cuda.synchronize()
+    worst = max(abs(a - b) / max(abs(b), 1e-12) for ra, rb in zip(hip, ref) for a, b in zip(ra, rb))
+    errs = [rel_err(a, b) for a, b in zip(hip_params, params)]
+    print("sem + normal + consistency: worst loss %.2e" % worst, "params", " ".join("%.1e" % e for e in errs))
+    print("fused / sem / normal / consistency losses, first and last:", hip[0], hip[-1])
+    assert all(x > 0 for x in hip[0]) and worst <= LOOP_TOL["loss"], worst
+    assert max(errs) <= LOOP_TOL["params"], errs
+    _loop_parts(wl, loop_start)
+
+
 def test_without_consistency_the_iteration_is_the_two_launch_native_graph(workload):
     from shine_mapping_amd import StepOptions, optim
     from shine_mapping_amd.loop import GraphedIteration

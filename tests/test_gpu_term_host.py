@@ -4,7 +4,9 @@ Table-driven over the three terms on one golden fixture's tree and decoder: a ba
 lane) and 33 pairs (one full 32-pair tile plus one).
 
 1. one resolver: array mode, array + idx gather and pool mode read the same rows in the same order — one library call each, with
-   the source, stride, idx and n expected, and the same loss to the bit; malformed inputs are refused alike by all three.
+   the source, stride, idx and n expected (and the weights' address and stride, where the step reads them), and the same loss to
+   the bit; malformed inputs are refused alike by all.  The time step (ops.fused_time_step, with the eikonal term) resolves its
+   batch and its weights through the same helpers and is a fourth row of this part's table.
 2. one prologue: a valid argument tuple with exactly one argument spoiled comes back SHINE_E_INVALID with the entry point's text
    for that defect, before anything is launched: the loss and the workspace are untouched (the workspace zero where its
    contract says so) and the valid call gives the same bits afterwards."""
@@ -30,7 +32,10 @@ TERMS = {
     "normal": dict(entry="shine_normal_train_step", n=10, feats=12, mlp=15, grad_mlp=16),
     "consistency": dict(entry="shine_consistency_train_step", n=5, feats=15, mlp=18, grad_mlp=19),
 }
-CFG, SRC, STRIDE, IDX = 1, 2, 3, 4  # the same places in all three
+# part 1 alone: the time step ends differently (a size argument follows its workspace), and its own suite covers its refusals
+RESOLVED = dict(TERMS, time=dict(entry="shine_time_step", n=11, weight=6))
+RESOLVED["normal"] = dict(TERMS["normal"], weight=5)  # (`weight`: the weights' address; their stride follows it)
+CFG, SRC, STRIDE, IDX = 1, 2, 3, 4  # the same places in all of them
 LOSS, WS = -3, -2                   # ... as are the last three: loss_out, workspace, stream
 
 
@@ -53,24 +58,31 @@ class Setup:
     draw of N rows, and the same rows as arrays"""
 
     def __init__(self):
-        from shine_mapping_amd import Decoder
+        from shine_mapping_amd import Decoder, autograd_ops
         from shine_mapping_amd.sampler import SortedPool
 
         fx = load_golden(FIXTURE)
         self.cfg, self.octree, self.dec = product_from_golden(fx)
         torch.manual_seed(1)
         self.sem = Decoder(sem_config("cuda", CLASSES - 1), is_geo_encoder=False)
+        self.timed = Decoder(self.cfg, is_time_conditioned=True).cuda()
+        with torch.no_grad():
+            self.timed.layers[0].weight[:, 8] *= 0.03  # (frame ids: the time column's share stays of the first bias's order)
+        assert self.timed.time_fusable
+        autograd_ops.time_step_workspace_bytes()  # (asked once, through the entry point: not among the calls counted below)
         coord, weight = fx["coord"].cuda(), fx["weight"].cuda()
         gen = torch.Generator(device="cuda").manual_seed(5)
         lab = torch.randint(0, CLASSES, (coord.shape[0],), generator=gen, device="cuda")
         nrm = torch.randn(coord.shape, generator=gen, device="cuda")
         nrm = (nrm / nrm.norm(dim=-1, keepdim=True)).contiguous()
+        frame = torch.randint(0, 4, (coord.shape[0],), generator=gen, device="cuda")
         self.pool = pool = SortedPool(self.octree, coord, fx["sdf_label"].cuda(), weight, seed=3, sem_label=lab, n_class=CLASSES,
-                                      normal_label=nrm)
+                                      normal_label=nrm, ts=frame)
         self.idx = idx = pool.draw(N)
         assert idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == N
         i = idx.long()
-        self.all = dict(coord=pool.soa()[0], weight=pool.soa()[2], label=pool.sem_label, normal=pool.normal_label)
+        self.all = dict(coord=pool.soa()[0], weight=pool.soa()[2], label=pool.sem_label, normal=pool.normal_label,
+                        sdf=pool.soa()[1], ts=pool.ts)
         self.rows = {k: v[i].contiguous() for k, v in self.all.items()}
         assert int((self.rows["weight"] > 0).sum()) > 0
         self.near = torch.randint(0, N, (K,), generator=gen, device="cuda").to(torch.int32)
@@ -78,15 +90,16 @@ class Setup:
         self.shift = ((torch.rand(K, 3, generator=gen, device="cuda") * 2 - 1) * (0.5 * cell)).contiguous()
 
     def clear(self):
-        for p in list(self.octree.hier_features) + list(self.dec.parameters()) + list(self.sem.parameters()):
+        for p in (list(self.octree.hier_features) + list(self.dec.parameters()) + list(self.sem.parameters())
+                  + list(self.timed.parameters())):
             p.grad = None
 
-    def decoder(self, term):
-        return self.sem if term == "sem" else self.dec
+    def mlp(self, term):
+        return self.sem.sem_params() if term == "sem" else self.timed.time_params() if term == "time" else self.dec.fused_params()
 
     def step(self, term, mode="array", **kw):
         """one term step reading the N rows in `mode`: "array" (the rows), "gather" (the pool's arrays through idx), "pool\""""
-        from shine_mapping_amd import ops
+        from shine_mapping_amd import StepOptions, ops
 
         src = dict(array=self.rows, gather=self.all, pool=dict.fromkeys(self.all))[mode]
         if mode == "gather":
@@ -99,6 +112,9 @@ class Setup:
             loss = ops.fused_sem_step(self.octree, self.sem, src["coord"], src["label"], 0.7, 1, **kw)
         elif term == "normal":
             loss = ops.fused_normal_step(self.octree, self.dec, src["coord"], src["weight"], src["normal"], 0.05, **kw)
+        elif term == "time":
+            opts = StepOptions(sigma=float(self.cfg.sigma_sigmoid), ekional_loss_on=True, weight_e=0.1)
+            loss = ops.fused_time_step(self.octree, self.timed, src["coord"], src["sdf"], src["weight"], src["ts"], opts, **kw)
         else:
             loss = ops.fused_consistency_step(self.octree, self.dec, src["coord"], 0.1, near_index=self.near, shift=self.shift, **kw)
         out = loss.clone()
@@ -112,12 +128,19 @@ def setup():
 
 
 # ---- 1. one resolver
-@pytest.mark.parametrize("term", list(TERMS))
+@pytest.mark.parametrize("term", list(RESOLVED))
 def test_one_resolver(setup, term):
-    s, at = setup, TERMS[term]
+    s, at = setup, RESOLVED[term]
     pool, idx = s.pool, s.idx
     pool_src = (pool.rec, 8) if pool.rec is not None else (pool.soa()[0], 3)
     want = dict(array=(s.rows["coord"], 3, None), gather=(s.all["coord"], 3, idx), pool=pool_src + (idx,))
+    if pool.rec is None:
+        pool_weight = (pool.soa()[2].data_ptr(), 1)
+    elif pool._weight_sep is None:  # word 4 of the 32-byte records
+        pool_weight = (pool.rec.data_ptr() + 16, 8)
+    else:
+        pool_weight = (pool._weight_sep.data_ptr(), 1)
+    weights = dict(array=(s.rows["weight"].data_ptr(), 1), gather=(s.all["weight"].data_ptr(), 1), pool=pool_weight)
     losses = {}
     for mode, (src, stride, ix) in want.items():
         with calls_of(at["entry"]) as (seen, _):
@@ -126,6 +149,8 @@ def test_one_resolver(setup, term):
         a = seen[0]
         assert a[SRC] == src.data_ptr() and a[STRIDE] == stride and a[at["n"]] == N, (term, mode)
         assert a[IDX] == (ix.data_ptr() if ix is not None else None), (term, mode)
+        if "weight" in at:
+            assert (a[at["weight"]], a[at["weight"] + 1]) == weights[mode], (term, mode)
     print(term, {m: float(v) for m, v in losses.items()})
     assert bool(torch.isfinite(losses["array"])) and float(losses["array"]) > 0
     assert torch.equal(losses["gather"], losses["array"]) and torch.equal(losses["pool"], losses["array"]), (term, losses)
@@ -144,7 +169,7 @@ def test_one_resolver(setup, term):
         for mode, kw, exc, text in bad:
             with pytest.raises(exc, match=text):
                 s.step(term, mode, **kw)
-        mixed = s.decoder(term).sem_params()[2] if term == "sem" else s.dec.fused_params()[2]
+        mixed = s.mlp(term)[2]
         mixed.requires_grad_(False)
         try:
             with pytest.raises(ValueError, match="six tensors must all require grad or all be frozen"):

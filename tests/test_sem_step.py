@@ -73,11 +73,14 @@ def test_public_surface():
     assert list(sig.parameters)[:10] == ["octree", "sem_decoder", "coord", "sem_label", "weight_s", "decimation", "pool", "idx",
                                           "grad_buffers", "out"]
     assert sig.parameters["decimation"].default == 1
-    # the non-semantic loop keeps its arguments and their defaults; `sem` is new, last and off
+    # the non-semantic loop keeps its arguments and their defaults; the terms follow, off, the later three by keyword only
     g = inspect.signature(loop.GraphedIteration.__init__).parameters
     assert list(g) == ["self", "octree", "decoder", "pool", "opt", "opts", "n", "lambda_forget", "unroll", "fold", "eager_first",
-                       "active_rows", "native", "graph_slot", "sem"]
-    assert g["sem"].default is None and g["native"].default is True and g["fold"].default is True
+                       "active_rows", "native", "graph_slot", "sem", "normal", "consistency", "ray"]
+    assert all(g[k].default is None for k in ("sem", "normal", "consistency", "ray"))
+    assert all(g[k].kind is inspect.Parameter.KEYWORD_ONLY for k in ("normal", "consistency", "ray"))
+    assert all(g[k].kind is inspect.Parameter.POSITIONAL_OR_KEYWORD for k in list(g)[:15])
+    assert g["native"].default is True and g["fold"].default is True
     term = loop.SemTerm(decoder=object())
     assert term.weight_s == 1.0 and term.decimation == 1
     for fn in (sampler.SortedPool.__init__, sampler.SortedPool.rebuild):
