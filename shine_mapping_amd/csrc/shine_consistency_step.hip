@@ -191,7 +191,7 @@ extern "C" int shine_consistency_train_step(const shine_tables* t, const shine_s
   a.weight_c = weight_c;
   a.loss_out = consistency_loss_out;
   a.ws = (unsigned char*)workspace;
-  const dim3 grid(gterm_blocks((n_pairs + 31) / 32));
+  const dim3 grid(term_blocks((n_pairs + 31) / 32));
   dispatch_levels_poly(cfg->n_levels, cfg->poly_int_on != 0, [&](auto l, auto p) {
     hipLaunchKernelGGL((k_consistency_step<decltype(l)::value, decltype(p)::value>), grid, dim3(kThreads), 0, st, a);
   });

@@ -2,16 +2,21 @@
 // shine_normal_step.hip; the gradient-consistency term, shine_consistency_step.hip): the closed-form g of a lane's point, the
 // term's q = dL/dg, and the second-order backward of that loss into the feature tables and W1, W2, w3.
 //
-// One wave = one tile of 64 lanes at a time, lane = point (k_sem_step's launch shape and LDS staging, [64][ST] floats per wave);
-// the per-point math is k_step_v0's lane-per-point chain, its loops over weight rows ROLLED with scalar loads as in k_sem_step
-// (fully unrolled with the weights in LDS it took 256 VGPRs + 256 AGPRs + 1.2 KB of scratch: DESIGN.md 3.18).  Second-order
-// backward with delta = 0: r = A q, a1 = m1 .* (W1 r), a2 = m2 .* (W2 a1); dW1 += v1 (x) r, dW2 += v2 (x) a1, dw3 += a2 by
-// contract64r over the staged tile; feature rows += (dw_c/dx . q) J with the lanes transposed to (row, feature) as in k_sem_step
-// — one fp32 atomic instruction covers 8 rows x the 8 features of a corner.
+// One wave = one tile of 64 lanes at a time, lane = point (a term step's launch shape, shine_term_dev.hpp, and the LDS staging
+// of the lane-per-point kernels, [64][ST] floats per wave); the per-point math is k_step_v0's lane-per-point chain, its loops
+// over weight rows ROLLED with scalar loads (fully unrolled with the weights in LDS it took 256 VGPRs + 256 AGPRs + 1.2 KB of
+// scratch: DESIGN.md 3.18).  Second-order backward with delta = 0: r = A q, a1 = m1 .* (W1 r), a2 = m2 .* (W2 a1);
+// dW1 += v1 (x) r, dW2 += v2 (x) a1, dw3 += a2 by contract64r over the staged tile; feature rows += (dw_c/dx . q) J with the
+// lanes transposed to (row, feature) — one fp32 atomic instruction covers 8 rows x the 8 features of a corner.
 //
-// The three weight grads and the loss are summed in a fixed order inside a wave and a workgroup and in two ticket levels
-// across workgroups (shine_arrive.hpp), so they are bit-identical from call to call; the workgroup that finishes the sum ADDS
-// them to grad_mlp and writes the loss.  The loss is summed in fp64 from the lanes up and divided by the term's count in fp64.
+// The three weight grads and the loss are summed in a fixed order inside a wave and a workgroup and in two ticket levels across
+// workgroups (grid_sum_two_level, shine_term_dev.hpp), so they are bit-identical from call to call; the workgroup that finishes
+// the sum ADDS them to grad_mlp, writes the loss and leaves the workspace all zero.  The loss is summed in fp64 from the lanes up
+// and divided by the term's count in fp64.
+//
+// Of the shared tail (shine_term_dev.hpp) this body takes the launch shape and the grid sum.  It keeps its own lines for the
+// level gather (a helper: 12 to 24 more VGPRs), for the scatter (scatter_corner_rows: k_normal_step<2, false> spills 75 SGPRs, not
+// 74) and for the workgroup's partial (tile_partial: k_consistency_step<1, *> spills 2 more SGPRs).
 //
 // A kernel instantiates gterm_step<L, POLY, P> with a POLICY P that says what a lane's point is, what the term is and what it
 // is divided by:
@@ -19,106 +24,29 @@
 //   P::Ctx, P::begin(a)          per-thread launch facts, read once; Ctx has `den` (the term's count, long long) and `scale`
 //                                (weight / den, what q is multiplied by)
 //   P::tiles(a)                  tiles of 64 lanes
-//   P::select(a, cx, t, lane, j, ln)   does the lane have a point in tile t -> bool; j = its row, ln (P::Lane) = what load / term need
+//   P::select(a, cx, t, lane, j, ln)   does the lane have a point in tile t -> bool; j = its row, ln (P::Lane) = what load / term
+//                                need
 //   P::load(a, j, lane, x0, x1, x2, ln)  the point's coordinates (called by the lanes select() accepted)
 //   P::term(g, ln, lane, scale, q)       -> the lane's addend to the loss sum; q = d (weight * loss) / d g of the lane's point
 //                                (q == 0: the lane sits out of the backward).  Called by every accepted lane of the wave at once
 //   P::kFlags                    the kernel marks a.touched[s][row] = 1 for every corner row a live lane scatters to
 //   P::finish(a, cx)             called by thread 0 of the workgroup that finished the grid sum, after the loss is written
 #pragma once
-#include "shine_arrive.hpp"
-#include "shine_internal.hpp"
+#include "shine_term_dev.hpp"
 
 namespace shine {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;  // waves of a workgroup, a tile each
-constexpr int kMaxBlocks = 256;
-constexpr int kGroup = 16;  // workgroups per first-level run
-constexpr int kGroups = kMaxBlocks / kGroup;
 // partial layout (floats): W1 [32][8] | W2 [32][32] | w3 [32]
 constexpr int P_W1 = 0, P_W2 = P_W1 + H * F, P_W3 = P_W2 + H * H, PW = P_W3 + H;
 // workspace: counters ([0] run-level ticket, [1..kGroups] first-level tickets) | float part[kMaxBlocks][PW] | float run[kGroups][PW]
 // | double loss_part[kMaxBlocks] | double loss_run[kGroups]
-constexpr size_t kCounterBytes = 256;
 constexpr size_t kPartOff = kCounterBytes;
 constexpr size_t kRunOff = kPartOff + (size_t)kMaxBlocks * PW * sizeof(float);
 constexpr size_t kLossOff = kRunOff + (size_t)kGroups * PW * sizeof(float);
 constexpr size_t kLossRunOff = kLossOff + (size_t)kMaxBlocks * sizeof(double);
 constexpr size_t kWorkspaceEnd = kLossRunOff + (size_t)kGroups * sizeof(double);
-static_assert((kGroups + 1) * sizeof(unsigned) <= kCounterBytes && PW % 4 == 0 && kLossOff % 8 == 0, "layout");
-static_assert(kGroup <= 64 && kGroups <= 64, "a run's loss partials are read by one wave, a lane each");
-
-#define NRM_LOOP_STR(x) #x
-#define NRM_ROW_LOOP(n) _Pragma(NRM_LOOP_STR(clang loop vectorize(disable) interleave(disable) unroll_count(n)))
-
-// The sum over the grid of the workgroups' partials, sem_grid_sum's two ticket levels: the last workgroup of each run of kGroup
-// to arrive sums that run in index order, the last run to finish sums the run sums in index order, ADDS them to the three
-// tensors and writes the loss (the fp64 sum over `den`, 0 without one).  Called by every thread of every workgroup; whoever sums a
-// partial clears it behind itself and the counters are reset, so the whole workspace is zero again when the launch ends.
-// -> whether this workgroup finished the sum.
-template <class Args>
-__device__ __forceinline__ bool gterm_grid_sum(const Args& a, bool wgrad, long long ns, unsigned* verdict) {
-  unsigned* cnt = reinterpret_cast<unsigned*>(a.ws);
-  float* part = reinterpret_cast<float*>(a.ws + kPartOff);
-  float* runsum = reinterpret_cast<float*>(a.ws + kRunOff);
-  double* lpart = reinterpret_cast<double*>(a.ws + kLossOff);
-  double* lrun = reinterpret_cast<double*>(a.ws + kLossRunOff);
-  const unsigned G = gridDim.x;
-  const unsigned grp = blockIdx.x / kGroup;
-  const unsigned g0 = grp * kGroup;
-  const unsigned gsz = (G - g0) < (unsigned)kGroup ? (G - g0) : (unsigned)kGroup;
-  const unsigned ngrp = (G + kGroup - 1) / kGroup;
-  const unsigned lane = threadIdx.x & 63u;
-
-  if (!arrive_last(cnt + 1 + grp, gsz, verdict)) return false;
-  if (wgrad) {
-    for (int c = threadIdx.x; c < PW / 4; c += kThreads) {
-      float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-      for (unsigned b = 0; b < gsz; ++b) {
-        float4* src = reinterpret_cast<float4*>(part + (size_t)(g0 + b) * PW + 4 * c);
-        const float4 v = *src;
-        s.x += v.x, s.y += v.y, s.z += v.z, s.w += v.w;
-        *src = make_float4(0.f, 0.f, 0.f, 0.f);  // (read once, by this thread: the workspace is left ALL zero)
-      }
-      *reinterpret_cast<float4*>(runsum + (size_t)grp * PW + 4 * c) = s;
-    }
-  }
-  if (threadIdx.x < 64) {  // (a lane per partial: per-lane addresses, then a fixed-order sum over the lanes)
-    const double v = lane < gsz ? lpart[g0 + lane] : 0.0;
-    if (lane < gsz) lpart[g0 + lane] = 0.0;
-    double s = 0.0;
-    for (unsigned b = 0; b < (unsigned)kGroup; ++b) s += __shfl(v, (int)b, 64);
-    if (lane == 0) lrun[grp] = s;
-  }
-  if (threadIdx.x == 0) __hip_atomic_store(cnt + 1 + grp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next call
-
-  if (!arrive_last(cnt, ngrp, verdict)) return false;
-  if (wgrad) {
-    for (int c = threadIdx.x; c < PW / 4; c += kThreads) {
-      float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-      for (unsigned r = 0; r < ngrp; ++r) {
-        float4* src = reinterpret_cast<float4*>(runsum + (size_t)r * PW + 4 * c);
-        const float4 v = *src;
-        s.x += v.x, s.y += v.y, s.z += v.z, s.w += v.w;
-        *src = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-      const int k = 4 * c;
-      float* dst = k < P_W2 ? a.gW1 + (k - P_W1) : k < P_W3 ? a.gW2 + (k - P_W2) : a.gw3 + (k - P_W3);
-      dst[0] += s.x, dst[1] += s.y, dst[2] += s.z, dst[3] += s.w;  // (a caller's grad tensor may be a 4-byte aligned view)
-    }
-  }
-  if (threadIdx.x < 64) {
-    const double v = lane < ngrp ? lrun[lane] : 0.0;
-    if (lane < ngrp) lrun[lane] = 0.0;
-    double s = 0.0;
-    for (unsigned r = 0; r < (unsigned)kGroups; ++r) s += __shfl(v, (int)r, 64);
-    if (lane == 0) a.loss_out[0] = ns > 0 ? (float)(s / (double)ns) : 0.f;
-  }
-  if (threadIdx.x == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return true;
-}
+static_assert(PW % 4 == 0 && kLossOff % 8 == 0, "layout");
 
 // The kernel's body: s_stage [kWaves * 64 * ST] floats, s_loss [kWaves] doubles and s_flag are the kernel's LDS.
 template <int L, bool POLY, class P>
@@ -202,11 +130,11 @@ __device__ __forceinline__ void gterm_step(const typename P::Args& a, float* s_s
           }
         }
       }
-      // ---- decoder forward for the ReLU masks, k_sem_step's way: ROLLED loops over the weight rows (scalar loads), the lane's
+      // ---- decoder forward for the ReLU masks: ROLLED loops over the weight rows (scalar loads), the lane's
       //      vectors in registers, what a rolled loop produces or consumes element by element in the lane's own LDS row
       const int rows = opaque(H);
       unsigned m1 = 0u;
-NRM_ROW_LOOP(4)
+TERM_ROW_LOOP(4)
       for (int k = 0; k < rows; ++k) {
         float z = w.B1[k];
 #pragma unroll
@@ -222,7 +150,7 @@ NRM_ROW_LOOP(4)
         for (int k = 0; k < H; ++k) h1[k] = row[k], v1[k] = 0.f;
         wave_lds_fence();
         // h2's masks, and v1 = W2^T (m2 .* w3) on the same pass over W2
-NRM_ROW_LOOP(2)
+TERM_ROW_LOOP(2)
         for (int jx = 0; jx < rows; ++jx) {
           float z = w.B2[jx];
 #pragma unroll
@@ -238,7 +166,7 @@ NRM_ROW_LOOP(2)
 #pragma unroll
       for (int k = 0; k < H; ++k) row[k] = ((m1 >> k) & 1u) ? v1[k] : 0.f;
       wave_lds_fence();
-NRM_ROW_LOOP(8)
+TERM_ROW_LOOP(8)
       for (int k = 0; k < rows; ++k) {
         const float vk = row[k];
 #pragma unroll
@@ -262,7 +190,7 @@ NRM_ROW_LOOP(8)
         for (int q = 0; q < F; ++q) rq[q] = A[q][0] * qv[0] + A[q][1] * qv[1] + A[q][2] * qv[2];
 #pragma unroll
         for (int q = 0; q < F; ++q) row[32 + q] = rq[q];
-NRM_ROW_LOOP(4)
+TERM_ROW_LOOP(4)
         for (int k = 0; k < rows; ++k) {
           float tt = 0.f;
 #pragma unroll
@@ -273,7 +201,7 @@ NRM_ROW_LOOP(4)
 #pragma unroll
         for (int k = 0; k < H; ++k) a1[k] = row[40 + k];
         wave_lds_fence();
-NRM_ROW_LOOP(2)
+TERM_ROW_LOOP(2)
         for (int jx = 0; jx < rows; ++jx) {
           float tt = 0.f;
 #pragma unroll
@@ -392,14 +320,18 @@ NRM_ROW_LOOP(2)
       reinterpret_cast<double*>(a.ws + kLossOff)[blockIdx.x] = s;
     }
   }
-  if (gterm_grid_sum(a, wgrad, ns, s_flag) && threadIdx.x == 0) P::finish(a, cx);
-}
-
-// Launch shape: k_sem_step's — four waves per workgroup, a tile each, at most kMaxBlocks workgroups with a grid stride past
-// 64 K lanes; it depends on the tile count alone, so equal batches sum in equal order.
-inline unsigned gterm_blocks(long long tiles) {
-  const long long b = (tiles + kWaves - 1) / kWaves;
-  return (unsigned)(b > kMaxBlocks ? kMaxBlocks : b);
+  // ADDS the three gradients and writes the loss: the fp64 sum over `den`, 0 without one; a frozen decoder: the loss alone
+  const GridSumWs gw = {reinterpret_cast<unsigned*>(a.ws), reinterpret_cast<float*>(a.ws + kPartOff),
+                        reinterpret_cast<float*>(a.ws + kRunOff), reinterpret_cast<double*>(a.ws + kLossOff),
+                        reinterpret_cast<double*>(a.ws + kLossRunOff)};
+  const bool last = grid_sum_two_level<PW, PW / 4, true, 1>(
+      gw, wgrad, s_flag,
+      [&](int k, float4 s) {
+        float* dst = k < P_W2 ? a.gW1 + (k - P_W1) : k < P_W3 ? a.gW2 + (k - P_W2) : a.gw3 + (k - P_W3);
+        dst[0] += s.x, dst[1] += s.y, dst[2] += s.z, dst[3] += s.w;  // (a caller's grad tensor may be a 4-byte aligned view)
+      },
+      [&](const double* sums) { a.loss_out[0] = ns > 0 ? (float)(sums[0] / (double)ns) : 0.f; });
+  if (last && threadIdx.x == 0) P::finish(a, cx);
 }
 
 }  // namespace

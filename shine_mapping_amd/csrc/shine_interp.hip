@@ -6,9 +6,9 @@
 //                      given gg = d loss / d(dx):  dg_p += sum_{l,c} (dw.gg) F_l[id] ;  dF_l[id] += (dw.gg) g_p
 //                      (the second derivative wrt x itself is not produced: coord is a leaf whose .grad nobody reads)
 // Forward is shine_forward(feat_out=...).  These two kernels are lane = point (unordered batches: no node runs to
-// merge), the feature-grad atomics are issued with the lanes transposed to (point, feature); the throughput tier is the
+// merge), the feature-grad atomics are the term steps' transposed scatter (shine_term_dev.hpp); the throughput tier is the
 // fused step.
-#include "shine_internal.hpp"
+#include "shine_term_dev.hpp"
 
 namespace shine {
 
@@ -28,7 +28,6 @@ __global__ __launch_bounds__(256) void k_interp_bwd(InterpArgs a) {
   __shared__ float s_g[4 * 64 * F];
   const int lane = threadIdx.x & 63;
   float* const gt = s_g + (threadIdx.x >> 6) * 64 * F;
-  const int sub = lane >> 3, fi = lane & 7;
   for (long long base = (long long)blockIdx.x * 256; base < a.n; base += (long long)gridDim.x * 256) {
     const bool valid = base + threadIdx.x < a.n;  // the loop itself stays wave-uniform: the trash-row sums are wave-wide
     const long long p = valid ? base + threadIdx.x : a.n - 1;
@@ -39,10 +38,9 @@ __global__ __launch_bounds__(256) void k_interp_bwd(InterpArgs a) {
       float4 g0 = gp[0], g1 = gp[1];
       g[0] = g0.x; g[1] = g0.y; g[2] = g0.z; g[3] = g0.w; g[4] = g1.x; g[5] = g1.y; g[6] = g1.z; g[7] = g1.w;
     }
-    // Feature-grad scatter with the lanes TRANSPOSED: one atomic instruction covers 8 points x the 8 features of one
-    // corner row each (8 x 32 contiguous bytes) instead of 64 different rows x 4 bytes — an eighth of the memory-side
-    // transactions.  g goes through LDS once per tile ([point][feature] -> lane (point & 7 group, feature)), the corner
-    // ids and coefficients of the source point come by shuffle.
+    // g through LDS once per tile for the transposed scatter: stage_row_grads' exchange, kept on its own lines because its
+    // fences sit elsewhere (one in FRONT of the write for the previous tile's reads, none behind the read-back: nothing else of
+    // this kernel touches the rows) and its writes are two float4
     float gval[8];
     wave_lds_fence();  // the previous tile's reads are done
     reinterpret_cast<float4*>(gt + lane * F)[0] = make_float4(g[0], g[1], g[2], g[3]);
@@ -70,15 +68,11 @@ __global__ __launch_bounds__(256) void k_interp_bwd(InterpArgs a) {
       corner_weight_grads(X, Y, Z, dw);
       int ids[8];
       if (slot >= 0) corner_ids(Lv.vals, (unsigned int)slot, ids);
-      float csum = 0.f;  // a miss: all eight corners address the trash row (index -1, :205,231), which receives sum_c
       float coefs[8];
-      int sids[8];  // scatter targets: -1 = nothing (a miss goes to the trash row below, a padding lane nowhere)
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         const float coef = SECOND ? (dw[c][0] * q0 + dw[c][1] * q1 + dw[c][2] * q2) : w[c];
         coefs[c] = coef;
-        csum += coef;
-        sids[c] = (slot >= 0 && valid) ? ids[c] : -1;
         if (slot >= 0 && (SECOND ? a.out_g != nullptr : a.out_x != nullptr)) {
           const float4* rp = reinterpret_cast<const float4*>(Lv.feat + (long long)ids[c] * F);
           float4 r0 = rp[0], r1 = rp[1];
@@ -96,27 +90,9 @@ __global__ __launch_bounds__(256) void k_interp_bwd(InterpArgs a) {
           }
         }
       }
-      if (Lv.grad) {
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-#pragma unroll
-          for (int G = 0; G < 8; ++G) {
-            const int id = __shfl(sids[c], G * 8 + sub, 64);
-            const float cf = __shfl(coefs[c], G * 8 + sub, 64);
-            if (id >= 0) atomic_add_f32(Lv.grad + (long long)id * F + fi, cf * gval[G]);
-          }
-        }
-      }
-      // one atomic per wave and feature for the trash row instead of 64 per missing point on the same 32 bytes (free-space
-      // samples outside the mapped shell miss at every level: same-address atomics serialise at the memory controller)
-      if (Lv.grad && __any(valid && slot < 0)) {
-        const float cm = (valid && slot < 0) ? csum : 0.f;
-#pragma unroll
-        for (int i = 0; i < F; ++i) {
-          const float tsum = wave_sum(cm * g[i]);
-          if (lane == 0 && tsum != 0.f) atomic_add_f32(Lv.grad + Lv.rows * F + i, tsum);
-        }
-      }
+      // a hit scatters to its corner rows, a miss (all eight corners address the trash row, index -1, :205,231) to the trash
+      // row, a padding lane nowhere
+      if (Lv.grad) scatter_corner_rows(Lv, ids, slot >= 0 && valid, valid && slot < 0, coefs, g, gval, lane);
     }
     if (!valid) continue;
     if (!SECOND && a.out_x) {

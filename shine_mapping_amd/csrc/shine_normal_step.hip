@@ -140,7 +140,7 @@ extern "C" int shine_normal_train_step(const shine_tables* t, const shine_step_c
   a.weight_n = weight_n;
   a.loss_out = normal_loss_out;
   a.ws = (unsigned char*)workspace;
-  const dim3 grid(gterm_blocks((n + 63) / 64));
+  const dim3 grid(term_blocks((n + 63) / 64));
   dispatch_levels_poly(cfg->n_levels, cfg->poly_int_on != 0, [&](auto l, auto p) {
     hipLaunchKernelGGL((k_normal_step<decltype(l)::value, decltype(p)::value>), grid, dim3(kThreads), 0, st, a);
   });

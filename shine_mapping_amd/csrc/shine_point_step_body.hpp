@@ -8,22 +8,26 @@
 //   eik    = mean over weight > 0 of (1 - |g|)^2,  g = sigma d pred / d x  (EIK builds; 0 without a surface row)
 //   grads += d loss / d {feature tables, W1, b1, W2, b2, w3, b3}
 //
-// One wave = one tile of batch rows at a time, lane = row (k_sem_step's launch shape).  The head has ONE output, so its
-// first-order backward is delta times the Jacobian chain the eikonal term needs anyway:
+// One wave = one tile of batch rows at a time, lane = row (a term step's launch shape, shine_term_dev.hpp).  The head has ONE
+// output, so its first-order backward is delta times the Jacobian chain the eikonal term needs anyway:
 //   v2 = m2 .* w3,  v1 = m1 .* (W2^T v2),  J = W1f^T v1 = d pred / d f;   d2 = delta v2,  d1 = delta v1,  d f = delta J
 // and with the eikonal term's second-order pieces (q = d loss / d g; r = sigma A q, a1 = m1 .* (W1f r), a2 = m2 .* (W2 a1),
 // shine_gterm_body.hpp's chain with delta = 0) every weight gradient is ONE contraction over the tile's 64 staged rows:
 //   dW1f += v1 (x) (delta f + r)     dW1[:,8] += v1 . (delta ts)     db1 += v1 . delta
 //   dW2  += v2 (x) (delta h1 + a1)   db2 += v2 . delta               dw3 += delta h2 + a2      db3 += delta
 // (the second-order part reaches W1f, W2 and w3 only: J depends on w_t, ts and the biases through the ReLU masks alone).
-// Feature rows receive (w_c delta + sigma dw_c/dx . q) J with the lanes transposed to (row, feature) as in k_sem_step — one fp32
-// atomic instruction covers 8 rows x the 8 features of a corner; the misses of a wave reach the trash row as one atomic per
-// feature.  The decoder layers are rolled loops over weight rows with scalar loads (3.18).
+// Feature rows receive (w_c delta + sigma dw_c/dx . q) J through the shared transposed scatter.  The decoder layers are rolled
+// loops over weight rows with scalar loads (3.18).
 //
 // The six weight grads and the P::NL loss sums (fp64 from the lanes up: [0] the main loss, [1] the eikonal term over the surface
 // rows, the rest the policy's) are added in a fixed order inside a wave and a workgroup and in two ticket levels across
 // workgroups (shine_arrive.hpp), so they are bit-identical from call to call; the workgroup that finishes the sum ADDS the grads,
 // hands the sums to P::finish and leaves the workspace all zero.
+//
+// Of the shared tail (shine_term_dev.hpp) this body takes the launch shape and the scatter.  It keeps its own lines for the level
+// gather (a helper: 12 to 24 more VGPRs in every EIK build) and for the workgroup's partial and the grid sum (through
+// grid_sum_two_level k_ray_step<1, *, false> spills 8 more SGPRs and every k_ray_step<*, *, false> has 2 more DS reads; with the
+// grid sum alone on its own lines k_time_step<1, true, true> and two more builds spill 2 more).
 //
 // A policy P has
 //   Args                      the kernel's argument: PointStepArgs + what P reads
@@ -38,17 +42,12 @@
 //   grad_dst(a, k)            where entry k of the partial layout is added (null: nowhere)
 //   finish(a, sums, ns)       one lane, with the grid's sums: writes the loss
 #pragma once
-#include "shine_arrive.hpp"
+#include "shine_term_dev.hpp"
 #include "shine_term_host.hpp"
 
 namespace shine {
 namespace pstep {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;  // waves of a workgroup, a tile each
-constexpr int kMaxBlocks = 256;
-constexpr int kGroup = 16;  // workgroups per first-level run
-constexpr int kGroups = kMaxBlocks / kGroup;
 // a lane's staging row (floats): [0,32) left operand | [32,64) right operand ([40] delta ts, [41] delta beside the 8-wide one)
 // | [64] delta | [65,97) h2, then delta h2 + a2
 constexpr int TST = 97;  // (odd: conflict-free column reads)
@@ -56,12 +55,7 @@ constexpr int R_TS = 40, R_D1 = 41, R_D2 = 64, R_H2 = 65;
 // partial layout (floats): W1f [32][8] | w_t [32] | b1 [32] | W2 [32][32] | b2 [32] | w3 [32] | b3 [1] + 3 unused
 constexpr int P_W1 = 0, P_WT = P_W1 + H * F, P_B1 = P_WT + H, P_W2 = P_B1 + H, P_B2 = P_W2 + H * H, P_W3 = P_B2 + H,
               P_B3 = P_W3 + H, PW = P_B3 + 4;
-constexpr int kMaxNL = 3;
-static_assert((kGroups + 1) * sizeof(unsigned) <= 256 && PW % 4 == 0, "layout");
-static_assert(kGroup * kMaxNL <= 64 && kGroups * kMaxNL <= 64, "a run's loss partials are read by one wave, a lane each");
-
-#define PSTEP_LOOP_STR(x) #x
-#define PSTEP_ROW_LOOP(n) _Pragma(PSTEP_LOOP_STR(clang loop vectorize(disable) interleave(disable) unroll_count(n)))
+static_assert(PW % 4 == 0, "layout");
 
 struct PointStepArgs {
   LevelSet ls;
@@ -101,7 +95,7 @@ struct PointWork {
 inline PointWork point_layout(void* workspace, int nl) {
   Arena ar(workspace);
   PointWork w;
-  w.cnt = ar.take<unsigned>(64);
+  w.cnt = ar.take<unsigned>(kCounterBytes / sizeof(unsigned));
   w.part = ar.take<float>((size_t)kMaxBlocks * PW);
   w.run = ar.take<float>((size_t)kGroups * PW);
   w.lpart = ar.take<double>((size_t)kMaxBlocks * nl);
@@ -110,20 +104,15 @@ inline PointWork point_layout(void* workspace, int nl) {
   return w;
 }
 
-// Launch shape: k_sem_step's — four waves per workgroup, a tile each, at most kMaxBlocks workgroups with a grid stride beyond;
-// it depends on the tile count alone, so equal batches sum in equal order.
-inline unsigned point_step_blocks(long long tiles) {
-  const long long b = (tiles + kWaves - 1) / kWaves;
-  return (unsigned)(b > kMaxBlocks ? kMaxBlocks : b);
-}
-
-// The sum over the grid of the workgroups' partials, gterm_grid_sum's two ticket levels with six tensors and NL loss sums: the
+// The sum over the grid of the workgroups' partials, grid_sum_two_level's two ticket levels on this body's own lines (see the
+// head of the file) with six tensors and NL loss sums: the
 // last workgroup of each run of kGroup to arrive sums that run in index order, the last run to finish sums the run sums in
 // index order, ADDS them to the six tensors and writes the loss.  Whoever sums a partial clears it behind itself and the tickets
 // are reset, so the whole workspace is zero again when the launch ends.
 template <class P>
 __device__ __forceinline__ void point_grid_sum(const typename P::Args& a, bool wgrad, long long ns, unsigned* verdict) {
   constexpr unsigned NL = P::NL;
+  static_assert(kGroup * NL <= 64 && kGroups * NL <= 64, "a run's loss partials are read by one wave, a lane each");
   const unsigned G = gridDim.x;
   const unsigned grp = blockIdx.x / kGroup;
   const unsigned g0 = grp * kGroup;
@@ -188,7 +177,6 @@ __device__ __forceinline__ void point_step_body(const typename P::Args& a, float
   float* st = s_stage + wv * 64 * TST;
   float* row = st + lane * TST;
   const int jj = lane & 31, hi = lane >> 5;
-  const int sub = lane >> 3, fi = lane & 7;
   const bool wgrad = a.want_wgrad != 0;
   const float sigma = a.sigma;
   const int rows = opaque(H);
@@ -271,7 +259,7 @@ __device__ __forceinline__ void point_step_body(const typename P::Args& a, float
     // ---- the head forward, rolled over the weight rows: h1 through the lane's LDS row into registers, h2 left at row[R_H2..),
     //      and v1 = W2^T (m2 .* w3) on the same pass over W2
     unsigned m1 = 0u, m2 = 0u;
-PSTEP_ROW_LOOP(4)
+TERM_ROW_LOOP(4)
     for (int k = 0; k < rows; ++k) {
       float z;
       if constexpr (P::SHIFT) z = fmaf(w.W1[k * W1S + F], P::shift(ln), w.B1[k]);  // a per-point shift of the first bias
@@ -287,7 +275,7 @@ PSTEP_ROW_LOOP(4)
     for (int k = 0; k < H; ++k) h1[k] = row[k], v1[k] = 0.f;
     wave_lds_fence();
     float y = w.B3[0];
-PSTEP_ROW_LOOP(2)
+TERM_ROW_LOOP(2)
     for (int jx = 0; jx < rows; ++jx) {
       float z = w.B2[jx];
 #pragma unroll
@@ -308,7 +296,7 @@ PSTEP_ROW_LOOP(2)
     float J[F];
 #pragma unroll
     for (int q = 0; q < F; ++q) J[q] = 0.f;
-PSTEP_ROW_LOOP(8)
+TERM_ROW_LOOP(8)
     for (int k = 0; k < rows; ++k) {
       const float vk = row[k];
 #pragma unroll
@@ -348,7 +336,7 @@ PSTEP_ROW_LOOP(8)
           second = true;
 #pragma unroll
           for (int q = 0; q < F; ++q) rq[q] = sigma * (A[q][0] * qv[0] + A[q][1] * qv[1] + A[q][2] * qv[2]);
-PSTEP_ROW_LOOP(4)
+TERM_ROW_LOOP(4)
           for (int k = 0; k < rows; ++k) {
             float tt = 0.f;
 #pragma unroll
@@ -360,7 +348,7 @@ PSTEP_ROW_LOOP(4)
 #pragma unroll
           for (int k = 0; k < H; ++k) a1[k] = row[32 + k];
           wave_lds_fence();
-PSTEP_ROW_LOOP(2)
+TERM_ROW_LOOP(2)
           for (int jx = 0; jx < rows; ++jx) {
             float tt = 0.f;
 #pragma unroll
@@ -384,7 +372,7 @@ PSTEP_ROW_LOOP(2)
       else row[R_TS] = 0.f;
       row[R_D1] = delta;
       wave_lds_fence();
-PSTEP_ROW_LOOP(4)
+TERM_ROW_LOOP(4)
       for (int pp = 0; pp < 64; ++pp) {
         const float* pr = st + pp * TST;
         const float l = pr[jj];
@@ -402,7 +390,7 @@ PSTEP_ROW_LOOP(4)
       for (int k = 0; k < H; ++k) row[32 + k] = h1[k];
       row[R_D2] = delta;
       wave_lds_fence();
-PSTEP_ROW_LOOP(4)
+TERM_ROW_LOOP(4)
       for (int pp = 0; pp < 64; ++pp) {
         const float* pr = st + pp * TST;
         const float l = pr[jj];
@@ -412,14 +400,9 @@ PSTEP_ROW_LOOP(4)
       }
       wave_lds_fence();
     }
-    // ---- feature grads: J through LDS once ([row][feature] -> lane (row & 7 group, feature)), ids and weights by shuffle
-#pragma unroll
-    for (int q = 0; q < F; ++q) st[lane * F + q] = J[q];
-    wave_lds_fence();
+    // ---- feature grads: rows += (w_c delta + sigma dw_c/dx . q) J
     float gval[8];
-#pragma unroll
-    for (int G = 0; G < 8; ++G) gval[G] = st[G * 64 + lane];
-    wave_lds_fence();
+    stage_row_grads(st, lane, J, gval);
 #pragma unroll
     for (int s = 0; s < L; ++s) {
       const LevelDev& Lv = a.ls.lv[s];
@@ -439,28 +422,7 @@ PSTEP_ROW_LOOP(4)
 #pragma unroll
         for (int c = 0; c < 8; ++c) cf[c] = fmaf(sigma, dw[c][0] * qv[0] + dw[c][1] * qv[1] + dw[c][2] * qv[2], cf[c]);
       }
-      float csum = 0.f;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        csum += cf[c];
-        const int sid = hit ? ids[c] : -1;
-#pragma unroll
-        for (int G = 0; G < 8; ++G) {
-          const int id = __shfl(sid, G * 8 + sub, 64);
-          const float cv = __shfl(cf[c], G * 8 + sub, 64);
-          if (id >= 0) atomic_add_f32(Lv.grad + (long long)id * F + fi, cv * gval[G]);
-        }
-      }
-      // a miss: all eight corners address the trash row, which receives sum_c of the same terms — one atomic per wave and feature
-      const bool miss = valid && !hit;
-      if (__any(miss)) {
-        const float cm = miss ? csum : 0.f;
-#pragma unroll
-        for (int q = 0; q < F; ++q) {
-          const float tsum = wave_sum(cm * J[q]);
-          if (lane == 0 && tsum != 0.f) atomic_add_f32(Lv.grad + Lv.rows * F + q, tsum);
-        }
-      }
+      scatter_corner_rows(Lv, ids, hit, valid && !hit, cf, J, gval, lane);
     }
   }
 

@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256) void k_query_points(QueryArgs a) {
     for (int s = 0; s < L; ++s) {
       const bool hit = slot[s] >= 0;
       if (s == a.check_slot) mask = hit;
-      // (one level of k_forward_points' interpolation; a shared helper raised this kernel's SGPR spills at L = 4)
+      // (one level of k_forward_points' interpolation; a shared helper raised this kernel's SGPR spills at L = 4: 50, not 38)
       const LevelDev& Lv = a.ls.lv[s];
       int ids[8];
       corner_ids(Lv.vals, hit ? (unsigned int)slot[s] : 0u, ids);

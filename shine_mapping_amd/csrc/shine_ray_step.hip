@@ -231,7 +231,7 @@ extern "C" int shine_ray_step(const shine_tables* t, const shine_step_config* cf
   a.neus = neus_on != 0;
   a.inv_r = 1.0f / (float)n_rays;
   a.dinv_r = 1.0 / (double)n_rays;
-  const dim3 grid(point_step_blocks((n_rays + a.rpt - 1) / a.rpt));
+  const dim3 grid(term_blocks((n_rays + a.rpt - 1) / a.rpt));
   dispatch_levels_poly(cfg->n_levels, cfg->poly_int_on != 0, [&](auto l, auto p) {
     constexpr int LL = decltype(l)::value;
     constexpr bool PP = decltype(p)::value;

@@ -1,25 +1,19 @@
 // shine_sem_head.hpp — the semantic head's device code shared by shine_semantic.hip (forward, backward, mesh labels) and
 // shine_sem_step.hip (the training loop's NLL launch): the weight pointers, the two hidden layers, the class layer with its
-// log-softmax, the layout of the per-workgroup weight-grad partials and the two-level ticket sum over them (sem_grid_sum).
+// log-softmax, the layout of the per-workgroup weight-grad partials and what the grid sum over them (shine_term_dev.hpp) does
+// with every summed element (sem_grid_sum).
 #pragma once
-#include "shine_arrive.hpp"
-#include "shine_internal.hpp"
+#include "shine_term_dev.hpp"
 
 namespace shine {
 namespace sem {
 
 constexpr int CM = SHINE_SEM_MAX_CLASSES;  // 32
 constexpr int SR = 33;                     // forward staging row stride (odd: the lanes' rows hit different banks)
-constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 256;            // backward workgroups at most
-constexpr int kGroup = 16;                 // workgroups per first-level run
-constexpr int kGroups = kMaxBlocks / kGroup;
 // partial layout (floats): W1 [32][8] | b1 [32] | W2 [32][32] | b2 [32] | Wc [32][32] | bc [32] (Wc / bc padded to 32 classes)
 constexpr int P_W1 = 0, P_B1 = P_W1 + H * F, P_W2 = P_B1 + H, P_B2 = P_W2 + H * H, P_WC = P_B2 + H, P_BC = P_WC + CM * H;
 constexpr int P_N = P_BC + CM;
-constexpr size_t kCounterBytes = 256;  // [0] run-level ticket, [1..kGroups] first-level tickets
 static_assert(kCounterBytes + (size_t)(kMaxBlocks + kGroups) * P_N * sizeof(float) <= SHINE_SEM_WORKSPACE_BYTES, "workspace");
-static_assert((kGroups + 1) * sizeof(unsigned) <= kCounterBytes, "counters");
 
 struct SemArgsPtrs {
   const float* mlp[6];  // W1 [32][8], b1 [32], W2 [32][32], b2 [32], Wc [C][32], bc [C]
@@ -37,16 +31,13 @@ __device__ __forceinline__ SemW sem_weights(const float* const* mlp) {
               uniform_ro(mlp[5])};
 }
 
-#define SEM_LOOP_STR(x) #x
-#define SEM_ROW_LOOP(n) _Pragma(SEM_LOOP_STR(clang loop vectorize(disable) interleave(disable) unroll_count(n)))
-
 // h1 = relu(W1 f + b1) (registers), h2 = relu(W2 h1 + b2) (staged at row[0..32)); the ReLU masks.  row: the lane's own LDS
 // row (>= 32 floats); h1 passes through it first.
 __device__ __forceinline__ void sem_hidden(const SemW& w, const float (&f)[F], float* row, float (&h1)[H], unsigned& m1,
                                            unsigned& m2) {
   const int rows = opaque(H);
   m1 = 0u, m2 = 0u;
-SEM_ROW_LOOP(4)
+TERM_ROW_LOOP(4)
   for (int k = 0; k < rows; ++k) {
     float z = w.B1[k];
 #pragma unroll
@@ -58,7 +49,7 @@ SEM_ROW_LOOP(4)
 #pragma unroll
   for (int k = 0; k < H; ++k) h1[k] = row[k];
   wave_lds_fence();
-SEM_ROW_LOOP(2)
+TERM_ROW_LOOP(2)
   for (int j = 0; j < rows; ++j) {
     float z = w.B2[j];
 #pragma unroll
@@ -77,7 +68,7 @@ __device__ __forceinline__ int sem_head(const SemW& w, float* row, int C) {
   wave_lds_fence();
   const int nc = opaque(C);
   float mx = -__builtin_inff();
-SEM_ROW_LOOP(2)
+TERM_ROW_LOOP(2)
   for (int c = 0; c < nc; ++c) {
     float z = w.BC[c];
 #pragma unroll
@@ -109,55 +100,31 @@ __device__ __forceinline__ float* sem_grad_slot(const SemGradPtrs& gp, int k, in
   return k - P_BC < C ? gp.g[5] + (k - P_BC) : nullptr;
 }
 
-// The sum over the grid of the workgroups' partial vectors (STRIDE floats each at ws + kCounterBytes, stored by the caller), in
-// two ticket levels (shine_arrive.hpp): the last workgroup of each run of kGroup to arrive sums that run's partials in index
-// order, the last run to finish sums the run sums in index order and stores them to (ADD: adds them to) the six tensors of gp.
-// With STRIDE = P_N + 4 the float at P_N is summed along and *loss_out = its sum * loss_scale.  Only the columns of four floats
-// from c0 on are summed (a frozen head: c0 = P_N / 4, the loss alone).  Called by every thread of every workgroup; leaves the
-// counters zero.  verdict: one LDS word.
+// The grid sum (grid_sum_two_level) of the workgroups' partial vectors, STRIDE floats each at ws + kCounterBytes, the run sums
+// behind them: every summed element is stored to (ADD: added to) its place in the six tensors of gp.  With STRIDE = P_N + 4 the
+// float at P_N is summed along and *loss_out = its sum * loss_scale (the three floats behind it are summed along and never used).
+// A frozen head (!wgrad): only the loss's column is summed.  The partials are left as they are: every launch stores all it reads.
 template <int STRIDE, bool ADD>
-__device__ __forceinline__ void sem_grid_sum(unsigned char* ws, int c0, const SemGradPtrs& gp, int C, float* loss_out,
+__device__ __forceinline__ void sem_grid_sum(unsigned char* ws, bool wgrad, const SemGradPtrs& gp, int C, float* loss_out,
                                              float loss_scale, unsigned* verdict) {
   static_assert((STRIDE == P_N || STRIDE == P_N + 4) && P_N % 4 == 0 && P_B1 % 4 == 0 && P_BC % 4 == 0, "float4 walk");
-  unsigned* cnt = reinterpret_cast<unsigned*>(ws);
-  const float* part = reinterpret_cast<const float*>(ws + kCounterBytes);
-  float* runsum = reinterpret_cast<float*>(ws + kCounterBytes) + (size_t)kMaxBlocks * STRIDE;  // [kGroups][STRIDE]
-  const unsigned G = gridDim.x;
-  const unsigned grp = blockIdx.x / kGroup;
-  const unsigned g0 = grp * kGroup;
-  const unsigned gsz = (G - g0) < (unsigned)kGroup ? (G - g0) : (unsigned)kGroup;
-  const unsigned ngrp = (G + kGroup - 1) / kGroup;
-
-  if (!arrive_last(cnt + 1 + grp, gsz, verdict)) return;
-  for (int c = c0 + threadIdx.x; c < STRIDE / 4; c += kThreads) {
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (unsigned b = 0; b < gsz; ++b) {
-      const float4 v = *reinterpret_cast<const float4*>(part + (size_t)(g0 + b) * STRIDE + 4 * c);
-      s.x += v.x, s.y += v.y, s.z += v.z, s.w += v.w;
-    }
-    *reinterpret_cast<float4*>(runsum + (size_t)grp * STRIDE + 4 * c) = s;
-  }
-  if (threadIdx.x == 0) __hip_atomic_store(cnt + 1 + grp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next call
-
-  if (!arrive_last(cnt, ngrp, verdict)) return;
-  for (int c = c0 + threadIdx.x; c < STRIDE / 4; c += kThreads) {
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (unsigned r = 0; r < ngrp; ++r) {
-      const float4 v = *reinterpret_cast<const float4*>(runsum + (size_t)r * STRIDE + 4 * c);
-      s.x += v.x, s.y += v.y, s.z += v.z, s.w += v.w;
-    }
-    if (4 * c == P_N) {
-      loss_out[0] = s.x * loss_scale;
-      continue;
-    }
-    const float sv[4] = {s.x, s.y, s.z, s.w};
+  float* part = reinterpret_cast<float*>(ws + kCounterBytes);
+  const GridSumWs w = {reinterpret_cast<unsigned*>(ws), part, part + (size_t)kMaxBlocks * STRIDE, nullptr, nullptr};
+  grid_sum_two_level<STRIDE, P_N / 4, false, 0>(
+      w, wgrad, verdict,
+      [&](int k, float4 s) {
+        if (k == P_N) {
+          loss_out[0] = s.x * loss_scale;
+          return;
+        }
+        const float sv[4] = {s.x, s.y, s.z, s.w};
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float* dst = sem_grad_slot(gp, 4 * c + e, C);
-      if (dst) *dst = ADD ? *dst + sv[e] : sv[e];
-    }
-  }
-  if (threadIdx.x == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int e = 0; e < 4; ++e) {
+          float* dst = sem_grad_slot(gp, k + e, C);
+          if (dst) *dst = ADD ? *dst + sv[e] : sv[e];
+        }
+      },
+      [](const double*) {});
 }
 
 inline int fill_mlp(SemArgsPtrs* p, const float* const* mlp, int32_t n_class, const char* what) {

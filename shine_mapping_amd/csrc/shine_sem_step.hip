@@ -8,13 +8,12 @@
 //
 // Only the m = ceil(n / d) decimated rows are computed.  One wave = one tile of 64 computed rows at a time, lane = row, exactly
 // k_sem_bwd's staging ([64][ST] floats of LDS per wave): forward through the head, dz = weight_s / m * (softmax - onehot), the
-// three weight-grad contractions, d feature, then the feature-grad scatter of shine_interp.hip's backward with the lanes
-// transposed to (row, feature) — one fp32 atomic instruction covers 8 rows x the 8 features of one corner each; the misses of a
-// wave reach the trash row as one atomic per feature.
+// three weight-grad contractions, d feature, then the shared tail of a term step (shine_term_dev.hpp): the transposed
+// feature-grad scatter with coefficients w_c, the workgroup's partial and the two-level grid sum.
 //
-// The six weight grads and the loss are summed as in k_sem_bwd (fixed order inside a wave and a workgroup, two ticket levels
-// across workgroups), so they are bit-identical from call to call; the workgroup that finishes the sum ADDS them to grad_mlp and
-// writes the loss.  What bounds the launch at the reference's batch (4096 rows = 64 tiles) is the latency of ONE tile through
+// The six weight grads and the loss are summed in a fixed order inside a wave and a workgroup and in two ticket levels across
+// workgroups, so they are bit-identical from call to call; the workgroup that finishes the sum ADDS them to grad_mlp and writes
+// the loss.  What bounds the launch at the reference's batch (4096 rows = 64 tiles) is the latency of ONE tile through
 // the head and back — the rolled weight-row loops are chains of scalar loads and FMAs — not throughput: 64 waves on 16 CUs.
 #include "shine_sem_head.hpp"
 #include "shine_term_host.hpp"
@@ -25,8 +24,6 @@ namespace {
 
 constexpr int PS = P_N + 4;  // partial stride in floats: the six weight grads, then [P_N] the tile losses
 static_assert(kCounterBytes + (size_t)(kMaxBlocks + kGroups) * PS * sizeof(float) <= SHINE_SEM_WORKSPACE_BYTES, "workspace");
-
-constexpr int kWaves = kThreads / 64;  // waves of a workgroup, a tile each
 
 struct SemStepArgs {
   LevelSet ls;
@@ -55,7 +52,6 @@ __global__ __launch_bounds__(kThreads) void k_sem_step(const SemStepArgs a) {
   float* st = s_stage + wv * 64 * ST;
   float* row = st + lane * ST;  // [0,32) left operands, [32,64) right operands
   const int jj = lane & 31, hi = lane >> 5;
-  const int sub = lane >> 3, fi = lane & 7;
   const bool wgrad = a.want_wgrad != 0;
   const int rows = opaque(H);
   const int nc = opaque(a.C);
@@ -142,7 +138,7 @@ __global__ __launch_bounds__(kThreads) void k_sem_step(const SemStepArgs a) {
     float dd[H];
 #pragma unroll
     for (int k = 0; k < H; ++k) dd[k] = 0.f;
-SEM_ROW_LOOP(2)
+TERM_ROW_LOOP(2)
     for (int c = 0; c < nc; ++c) {
       const float dz = row[c];
 #pragma unroll
@@ -161,7 +157,7 @@ SEM_ROW_LOOP(2)
     // dh1 = W2^T d2; d1 = m1 .* dh1
 #pragma unroll
     for (int k = 0; k < H; ++k) dd[k] = 0.f;
-SEM_ROW_LOOP(2)
+TERM_ROW_LOOP(2)
     for (int j = 0; j < rows; ++j) {
       const float d2 = row[j];
 #pragma unroll
@@ -177,7 +173,7 @@ SEM_ROW_LOOP(2)
     float df[F];
 #pragma unroll
     for (int q = 0; q < F; ++q) df[q] = 0.f;
-SEM_ROW_LOOP(8)
+TERM_ROW_LOOP(8)
     for (int k = 0; k < rows; ++k) {
       const float dk = row[k];
 #pragma unroll
@@ -187,14 +183,9 @@ SEM_ROW_LOOP(8)
       contract64r<4>(st, jj, 32 + hi * 4, accW1, accb1, true);
     }
     wave_lds_fence();
-    // ---- feature grads: df through LDS once ([row][feature] -> lane (row & 7 group, feature)), ids and weights by shuffle
-#pragma unroll
-    for (int q = 0; q < F; ++q) st[lane * F + q] = df[q];
-    wave_lds_fence();
+    // ---- feature grads: rows += w_c df
     float gval[8];
-#pragma unroll
-    for (int G = 0; G < 8; ++G) gval[G] = st[G * 64 + lane];
-    wave_lds_fence();
+    stage_row_grads(st, lane, df, gval);
 #pragma unroll
     for (int s = 0; s < L; ++s) {
       const LevelDev& Lv = a.ls.lv[s];
@@ -206,27 +197,7 @@ SEM_ROW_LOOP(8)
                  Z = axis_weight<POLY>(x2, Lv.res, Lv.dres);
       float wc[8];
       corner_weights(X.t, Y.t, Z.t, wc);
-      float csum = 0.f;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        csum += wc[c];
-        const int sid = hit ? ids[c] : -1;
-#pragma unroll
-        for (int G = 0; G < 8; ++G) {
-          const int id = __shfl(sid, G * 8 + sub, 64);
-          const float cf = __shfl(wc[c], G * 8 + sub, 64);
-          if (id >= 0) atomic_add_f32(Lv.grad + (long long)id * F + fi, cf * gval[G]);
-        }
-      }
-      // a miss: all eight corners address the trash row, which receives sum_c w_c * df — one atomic per wave and feature
-      if (__any(valid && !hit)) {
-        const float cm = (valid && !hit) ? csum : 0.f;
-#pragma unroll
-        for (int q = 0; q < F; ++q) {
-          const float tsum = wave_sum(cm * df[q]);
-          if (lane == 0 && tsum != 0.f) atomic_add_f32(Lv.grad + Lv.rows * F + q, tsum);
-        }
-      }
+      scatter_corner_rows(Lv, ids, hit, valid && !hit, wc, df, gval, lane);
     }
   }
 
@@ -240,17 +211,9 @@ SEM_ROW_LOOP(8)
 #pragma unroll
   for (int q = 0; q < 4; ++q) vals[32 + q] = accW1[q];
   vals[36] = accbc, vals[37] = accb2, vals[38] = accb1, vals[39] = accloss;
-#pragma unroll
-  for (int v = 0; v < NV; ++v) s_stage[(wv * NV + v) * 64 + lane] = vals[v];
-  __syncthreads();
-  float* part = reinterpret_cast<float*>(a.ws + kCounterBytes);
-  float* mine = part + (size_t)blockIdx.x * PS;
+  tile_partial<NV>(vals, s_stage, wv, lane);
   if (wv == 0) {
-#pragma unroll
-    for (int ww = 1; ww < kWaves; ++ww) {
-#pragma unroll
-      for (int v = 0; v < NV; ++v) vals[v] += s_stage[(ww * NV + v) * 64 + lane];
-    }
+    float* mine = reinterpret_cast<float*>(a.ws + kCounterBytes) + (size_t)blockIdx.x * PS;
     if (wgrad) {
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
@@ -269,17 +232,7 @@ SEM_ROW_LOOP(8)
   }
   // ADDS the six gradients and writes the loss (the three floats behind the loss's slot are summed along and never used); a
   // frozen head: only the loss's column is summed
-  sem_grid_sum<PS, true>(a.ws, wgrad ? 0 : P_N / 4, a.gp, a.C, a.loss_out, a.inv_m, &s_flag);
-}
-
-// Launch shape: four waves per workgroup, a tile each, at most kMaxBlocks workgroups with a grid stride past 64 K rows; it
-// depends on m alone, so equal batches sum in equal order.  (One wave per workgroup — a tile per CU up to 16 K rows — was
-// measured at N = 4096: 8 us less with the head frozen, 13 us MORE with it training, where 64 partial vectors instead of 16
-// meet in the ticket sums; not kept.  DESIGN.md 3.15.)
-unsigned sem_step_blocks(long long m) {
-  const long long tiles = (m + 63) / 64;
-  const long long b = (tiles + kWaves - 1) / kWaves;
-  return (unsigned)(b > kMaxBlocks ? kMaxBlocks : b);
+  sem_grid_sum<PS, true>(a.ws, wgrad, a.gp, a.C, a.loss_out, a.inv_m, &s_flag);
 }
 
 }  // namespace
@@ -320,7 +273,7 @@ extern "C" int shine_sem_train_step(const shine_tables* t, const shine_step_conf
   a.want_wgrad = grad_mlp ? 1 : 0;
   a.loss_out = sem_loss_out;
   a.ws = (unsigned char*)workspace;
-  const dim3 grid(sem_step_blocks(m));
+  const dim3 grid(term_blocks((m + 63) / 64));
   dispatch_levels_poly(cfg->n_levels, cfg->poly_int_on != 0, [&](auto l, auto p) {
     hipLaunchKernelGGL((k_sem_step<decltype(l)::value, decltype(p)::value>), grid, dim3(kThreads), 0, st, a);
   });

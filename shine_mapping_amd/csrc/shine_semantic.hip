@@ -11,7 +11,7 @@
 // rounded logp with the first index winning ties, exactly torch.argmax(sem_label_prob(f)).
 //
 // Weight grads are repeat-bit-identical: every wave accumulates its tiles in a fixed order, the four waves of a workgroup are
-// summed in a fixed order, and the workgroups' partials meet in the two ticket levels of shine_sem_head.hpp's sem_grid_sum.
+// summed in a fixed order, and the workgroups' partials meet in the two ticket levels of shine_term_dev.hpp's grid sum.
 #include "shine_sem_head.hpp"
 #include "shine_term_host.hpp"
 
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(kThreads) void k_sem_bwd(const float* __restrict__ 
   for (int q = 0; q < 4; ++q) accW1[q] = 0.f;
 
   const long long tiles = (n + 63) >> 6;
-  for (long long t = (long long)blockIdx.x * 4 + wv; t < tiles; t += (long long)gridDim.x * 4) {
+  for (long long t = (long long)blockIdx.x * kWaves + wv; t < tiles; t += (long long)gridDim.x * kWaves) {
     const long long i = t * 64 + lane;
     const bool valid = i < n;
     float f[F];
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(kThreads) void k_sem_bwd(const float* __restrict__ 
     float d[H];
 #pragma unroll
     for (int k = 0; k < H; ++k) d[k] = 0.f;
-SEM_ROW_LOOP(2)
+TERM_ROW_LOOP(2)
     for (int c = 0; c < nc; ++c) {
       const float dz = row[c];
 #pragma unroll
@@ -121,7 +121,7 @@ SEM_ROW_LOOP(2)
     // dh1 = W2^T d2; d1 = m1 .* dh1
 #pragma unroll
     for (int k = 0; k < H; ++k) d[k] = 0.f;
-SEM_ROW_LOOP(2)
+TERM_ROW_LOOP(2)
     for (int j = 0; j < rows; ++j) {
       const float d2 = row[j];
 #pragma unroll
@@ -137,7 +137,7 @@ SEM_ROW_LOOP(2)
     float df[F];
 #pragma unroll
     for (int q = 0; q < F; ++q) df[q] = 0.f;
-SEM_ROW_LOOP(8)
+TERM_ROW_LOOP(8)
     for (int k = 0; k < rows; ++k) {
       const float dk = row[k];
 #pragma unroll
@@ -155,7 +155,8 @@ SEM_ROW_LOOP(8)
   }
   if (!wgrad) return;
 
-  // ---- the workgroup's partial: the four waves summed in a fixed order through LDS
+  // ---- the workgroup's partial: the four waves summed PAIRWISE, (0 + 1) + (2 + 3), through LDS — not tile_partial's index
+  //      order, which rounds differently: these grads keep the bits they have always had
   __syncthreads();
   constexpr int NV = 39;
   float vals[NV];
@@ -187,7 +188,7 @@ SEM_ROW_LOOP(8)
       mine[P_B1 + jj] = vals[38];
     }
   }
-  sem_grid_sum<P_N, false>(ws, 0, gp, C, nullptr, 0.f, &s_flag);  // writes the six gradients
+  sem_grid_sum<P_N, false>(ws, true, gp, C, nullptr, 0.f, &s_flag);  // writes the six gradients
 }
 
 // ---- mesh labels: the interpolation of shine_query_points (shine_query.hip), then the head above; nothing but the label leaves
@@ -279,11 +280,8 @@ extern "C" int shine_sem_backward(const float* feat, const float* logp, const fl
     }
     return SHINE_OK;
   }
-  const long long tiles = (n + 63) / 64;
-  const long long b = (tiles + 3) / 4;
-  const unsigned grid = (unsigned)(b > kMaxBlocks ? kMaxBlocks : b);
-  hipLaunchKernelGGL(k_sem_bwd, dim3(grid), dim3(kThreads), 0, st, feat, logp, grad_logp, (long long)n, p, (int)n_class,
-                     grad_feat_out, gp, grad_mlp ? 1 : 0, (unsigned char*)workspace);
+  hipLaunchKernelGGL(k_sem_bwd, dim3(term_blocks((n + 63) / 64)), dim3(kThreads), 0, st, feat, logp, grad_logp, (long long)n, p,
+                     (int)n_class, grad_feat_out, gp, grad_mlp ? 1 : 0, (unsigned char*)workspace);
   SHINE_HIP_CHECK(hipGetLastError());
   return SHINE_OK;
 }

@@ -11,7 +11,7 @@
 //
 // The chain below is shine_point_step_body.hpp's (shared with k_ray_step, shine_ray_step.hip); this file holds its TimePolicy — the
 // 9-wide head and the BCE's delta — and the entry point.
-// One wave = one tile of 64 batch rows at a time, lane = row (k_sem_step's launch shape).  The head has ONE output, so its
+// One wave = one tile of 64 batch rows at a time, lane = row (a term step's launch shape, shine_term_dev.hpp).  The head has ONE output, so its
 // first-order backward is delta = d bce / d pred times the Jacobian chain the eikonal term needs anyway:
 //   v2 = m2 .* w3,  v1 = m1 .* (W2^T v2),  J = W1f^T v1 = d pred / d f;   d2 = delta v2,  d1 = delta v1,  d f = delta J
 // and with the eikonal term's second-order pieces (q = d loss / d g; r = sigma A q, a1 = m1 .* (W1f r), a2 = m2 .* (W2 a1),
@@ -19,9 +19,8 @@
 //   dW1f += v1 (x) (delta f + r)     dW1[:,8] += v1 . (delta ts)     db1 += v1 . delta
 //   dW2  += v2 (x) (delta h1 + a1)   db2 += v2 . delta               dw3 += delta h2 + a2      db3 += delta
 // (the second-order part reaches W1f, W2 and w3 only: J depends on w_t, ts and the biases through the ReLU masks alone).
-// Feature rows receive (w_c delta + sigma dw_c/dx . q) J with the lanes transposed to (row, feature) as in k_sem_step — one fp32
-// atomic instruction covers 8 rows x the 8 features of a corner; the misses of a wave reach the trash row as one atomic per
-// feature.  The decoder layers are rolled loops over weight rows with scalar loads (3.18).
+// Feature rows receive (w_c delta + sigma dw_c/dx . q) J through the shared transposed scatter (shine_term_dev.hpp).  The decoder
+// layers are rolled loops over weight rows with scalar loads (3.18).
 //
 // The six weight grads and both loss sums (BCE over the batch, eikonal over the surface rows, fp64 from the lanes up) are
 // added in a fixed order inside a wave and a workgroup and in two ticket levels across workgroups (shine_arrive.hpp), so they
@@ -152,7 +151,7 @@ extern "C" int shine_time_step(const shine_tables* t, const shine_step_config* c
   a.pred = pred_out;
   a.loss_out = loss_out;
   a.cnt = wk.cnt, a.part = wk.part, a.run = wk.run, a.lpart = wk.lpart, a.lrun = wk.lrun;
-  const dim3 grid(point_step_blocks((n + 63) / 64));
+  const dim3 grid(term_blocks((n + 63) / 64));
   dispatch_levels_poly(cfg->n_levels, cfg->poly_int_on != 0, [&](auto l, auto p) {
     constexpr int LL = decltype(l)::value;
     constexpr bool PP = decltype(p)::value;

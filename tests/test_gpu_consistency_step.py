@@ -108,6 +108,39 @@ def test_pair_counts_and_the_reversed_gather(k):
     _check("k=%d gathered" % k, _fused(octree, dec, coord, (n - 1 - near_k).contiguous(), shift_k, idx=idx), ref)
 
 
+# ---- 2b. the grid sum's boundaries (a tile is 32 pairs, a workgroup 4 tiles, a first-level run 16 workgroups): exactly one full
+#      run, a run of one workgroup behind it, and every workgroup plus a grid-stride pass.  The case's pairs repeated.  The loss
+#      and the weight grads are the same bits from call to call at each size.  The fp64 oracle takes half a minute at 32769
+#      pairs, so there it is put together from its values on the case's pairs and on the pairs behind the whole repeats: the term
+#      is a sum over pairs divided by their count.
+@pytest.mark.parametrize("k", [2048, 2049, 32769])
+def test_grid_sum_boundary_pair_counts(k):
+    c = co.case("kitti_eik_L3")
+    _, octree, dec = _product("kitti_eik_L3")
+    coord, near, shift = _dev(c)
+    k0 = near.numel()
+    sel = torch.arange(k) % k0
+    near_k, shift_k = near[sel.cuda()].contiguous(), shift[sel.cuda()].contiguous()
+    a, b = _fused(octree, dec, coord, near_k, shift_k), _fused(octree, dec, coord, near_k, shift_k)
+    assert torch.equal(a[0], b[0]) and all(torch.equal(x, y) for x, y in zip(a[2], b[2])), k
+    oct_, mlp = no.wide_oracle(c.fx)
+    if k <= 2 * k0 + 64:
+        ref = co.consistency_term(oct_, mlp, c.pairs.coord_a[sel], c.pairs.coord_b[sel], WC)
+    else:
+        q, r = divmod(k, k0)
+        whole = co.consistency_term(oct_, mlp, c.pairs.coord_a, c.pairs.coord_b, WC)
+        rest = co.consistency_term(oct_, mlp, c.pairs.coord_a[:r], c.pairs.coord_b[:r], WC)
+        assert r > 0
+
+        def mix(x, y):
+            return (q * k0 * x.double() + r * y.double()) / k
+
+        ref = dict(loss=mix(whole["loss"], rest["loss"]),
+                   feat_grads=[mix(x, y) for x, y in zip(whole["feat_grads"], rest["feat_grads"])],
+                   mlp_grads=[mix(x, y) for x, y in zip(whole["mlp_grads"], rest["mlp_grads"])])
+    _check("k=%d" % k, a, ref)
+
+
 def test_no_pair_one_row_repeated_and_a_zero_shift():
     from shine_mapping_amd import ops
 

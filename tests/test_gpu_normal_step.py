@@ -121,6 +121,39 @@ def test_sizes_and_the_reversed_gather(n):
     _clear(octree, dec)
 
 
+# ---- 2b. the grid sum's boundaries (a tile is 64 rows, a workgroup 4 tiles, a first-level run 16 workgroups): exactly one full
+#      run, a run of one workgroup behind it, and every workgroup plus a grid-stride pass.  The fixture's 2048 rows repeated.  The
+#      loss and the weight grads are the same bits from call to call at each size.  The fp64 oracle takes half a minute at 65537
+#      rows, so there it is put together from its values on the 2048 rows and on the one row behind the 32 repeats: the term is a
+#      sum over surface rows divided by their count.
+@pytest.mark.parametrize("n", [4096, 4113, 65537])
+def test_grid_sum_boundary_sizes(n):
+    c = no.case("kitti_eik_L3")
+    _, octree, dec = _product("kitti_eik_L3")
+    n0 = c.coord.shape[0]
+    rows = torch.arange(n) % n0
+    coord, weight, normal = (t[rows].contiguous().cuda() for t in (c.coord, c.weight, c.normal))
+    a, b = _fused(octree, dec, coord, weight, normal), _fused(octree, dec, coord, weight, normal)
+    assert torch.equal(a[0], b[0]) and all(torch.equal(x, y) for x, y in zip(a[2], b[2])), n
+    oct_, mlp = no.wide_oracle(c.fx)
+    if n <= 2 * n0 + 64:
+        ref = no.normal_term(oct_, mlp, c.coord[rows], c.weight[rows], c.normal[rows], WN)
+    else:
+        q, r = divmod(n, n0)
+        whole = no.normal_term(oct_, mlp, c.coord, c.weight, c.normal, WN)
+        rest = no.normal_term(oct_, mlp, c.coord[:r], c.weight[:r], c.normal[:r], WN)
+        w0, wr = q * int((c.weight > 0).sum()), int((c.weight[:r] > 0).sum())
+        assert r > 0 and wr > 0
+
+        def mix(x, y):
+            return (w0 * x.double() + wr * y.double()) / (w0 + wr)
+
+        ref = dict(loss=mix(whole["loss"], rest["loss"]),
+                   feat_grads=[mix(x, y) for x, y in zip(whole["feat_grads"], rest["feat_grads"])],
+                   mlp_grads=[mix(x, y) for x, y in zip(whole["mlp_grads"], rest["mlp_grads"])])
+    _check("n=%d" % n, a, ref)
+
+
 # ---- 3. every instantiation against the GPU composite
 def _composite(octree, dec, coord, weight, normal, weight_n=WN):
     from shine_mapping_amd import get_gradient, losses

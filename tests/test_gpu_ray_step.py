@@ -144,6 +144,25 @@ def test_tile_edges_at_six_samples(n):
     _edge("kitti_eik_L3", 6, n, neus=(n % 2 == 0), stride=3 if n > 341 else None)
 
 
+# the grid sum's boundaries at six samples (10 rays per tile, 40 per workgroup): 641 rays are 17 workgroups — a full first-level run
+# and a run of one behind it, checked against the oracle above — and 10241 rays are 257, every workgroup plus a grid-stride pass.
+# The loss, the weight grads, the sigma_size grad, pred and dpred are the same bits from call to call at both sizes.  The fp64
+# oracle takes most of a minute on the 61446 rows of the larger one, so that size checks the deterministic outputs call to call only.
+@pytest.mark.parametrize("n", [641, 10241])
+def test_grid_sum_boundary_ray_counts_repeat_bit_identically(n):
+    c = _rays_of("kitti_eik_L3", 6, False)
+    _, octree, dec = _product("kitti_eik_L3", c.out_scale)
+    coord, weight, depth, ray_depth = _dev(c)
+    idx = (torch.arange(n) % c.ray_depth.numel()).to(torch.int32).cuda()
+    opts, ss = _opts(c.sigma, True, c.weight_e), _sigma(c.sigma_size)
+    a = _fused(octree, dec, coord, weight, depth, ray_depth, ss, opts, 6, False, idx=idx)
+    b = _fused(octree, dec, coord, weight, depth, ray_depth, ss, opts, 6, False, idx=idx)
+    assert torch.equal(a[0], b[0]) and all(torch.equal(x, y) for x, y in zip(a[2], b[2])), n
+    assert torch.equal(a[3], b[3]) and torch.equal(a[4], b[4]), n
+    assert all(bool(torch.isfinite(t).all()) for t in [a[0], a[3], a[4]] + a[1] + a[2]) and float(a[0]) > 0.0
+    assert float(a[2][6].abs().max()) > 0.0
+
+
 @pytest.mark.parametrize("S", [1, 2, 7, 8, 9, 16, 17, 32])
 def test_tile_edges_at_every_sample_count(S):
     for n in (1, 64 // S, 64 // S + 1):

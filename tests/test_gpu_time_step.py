@@ -124,6 +124,28 @@ def test_tile_edges_and_the_reversed_gather(n):
     _check("n=%d gathered" % n, got[:3] + (got[3].flip(0),), ref)  # (pred is written at the batch position)
 
 
+# ---- 2b. the grid sum's boundaries (a tile is 64 rows, a workgroup 4 tiles, a first-level run 16 workgroups): exactly one full
+#      run, a run of one workgroup behind it, and every workgroup plus a grid-stride pass.  The fixture's 2048 rows repeated.  The
+#      loss, the weight grads and pred are the same bits from call to call at each size.  The fp64 oracle takes half a minute at
+#      65537 rows and its two terms have two divisors, so that size checks the deterministic outputs call to call only.
+@pytest.mark.parametrize("n", [4096, 4113, 65537])
+def test_grid_sum_boundary_sizes(n):
+    name, kind = "kitti_eik_L3", "frames"
+    c = to.case(name, kind, True)
+    _, octree, dec = _product(name, kind)
+    rows = torch.arange(n) % c.coord.shape[0]
+    dev = [t[rows].contiguous().cuda() for t in (c.coord, c.label, c.weight, c.ts)]
+    opts = _opts(c.sigma, True, c.weight_e)
+    a, b = _fused(octree, dec, *dev, opts), _fused(octree, dec, *dev, opts)
+    assert torch.equal(a[0], b[0]) and all(torch.equal(x, y) for x, y in zip(a[2], b[2])) and torch.equal(a[3], b[3]), n
+    assert all(bool(torch.isfinite(t).all()) for t in [a[0], a[3]] + a[1] + a[2]) and float(a[0]) > 0.0
+    if n > 8192:
+        return
+    oct_, mlp = to.oracle_for(c.fx, c.w_t, wide=True)
+    ref = to.time_step(oct_, mlp, c.coord[rows], c.label[rows], c.weight[rows], c.ts[rows], c.sigma, eik=True, weight_e=c.weight_e)
+    _check("n=%d" % n, a, ref)
+
+
 def test_an_empty_batch_writes_a_zero_loss_and_nothing_else():
     from shine_mapping_amd import ops
 

@@ -18,6 +18,22 @@ def demangle(names):
         return names
 
 
+def short_name(pretty):
+    """`void shine::(anonymous namespace)::k_sem_step<4, true>(shine::SemStepArgs)` -> `k_sem_step<4, true>`: the kernel's
+    name with its template arguments, without the return type, the namespaces and the parameter list."""
+    s = pretty.replace("(anonymous namespace)::", "").replace("shine::", "")
+    depth = 0
+    for i, ch in enumerate(s):  # the parameter list opens at the first '(' outside the template arguments
+        if ch == "<":
+            depth += 1
+        elif ch == ">":
+            depth -= 1
+        elif ch == "(" and depth == 0:
+            s = s[:i]
+            break
+    return s[5:] if s.startswith("void ") else s
+
+
 def main():
     only = sys.argv[1:]
     print("# kernel | vgpr agpr sgpr | vgpr-spill sgpr-spill scratch-B lds-B | mfma valu salu ds global atomics")
@@ -44,7 +60,7 @@ def main():
                 ins = [l.split()[0] for l in body.splitlines() if l.startswith("\t") and l.strip() and not l.strip().startswith((";", "."))]
                 cnt = lambda p: sum(1 for i in ins if re.match(p, i))
                 k = meta[n]
-                short = re.sub(r"\(.*", "", pretty[n]).replace("shine::", "")
+                short = short_name(pretty[n])
                 print("%-44s | %3d %3d %3d | %4d %4d %5d %6d | %3d %4d %4d %3d %3d %3d" % (
                     short[:44], k.get("vgpr_count", 0), k.get("agpr_count", 0), k.get("sgpr_count", 0), k.get("vgpr_spill_count", 0),
                     k.get("sgpr_spill_count", 0), k.get("private_segment_fixed_size", 0), k.get("group_segment_fixed_size", 0),
