@@ -8,14 +8,79 @@ setup_optimizer builds torch.optim.Adam(betas=(0.9, 0.99), eps=config.adam_eps) 
 FusedAdam takes the same param_groups (so step_lr_decay, utils/tools.py:135-155, keeps working on
 ``opt.param_groups``) and applies the dense update to every tensor in ONE kernel, optionally clearing the grads
 in the same pass.  Numerics follow torch.optim.Adam (tests compare the two on the GPU).
+
+The stepped set of a call is every parameter that requires grad and holds one, in group order (_tensors()).  Graph-replayable
+steps read their step counter and learning rates from a DeviceState, and a captured graph bakes its pointers in, so the state
+keeps one invariant: all its tensors have ONE age (the device counter is the bias correction's t for each of them), it is bound
+to those tensors by identity — a stepped set with other members, even as many, is another set — and it is made, or folded back
+into the host ages and re-made, in _device_state() alone.
 """
 import ctypes as C
 import struct
+from typing import NamedTuple
 
 import torch
 
 from . import _ext, _lib
 from .autograd_ops import bump_param_epoch
+
+
+class Stepped(NamedTuple):
+    """one tensor of the stepped set: the parameter, its exp_avg and exp_avg_sq, its group's learning rate and weight decay"""
+    p: torch.Tensor
+    m: torch.Tensor
+    v: torch.Tensor
+    lr: float
+    wd: float
+
+
+class DeviceState(NamedTuple):
+    """what graph-replayable steps read on the device, and the tensors it counts for"""
+    state: torch.Tensor  # int64[8]: [0] steps taken, [1] the step's bias corrections; the rest is reserved (_make_dev_state)
+    lr: torch.Tensor  # float[n]: the learning rates of `params`, in their order (sync_lr)
+    params: tuple  # the stepped set the state was made for
+
+
+def _same(a, b) -> bool:
+    return len(a) == len(b) and all(x is y for x, y in zip(a, b))
+
+
+def _check(sel):
+    for t in sel:
+        p = t.p
+        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad.is_contiguous()):
+            raise ValueError("FusedAdam needs contiguous CUDA float32 parameters and grads")
+
+
+def _arrays(sel):
+    """the five arrays every Adam entry point takes for the (checked) selection: p, p.grad, exp_avg, exp_avg_sq, numel"""
+    _check(sel)
+    return (_lib.ptr_array([t.p.data_ptr() for t in sel]), _lib.ptr_array([t.p.grad.data_ptr() for t in sel]),
+            _lib.ptr_array([t.m.data_ptr() for t in sel]), _lib.ptr_array([t.v.data_ptr() for t in sel]),
+            _lib.i64_array([t.p.numel() for t in sel]))
+
+
+def _floats(vals):
+    return (C.c_float * len(vals))(*vals)
+
+
+def _flag_tensors(sel, row_flags):
+    """step()'s `row_flags` as one flag tensor (or None) per tensor of the selection; [] without flags.  The extension takes the
+    tensors, the C ABI their pointers (_flag_ptrs)."""
+    if not row_flags:
+        return []
+    if not isinstance(row_flags, dict):
+        raise ValueError("row_flags must be a dict {parameter: uint8 flag tensor}")
+    by_id = {id(p): f for p, f in row_flags.items()}
+    flags = [by_id.get(id(t.p)) for t in sel]
+    for t, f in zip(sel, flags):
+        if f is not None and not (f.is_cuda and f.dtype == torch.uint8 and f.is_contiguous() and f.numel() * 8 >= t.p.numel()):
+            raise ValueError("row_flags: one uint8 flag per row of the [rows, 8] table")
+    return flags
+
+
+def _flag_ptrs(flags):
+    return _lib.ptr_array([f.data_ptr() if f is not None else None for f in flags]) if flags else None
 
 
 class FusedAdam:
@@ -32,8 +97,7 @@ class FusedAdam:
         self.step_count = 0
         self.state = {}
         self._age = {}  # per-tensor step count, like torch.optim.Adam's state[p]["step"] (bias correction is per tensor)
-        self._dev = None  # (step_state int64[8], lr float[n]) for graph-replayable steps
-        self._dev_params = []  # the tensors those steps update (the set the device-side counter counts for)
+        self._dev = None  # the DeviceState of graph-replayable steps (_device_state)
         self._fast = None  # (params, exp_avg, exp_avg_sq, age) of the last eager step when every tensor had the same age (_step_fast)
 
     # ------------------------------------------------------------------ torch.optim.Optimizer's checkpoint interface
@@ -48,7 +112,7 @@ class FusedAdam:
         extra = {}
         if self._dev is not None:
             more = self.steps_taken() - self.step_count
-            extra = {id(p): more for p in self._dev_params}
+            extra = {id(p): more for p in self._dev.params}
         state, groups, k = {}, [], 0
         for g in self.param_groups:
             idx = []
@@ -112,7 +176,7 @@ class FusedAdam:
                     st = (torch.zeros_like(p, memory_format=torch.contiguous_format),
                           torch.zeros_like(p, memory_format=torch.contiguous_format))
                     self.state[p] = st
-                out.append((p, st[0], st[1], float(g["lr"]), float(g["weight_decay"])))
+                out.append(Stepped(p, st[0], st[1], float(g["lr"]), float(g["weight_decay"])))
         return out
 
     def zero_grad(self, set_to_none=False):
@@ -127,18 +191,18 @@ class FusedAdam:
     def sync_lr(self):
         """Graph-replayable mode: push the param_groups' learning rates to the device copy the captured step reads
         (call after step_lr_decay, utils/tools.py:135-155; outside the graph)."""
-        if self._dev is not None:
-            ts = self._tensors()
-            self._dev[1].copy_(torch.tensor([t[3] for t in ts], dtype=torch.float32), non_blocking=False)
+        if self._dev is not None:  # (the state's own tensors, whichever of them hold a grad right now)
+            lr = {id(p): float(g["lr"]) for g in self.param_groups for p in g["params"]}
+            self._dev.lr.copy_(torch.tensor([lr[id(p)] for p in self._dev.params], dtype=torch.float32), non_blocking=False)
 
     def steps_taken(self) -> int:
         """Optimiser steps so far (host counter, or the device counter once graph-replayable steps were used)."""
-        return int(self._dev[0][0].item()) if self._dev is not None else self.step_count
+        return int(self._dev.state[0].item()) if self._dev is not None else self.step_count
 
     def device_state(self):
         """The device-side step state of graph-replayable steps (int64[8]; None before the first such step): hand it to the
         fused step (StepOptions.adam_state) and the step's reduction launch advances it — then call step(..., advanced=True)."""
-        return None if self._dev is None else self._dev[0]
+        return None if self._dev is None else self._dev.state
 
     def _make_dev_state(self, dev):
         """[0] steps taken, [1] bias corrections (floats, written by the advance), [2] / [3] beta1^t / beta2^t as doubles"""
@@ -156,11 +220,47 @@ class FusedAdam:
         re-made): only the tensors that were part of the device-state set took those steps — a tensor that was frozen
         meanwhile keeps its age, like torch.optim.Adam's per-parameter state["step"]."""
         taken = self.steps_taken()
-        for p in self._dev_params:
+        for p in self._dev.params:
             self._age[p] = self._age.get(p, 0) + (taken - self.step_count)
         self.step_count = taken
         self._dev = None
-        self._dev_params = []
+
+    def _device_state(self, ts) -> DeviceState:
+        """The live device state for the stepped set `ts`: the one there is if it was made for these very tensors, else a new one.
+        A set that changed while the device-side counter was live (e.g. the decoder was frozen / unfrozen) first has the steps
+        the graph took folded back into the host counters, or the bias correction would silently restart from the stale host
+        count; a state is only made for tensors of one age, the optimiser's."""
+        params = tuple(t.p for t in ts)
+        if self._dev is not None and not _same(self._dev.params, params):
+            self._fold_device_steps()
+        if self._dev is None:
+            if {self._age.get(p, 0) for p in params} != {self.step_count}:
+                raise NotImplementedError("graph-replayable FusedAdam steps need all tensors to have the same age "
+                                          "(a parameter that started receiving grads later: use eager steps)")
+            dev = params[0].device
+            lr = _lib.device_constants([t.lr for t in ts], torch.float32, dev)
+            self._dev = DeviceState(self._make_dev_state(dev), lr, params)
+        return self._dev
+
+    def _stepped_of_state(self, who, how):
+        """the stepped set, for a launch that reads the device state as it is: there must be one, made for this set"""
+        if self._dev is None:
+            raise RuntimeError("%s needs the device-side step state: %s first" % (who, how))
+        ts = self._tensors()
+        if not _same(self._dev.params, [t.p for t in ts]):
+            raise RuntimeError("%s: the set of tensors changed since the device state was made" % who)
+        return ts
+
+    def _launch_dev(self, sel, lr_ptr, bits, flags):
+        """shine_adam_step_dev on `sel`: step counter and bias corrections from the device state, the learning rates from `lr_ptr`
+        (the selection's first entry of the state's lr), bits: 1 clear the grads | 2 the step was counted already"""
+        _lib.check(
+            _lib.lib().shine_adam_step_dev(
+                len(sel), *_arrays(sel), lr_ptr, _floats([t.wd for t in sel]), float(self.betas[0]), float(self.betas[1]),
+                float(self.eps), self._dev.state.data_ptr(), bits, flags, _lib.current_stream_handle(),
+            ),
+            "shine_adam_step_dev",
+        )
 
     @torch.no_grad()
     def step(self, zero_grad=False, graph_safe=False, advanced=False, row_flags=None):
@@ -180,55 +280,21 @@ class FusedAdam:
         if not ts:
             return
         bump_param_epoch()  # (the parameters change behind torch's back: tensor._version does not move)
-        n = len(ts)
-        ages = [self._age.get(t[0], 0) for t in ts]
         if graph_safe:
-            if len(set(ages)) != 1 or (self._dev is None and ages[0] != self.step_count):
-                raise NotImplementedError("graph-replayable FusedAdam steps need all tensors to have the same age "
-                                          "(a parameter that started receiving grads later: use eager steps)")
-            dev = ts[0][0].device
-            if self._dev is not None and self._dev[1].numel() != n:
-                # the set of tensors that receive grads changed while the device-side counter was live (e.g. the decoder was
-                # frozen / unfrozen): fold the steps the graph took back into the host counters before the state is re-made,
-                # or the bias correction would silently restart from the stale host count
-                self._fold_device_steps()
-                ages = [self._age.get(t[0], 0) for t in ts]
-                if len(set(ages)) != 1 or ages[0] != self.step_count:
-                    raise NotImplementedError("graph-replayable FusedAdam steps need all tensors to have the same age "
-                                              "(a parameter that started receiving grads later: use eager steps)")
-            if self._dev is None:
-                # int64[8]: [0] steps taken, [1] the step's bias corrections; the rest is reserved (zeros)
-                self._dev = (self._make_dev_state(dev), _lib.device_constants([t[3] for t in ts], torch.float32, dev))
-                self._dev_params = [t[0] for t in ts]
-            for p, m, v, _, _ in ts:
-                if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad.is_contiguous()):
-                    raise ValueError("FusedAdam needs contiguous CUDA float32 parameters and grads")
-            wd = (C.c_float * n)(*[t[4] for t in ts])
-            flags = self._flag_array(ts, row_flags)
-            _lib.check(
-                _lib.lib().shine_adam_step_dev(
-                    n, _lib.ptr_array([t[0].data_ptr() for t in ts]), _lib.ptr_array([t[0].grad.data_ptr() for t in ts]),
-                    _lib.ptr_array([t[1].data_ptr() for t in ts]), _lib.ptr_array([t[2].data_ptr() for t in ts]),
-                    _lib.i64_array([t[0].numel() for t in ts]), self._dev[1].data_ptr(), wd, float(self.betas[0]),
-                    float(self.betas[1]), float(self.eps), self._dev[0].data_ptr(),
-                    (1 if zero_grad else 0) | (2 if advanced else 0), flags, _lib.current_stream_handle(),
-                ),
-                "shine_adam_step_dev",
-            )
+            lr = self._device_state(ts).lr
+            self._launch_dev(ts, lr.data_ptr(), (1 if zero_grad else 0) | (2 if advanced else 0),
+                             _flag_ptrs(_flag_tensors(ts, row_flags)))
             return
         if self._dev is not None:  # continue the count a graph advanced on the device
             self._fold_device_steps()
-            ages = [self._age.get(t[0], 0) for t in ts]
+        ages = [self._age.get(t.p, 0) for t in ts]
         self.step_count += 1
-        if len(set(ages)) > 1:  # torch.optim.Adam semantics: one launch per distinct age (normally there is one)
-            for age in sorted(set(ages)):
-                self._launch([t for t, a in zip(ts, ages) if a == age], age + 1, zero_grad, row_flags)
-        else:
-            self._launch(ts, ages[0] + 1, zero_grad, row_flags)
+        for age in sorted(set(ages)):  # torch.optim.Adam semantics: one launch per distinct age (normally there is one)
+            self._launch([t for t, a in zip(ts, ages) if a == age], age + 1, zero_grad, row_flags)
         for t in ts:
-            self._age[t[0]] = self._age.get(t[0], 0) + 1
+            self._age[t.p] = self._age.get(t.p, 0) + 1
         if len(set(ages)) == 1 and not row_flags:
-            self._fast = ([t[0] for t in ts], [t[1] for t in ts], [t[2] for t in ts], ages[0] + 1)
+            self._fast = ([t.p for t in ts], [t.m for t in ts], [t.v for t in ts], ages[0] + 1)
 
     def _step_fast(self, zero_grad) -> bool:
         """The eager step of a loop in steady state (the same tensors received grads as in the last step, all of one age): the
@@ -263,52 +329,132 @@ class FusedAdam:
         self._fast = (params, m, v, age + 1)
         return True
 
-    @staticmethod
-    def _flag_array(ts, row_flags):
-        if not row_flags:
-            return None
-        by_id = {id(p): f for p, f in row_flags.items()} if isinstance(row_flags, dict) else None
-        if by_id is None:
-            raise ValueError("row_flags must be a dict {parameter: uint8 flag tensor}")
-        ptrs = []
-        for t in ts:
-            f = by_id.get(id(t[0]))
-            if f is not None and not (f.is_cuda and f.dtype == torch.uint8 and f.is_contiguous()
-                                      and f.numel() * 8 >= t[0].numel()):
-                raise ValueError("row_flags: one uint8 flag per row of the [rows, 8] table")
-            ptrs.append(f.data_ptr() if f is not None else None)
-        return _lib.ptr_array(ptrs)
-
     def _launch(self, ts, step, zero_grad, row_flags=None):
         n = len(ts)
         if n > 16:
             raise NotImplementedError("FusedAdam handles up to 16 tensors (decoder 6 + feature levels)")
-        for p, m, v, _, _ in ts:
-            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad.is_contiguous()):
-                raise ValueError("FusedAdam needs contiguous CUDA float32 parameters and grads")
+        b1, b2, eps = float(self.betas[0]), float(self.betas[1]), float(self.eps)
         ext = _ext.module()
         if ext is not None:  # (one call with tensor lists instead of five ctypes pointer arrays)
-            flags = []
-            if row_flags:
-                self._flag_array(ts, row_flags)  # (validates)
-                by_id = {id(p): f for p, f in row_flags.items()}
-                flags = [by_id.get(id(t[0])) for t in ts]
-            ext.adam_step([t[0] for t in ts], [t[0].grad for t in ts], [t[1] for t in ts], [t[2] for t in ts], [t[3] for t in ts],
-                          [t[4] for t in ts], float(self.betas[0]), float(self.betas[1]), float(self.eps), int(step),
-                          bool(zero_grad), flags)
+            _check(ts)
+            ext.adam_step([t.p for t in ts], [t.p.grad for t in ts], [t.m for t in ts], [t.v for t in ts], [t.lr for t in ts],
+                          [t.wd for t in ts], b1, b2, eps, int(step), bool(zero_grad), _flag_tensors(ts, row_flags))
             return
-        lr = (C.c_float * n)(*[t[3] for t in ts])
-        wd = (C.c_float * n)(*[t[4] for t in ts])
         _lib.check(
             _lib.lib().shine_adam_step(
-                n, _lib.ptr_array([t[0].data_ptr() for t in ts]), _lib.ptr_array([t[0].grad.data_ptr() for t in ts]),
-                _lib.ptr_array([t[1].data_ptr() for t in ts]), _lib.ptr_array([t[2].data_ptr() for t in ts]),
-                _lib.i64_array([t[0].numel() for t in ts]), lr, wd, float(self.betas[0]), float(self.betas[1]),
-                float(self.eps), int(step), 1 if zero_grad else 0, self._flag_array(ts, row_flags),
-                _lib.current_stream_handle(),
+                n, *_arrays(ts), _floats([t.lr for t in ts]), _floats([t.wd for t in ts]), b1, b2, eps, int(step),
+                1 if zero_grad else 0, _flag_ptrs(_flag_tensors(ts, row_flags)), _lib.current_stream_handle(),
             ),
             "shine_adam_step",
         )
+
+    def prepare_graph_safe(self, skip=()):
+        """Create the device-side step state (what the first step(graph_safe=True) does) without taking a step, so that an
+        iteration can be captured into a HIP graph without an eager one in front of it.
+        `skip`: parameters that never receive a gradient (the semantic decoder's lout): they get no zero gradient here, so they stay
+        out of the stepped set as torch.optim.Adam keeps them out — with weight decay a zero gradient would still move them."""
+        skip = {id(p) for p in skip}
+        # the dense gradient tensors the fused step would create on its first launch and the optimiser's exp_avg / exp_avg_sq, for
+        # every parameter that has neither yet: views of ONE zero-filled buffer (incremental mapping builds a new optimiser every
+        # frame, shine_incre.py:107-109: 27 small fills per frame otherwise)
+        fresh = [p for g in self.param_groups for p in g["params"]
+                 if p.requires_grad and p.grad is None and p not in self.state and p.is_cuda and p.dtype == torch.float32
+                 and id(p) not in skip]
+        if fresh:
+            sizes = [(p.numel() + 3) // 4 * 4 for p in fresh]  # (16-byte aligned views)
+            total = sum(sizes)
+            flat = torch.zeros(3 * total, dtype=torch.float32, device=fresh[0].device)
+            parts = flat.split(sizes * 3)  # (one call for the 3 x len(fresh) views: a slice + view each was ~120 us per frame)
+            k = len(fresh)
+            for i, (p, sz) in enumerate(zip(fresh, sizes)):
+                n = p.numel()
+                g, m, v = parts[i], parts[k + i], parts[2 * k + i]
+                if n != sz:
+                    g, m, v = g[:n], m[:n], v[:n]
+                p.grad = g.view(p.shape)
+                self.state[p] = (m.view(p.shape), v.view(p.shape))
+        for g in self.param_groups:
+            for p in g["params"]:
+                if p.requires_grad and p.grad is None and id(p) not in skip:
+                    p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        ts = self._tensors()
+        if not ts:
+            raise RuntimeError("prepare_graph_safe: no parameter requires grad")
+        return self._device_state(ts).state
+
+    def finish_iteration(self, pending, regulariser=None, next_draw=None, active_flags=None, graph=None, others=()):
+        """The tail of an iteration in ONE launch (shine_finish_iteration): `pending` is the dict a
+        fused_train_step(..., pending=...) filled — its partial sums are added up where they are consumed, the regulariser
+        (regulariser = dict(lambda_forget, touched, out) as for ops.fused_regularization) is evaluated on the touched rows, Adam
+        is applied to every tensor and the grads are cleared; next_draw = SortedPool.next_draw(...) also draws the next
+        iteration's batch in the same launch.  Graph-replayable only: the step must have counted the optimiser
+        step (StepOptions.adam_state = device_state()).
+        active_flags (the per-level uint8 flags the step was given as `touched`): EXACT active-row Adam — the flags are kept sticky
+        and rows whose flag is 0 (no gradient since this optimiser and the flags were created: m = v = g = 0, which torch's Adam
+        leaves bit for bit unchanged) are not read.  The caller zeroes the flags whenever it creates the optimiser.
+        graph (loop.IterationGraph): nothing is launched — the launch becomes the tail node of the library-built iteration graph.
+        others: tensors of this optimiser that a launch of their own steps (step_tensors_dev: the semantic head) — the tail selects
+        the feature tables and the decoder and leaves these alone."""
+        ts = self._stepped_of_state("finish_iteration", "run one step(graph_safe=True)")
+        bump_param_epoch()
+        octree, decoder = pending["octree"], pending["decoder"]
+        by_param = {id(t.p): i for i, t in enumerate(ts)}
+        order = list(octree.hier_features) + (list(decoder.fused_params()) if pending["dec_grad"] else [])
+        other_ids = {id(p) for p in others}
+        if (len(order) + len(other_ids) != len(ts) or any(id(p) not in by_param for p in order)
+                or any(i not in by_param for i in other_ids) or any(id(p) in other_ids for p in order)):
+            raise NotImplementedError("finish_iteration: the optimiser must hold exactly the feature tables and the decoder tensors "
+                                      "that receive grads")
+        pos = [by_param[id(p)] for p in order]  # (where each tensor's learning rate stands in the device state's lr)
+        sel = [ts[i] for i in pos]
+        arrays = _arrays(sel)
+        n = len(sel)
+        L = len(octree.hier_features)
+        cfg = pending["cfg"]
+        lam, last, imp, touched, grad_on, reg_out = 0.0, None, None, None, None, None
+        if regulariser is not None and float(regulariser["lambda_forget"]) != 0.0:
+            lam = float(regulariser["lambda_forget"])
+            keep = pending.setdefault("keep", [])  # (contiguous copies must outlive the launch)
+            lasts = [t.detach().contiguous() for t in octree.features_last_frame]
+            imps = [t.contiguous() for t in octree.importance_weight]
+            keep += lasts + imps
+            last = _lib.ptr_array([t.data_ptr() for t in lasts])
+            imp = _lib.ptr_array([t.data_ptr() for t in imps])
+            touched = _lib.ptr_array([t.data_ptr() for t in regulariser["touched"]])
+            grad_on = (C.c_int32 * L)(*[1 if g else 0 for g in octree._reg_grad_on])
+            reg_out = regulariser["out"].data_ptr()
+        if active_flags is not None:
+            if regulariser is not None and any(a is not b for a, b in zip(active_flags, regulariser["touched"])):
+                raise ValueError("finish_iteration: active_flags must be the regulariser's touched flags")
+            touched = _lib.ptr_array([t.data_ptr() for t in active_flags])
+        ns = pending["n_surf"]
+        lib = _lib.lib()
+        entry = lib.shine_finish_iteration if graph is None else \
+            (lambda *a: lib.shine_iter_graph_set_finish(graph.handle, *a[:-1]))  # (the same arguments minus the stream)
+        pending.setdefault("keep", []).extend(x for t in sel for x in (t.m, t.v))  # (the optimiser state the launch names)
+        _lib.check(
+            entry(
+                C.byref(cfg), pending["n"], pending["workspace"].data_ptr(), ns.data_ptr() if ns is not None else None,
+                pending["loss_parts"].data_ptr(), last, imp, touched, grad_on, lam, reg_out, n, *arrays,
+                self._dev.lr.data_ptr(), (C.c_int32 * n)(*pos), _floats([t.wd for t in sel]), float(self.betas[0]),
+                float(self.betas[1]), float(self.eps), self._dev.state.data_ptr(),
+                C.byref(next_draw) if next_draw is not None else None, 1 if active_flags is not None else 0,
+                _lib.current_stream_handle()),
+            "shine_finish_iteration")
+
+    @torch.no_grad()
+    def step_tensors_dev(self, params):
+        """One graph-replayable Adam launch (shine_adam_step_dev) on `params` alone — a run of consecutive tensors of the
+        device-state set, e.g. the semantic head's six — with the step state another launch of the iteration already advanced
+        (the fused step, StepOptions.adam_state) and the grads cleared in the same pass: zero_grad bits 1 | 2.  The learning rates
+        are read from the device copy sync_lr() maintains."""
+        ts = self._stepped_of_state("step_tensors_dev", "call prepare_graph_safe()")
+        by_param = {id(t.p): i for i, t in enumerate(ts)}
+        pos = [by_param.get(id(p)) for p in params]
+        if not pos or any(i is None for i in pos) or pos != list(range(pos[0], pos[0] + len(pos))):
+            raise NotImplementedError("step_tensors_dev: the tensors must be consecutive members of the optimiser's stepped set")
+        bump_param_epoch()
+        self._launch_dev([ts[i] for i in pos], self._dev.lr.data_ptr() + 4 * pos[0], 1 | 2, None)
 
 
 def setup_optimizer(config, octree_feat, mlp_geo_param, mlp_sem_param=None, sigma_size=None):
@@ -336,153 +482,3 @@ def setup_optimizer(config, octree_feat, mlp_geo_param, mlp_sem_param=None, sigm
     if ray_loss:
         groups.append({"params": [sigma_size], "lr": config.lr})
     return FusedAdam(groups, betas=(0.9, 0.99), eps=getattr(config, "adam_eps", 1e-15))
-
-
-def _prepare_graph_safe(self, skip=()):
-    """Create the device-side step state (what the first step(graph_safe=True) does) without taking a step, so that an
-    iteration can be captured into a HIP graph without an eager one in front of it.
-    `skip`: parameters that never receive a gradient (the semantic decoder's lout): they get no zero gradient here, so they stay
-    out of the stepped set as torch.optim.Adam keeps them out — with weight decay a zero gradient would still move them."""
-    skip = {id(p) for p in skip}
-    # the dense gradient tensors the fused step would create on its first launch and the optimiser's exp_avg / exp_avg_sq, for
-    # every parameter that has neither yet: views of ONE zero-filled buffer (incremental mapping builds a new optimiser every
-    # frame, shine_incre.py:107-109: 27 small fills per frame otherwise)
-    fresh = [p for g in self.param_groups for p in g["params"]
-             if p.requires_grad and p.grad is None and p not in self.state and p.is_cuda and p.dtype == torch.float32
-             and id(p) not in skip]
-    if fresh:
-        sizes = [(p.numel() + 3) // 4 * 4 for p in fresh]  # (16-byte aligned views)
-        total = sum(sizes)
-        flat = torch.zeros(3 * total, dtype=torch.float32, device=fresh[0].device)
-        parts = flat.split(sizes * 3)  # (one call for the 3 x len(fresh) views: a slice + view each was ~120 us per frame)
-        k = len(fresh)
-        for i, (p, sz) in enumerate(zip(fresh, sizes)):
-            n = p.numel()
-            g, m, v = parts[i], parts[k + i], parts[2 * k + i]
-            if n != sz:
-                g, m, v = g[:n], m[:n], v[:n]
-            p.grad = g.view(p.shape)
-            self.state[p] = (m.view(p.shape), v.view(p.shape))
-    for g in self.param_groups:
-        for p in g["params"]:
-            if p.requires_grad and p.grad is None and id(p) not in skip:
-                p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
-    ts = self._tensors()
-    if not ts:
-        raise RuntimeError("prepare_graph_safe: no parameter requires grad")
-    ages = [self._age.get(t[0], 0) for t in ts]
-    if len(set(ages)) != 1 or (self._dev is None and ages[0] != self.step_count):
-        raise NotImplementedError("graph-replayable FusedAdam steps need all tensors to have the same age")
-    if self._dev is None or self._dev[1].numel() != len(ts):
-        if self._dev is not None:
-            self._fold_device_steps()
-        dev = ts[0][0].device
-        self._dev = (self._make_dev_state(dev), _lib.device_constants([t[3] for t in ts], torch.float32, dev))
-        self._dev_params = [t[0] for t in ts]
-    return self._dev[0]
-
-
-def _finish_iteration(self, pending, regulariser=None, next_draw=None, active_flags=None, graph=None, others=()):
-    """The tail of an iteration in ONE launch (shine_finish_iteration): `pending` is the dict a
-    fused_train_step(..., pending=...) filled — its partial sums are added up where they are consumed, the regulariser
-    (regulariser = dict(lambda_forget, touched, out) as for ops.fused_regularization) is evaluated on the touched rows, Adam
-    is applied to every tensor and the grads are cleared; next_draw = SortedPool.next_draw(...) also draws the next
-    iteration's batch in the same launch.  Graph-replayable only: the step must have counted the optimiser
-    step (StepOptions.adam_state = device_state()).
-    active_flags (the per-level uint8 flags the step was given as `touched`): EXACT active-row Adam — the flags are kept sticky
-    and rows whose flag is 0 (no gradient since this optimiser and the flags were created: m = v = g = 0, which torch's Adam
-    leaves bit for bit unchanged) are not read.  The caller zeroes the flags whenever it creates the optimiser.
-    graph (loop.IterationGraph): nothing is launched — the launch becomes the tail node of the library-built iteration graph.
-    others: tensors of this optimiser that a launch of their own steps (step_tensors_dev: the semantic head) — the tail selects
-    the feature tables and the decoder and leaves these alone."""
-    if self._dev is None:
-        raise RuntimeError("finish_iteration needs the device-side step state: run one step(graph_safe=True) first")
-    bump_param_epoch()
-    octree, decoder = pending["octree"], pending["decoder"]
-    ts = self._tensors()
-    by_param = {id(t[0]): (i, t) for i, t in enumerate(ts)}
-    order = list(octree.hier_features) + (list(decoder.fused_params()) if pending["dec_grad"] else [])
-    other_ids = {id(p) for p in others}
-    if (len(order) + len(other_ids) != len(ts) or any(id(p) not in by_param for p in order)
-            or any(i not in by_param for i in other_ids) or any(id(p) in other_ids for p in order)):
-        raise NotImplementedError("finish_iteration: the optimiser must hold exactly the feature tables and the decoder tensors "
-                                  "that receive grads")
-    if self._dev[1].numel() != len(ts):
-        raise RuntimeError("finish_iteration: the set of tensors changed since the device state was made")
-    sel = [by_param[id(p)] for p in order]
-    for _, (p, m, v, _, _) in sel:
-        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad.is_contiguous()):
-            raise ValueError("FusedAdam needs contiguous CUDA float32 parameters and grads")
-    n = len(sel)
-    L = len(octree.hier_features)
-    cfg = pending["cfg"]
-    lam, last, imp, touched, grad_on, reg_out = 0.0, None, None, None, None, None
-    if regulariser is not None and float(regulariser["lambda_forget"]) != 0.0:
-        lam = float(regulariser["lambda_forget"])
-        keep = pending.setdefault("keep", [])  # (contiguous copies must outlive the launch)
-        lasts = [t.detach().contiguous() for t in octree.features_last_frame]
-        imps = [t.contiguous() for t in octree.importance_weight]
-        keep += lasts + imps
-        last = _lib.ptr_array([t.data_ptr() for t in lasts])
-        imp = _lib.ptr_array([t.data_ptr() for t in imps])
-        touched = _lib.ptr_array([t.data_ptr() for t in regulariser["touched"]])
-        grad_on = (C.c_int32 * L)(*[1 if g else 0 for g in octree._reg_grad_on])
-        reg_out = regulariser["out"].data_ptr()
-    if active_flags is not None:
-        if regulariser is not None and any(a is not b for a, b in zip(active_flags, regulariser["touched"])):
-            raise ValueError("finish_iteration: active_flags must be the regulariser's touched flags")
-        touched = _lib.ptr_array([t.data_ptr() for t in active_flags])
-    ns = pending["n_surf"]
-    lib = _lib.lib()
-    entry = lib.shine_finish_iteration if graph is None else \
-        (lambda *a: lib.shine_iter_graph_set_finish(graph.handle, *a[:-1]))  # (the same arguments minus the stream)
-    pending.setdefault("keep", []).extend(t[k] for _, t in sel for k in (1, 2))  # (the optimiser state the launch names)
-    _lib.check(
-        entry(
-            C.byref(cfg), pending["n"], pending["workspace"].data_ptr(), ns.data_ptr() if ns is not None else None,
-            pending["loss_parts"].data_ptr(), last, imp, touched, grad_on, lam, reg_out, n,
-            _lib.ptr_array([t[0].data_ptr() for _, t in sel]), _lib.ptr_array([t[0].grad.data_ptr() for _, t in sel]),
-            _lib.ptr_array([t[1].data_ptr() for _, t in sel]), _lib.ptr_array([t[2].data_ptr() for _, t in sel]),
-            _lib.i64_array([t[0].numel() for _, t in sel]), self._dev[1].data_ptr(), (C.c_int32 * n)(*[i for i, _ in sel]),
-            (C.c_float * n)(*[t[4] for _, t in sel]), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-            self._dev[0].data_ptr(), C.byref(next_draw) if next_draw is not None else None,
-            1 if active_flags is not None else 0, _lib.current_stream_handle()),
-        "shine_finish_iteration")
-
-
-@torch.no_grad()
-def _step_tensors_dev(self, params):
-    """One graph-replayable Adam launch (shine_adam_step_dev) on `params` alone — a run of consecutive tensors of the
-    device-state set, e.g. the semantic head's six — with the step state another launch of the iteration already advanced
-    (the fused step, StepOptions.adam_state) and the grads cleared in the same pass: zero_grad bits 1 | 2.  The learning rates
-    are read from the device copy sync_lr() maintains."""
-    if self._dev is None:
-        raise RuntimeError("step_tensors_dev needs the device-side step state: call prepare_graph_safe() first")
-    ts = self._tensors()
-    if self._dev[1].numel() != len(ts):
-        raise RuntimeError("step_tensors_dev: the set of tensors changed since the device state was made")
-    by_param = {id(t[0]): i for i, t in enumerate(ts)}
-    pos = [by_param.get(id(p)) for p in params]
-    if not pos or any(i is None for i in pos) or pos != list(range(pos[0], pos[0] + len(pos))):
-        raise NotImplementedError("step_tensors_dev: the tensors must be consecutive members of the optimiser's stepped set")
-    sel = [ts[i] for i in pos]
-    for p, m, v, _, _ in sel:
-        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad.is_contiguous()):
-            raise ValueError("FusedAdam needs contiguous CUDA float32 parameters and grads")
-    n = len(sel)
-    bump_param_epoch()
-    _lib.check(
-        _lib.lib().shine_adam_step_dev(
-            n, _lib.ptr_array([t[0].data_ptr() for t in sel]), _lib.ptr_array([t[0].grad.data_ptr() for t in sel]),
-            _lib.ptr_array([t[1].data_ptr() for t in sel]), _lib.ptr_array([t[2].data_ptr() for t in sel]),
-            _lib.i64_array([t[0].numel() for t in sel]), self._dev[1].data_ptr() + 4 * pos[0],
-            (C.c_float * n)(*[t[4] for t in sel]), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-            self._dev[0].data_ptr(), 1 | 2, None, _lib.current_stream_handle(),
-        ),
-        "shine_adam_step_dev",
-    )
-
-
-FusedAdam.finish_iteration = _finish_iteration
-FusedAdam.step_tensors_dev = _step_tensors_dev
-FusedAdam.prepare_graph_safe = _prepare_graph_safe
